@@ -30,7 +30,7 @@ kernel's live-measured duration, PMC traffic from the committed counter passes o
 `roofline.binding`: the roof that actually binds these kernels -- fp64 vector issue -- with achieved,
 peak, frac, the useful (recurrence) share and VALU busy.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--kernel direct|recurrence]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--kernel direct|recurrence] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -250,6 +250,28 @@ class Timer(object):
         return time.perf_counter() - t0
 
 
+DUMP_BYTES_MAX = 64 << 20      # --dump-outputs: the most it writes in all
+DUMP_PIXELS = 1 << 21          # model-image values sampled per run (16 MB of float64, + their flat indices)
+
+
+def pixel_sample(size, n):
+    """n flat indices into an image stack of `size` values, sorted: the same seeded sample on every run of every build"""
+    if size <= n:
+        return np.arange(size)
+    return np.sort(np.random.RandomState(12345).choice(size, n, replace=False))
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> what the timed path computed in its last step) as <path>/<name>.npy in float64"""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        raise RuntimeError("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_BYTES_MAX))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def reduce_over_ranks(torch, world, local, dt, sums):
     """max over ranks of the elapsed time, sum over ranks of the work counters"""
     if world == 1:
@@ -459,6 +481,7 @@ def run_render(args, env):
 
     def step():
         ll, llb = field.images.render(field.sources, loglik=True)
+        last["ret"] = (ll, llb)
         if reducer is not None:
             reducer.submit_device([field.images])     # the sums go from the library's device memory straight into the collective
             if len(reducer.pending) > 1:
@@ -477,6 +500,13 @@ def run_render(args, env):
         if reducer is not None:
             last["llb"] = reducer.drain()[-1]
     dt = Timer(dist, torch).run(step, args.warmup, args.steps, after_warmup, finish, prime=100)
+    if args.dump_outputs and rank == 0:
+        # before the legs below render again under other settings: the last timed step's return value and model images
+        lam = field.images.model_images().ravel()
+        idx = pixel_sample(lam.size, DUMP_PIXELS)
+        dump_outputs(args.dump_outputs, {"loglik": last["ret"][0], "loglik_band": last["ret"][1],
+                                         "model_images_sample": lam[idx], "model_images_sample_index": idx})
+        del lam
     t_render, n_render, render_kernel = ctx.profile_render()
     ctx.profile(1)
     for _ in range(20):                 # untimed: prep / binning / reduction durations for `kernels_ms`
@@ -1032,6 +1062,7 @@ def run_fields(args, env):
         per = [lane(0)] if pool is None else list(pool.map(lane, range(n_str)))
         for i in range(len(fields)):
             llb += per[i % n_str][i // n_str]
+        last["per"] = per
         if reducer is not None:
             reducer.submit_device([f.images for f in fields])     # summed on the device, then all-reduced: no host hop before the collective
             if len(reducer.pending) > 1:
@@ -1048,6 +1079,14 @@ def run_fields(args, env):
         if reducer is not None:
             last["llb"] = reducer.drain()[-1]
     dt = Timer(dist, torch).run(step, args.warmup, args.steps, after_warmup, finish, prime=max(2, 100 // max(K // world, 1)))
+    if args.dump_outputs and rank == 0:
+        # this rank's fields in field order: the per-band log-likelihoods of each, and the same pixel sample of each field's model images
+        n = len(fields)
+        idx = pixel_sample(B * fields[0].H * fields[0].W, DUMP_PIXELS // n)
+        dump_outputs(args.dump_outputs, {
+            "loglik_band_per_field": np.array([last["per"][i % n_str][i // n_str] for i in range(n)]),
+            "model_images_sample": np.array([f.images.model_images().ravel()[idx] for f in fields]),
+            "model_images_sample_index": idx})
     tn = [cx.profile_render()[:2] for cx in ctxs]
     n_render = sum(n for _, n in tn)
     t_render = sum(t * n for t, n in tn) / max(n_render, 1)
@@ -1204,10 +1243,12 @@ def run_gibbs(args, env):
                                     seed=1 + 1000 * rank, slice_args=slice_args)   # one independent chain per rank
     reducer = dist.LoglikReducer(1, device=local, depth=2) if (world > 1 and not strong) else None
     trace = []
+    last_ll = [None]
 
     def step():
         g.sweep(shapes=args.shapes)
         ll = np.array([g.log_likelihood()])          # the chain's trace (one render)
+        last_ll[0] = ll[0]
         if reducer is not None:
             reducer.submit(ll)
             if len(reducer.pending) > 1:
@@ -1226,6 +1267,9 @@ def run_gibbs(args, env):
             trace.append(float(reducer.drain()[-1][0]))
     ll0 = g.log_likelihood()
     dt = Timer(dist, torch).run(step, args.warmup, args.steps, after_warmup, finish, prime=3)
+    if args.dump_outputs and rank == 0:
+        # the chain's state after the last timed sweep and that sweep's field log-likelihood
+        dump_outputs(args.dump_outputs, {"locations": g.u, "fluxes": g.fluxes, "shapes": g.shape, "loglik": last_ll[0]})
     g.sweeps_timed = args.steps
     rep = gibbs_report(g, gf, ctx, args.steps, dt, S, B)
     ctx.profile(False)
@@ -1326,6 +1370,11 @@ def main():
                     help="default run at N = 1: skip `secondary.projected_strong_N8` (the ranks of the 8-GPU strong-scaling jobs played "
                          "one at a time on this GPU: ~10 s)")
     ap.add_argument("--master-port", type=int, default=0, help="self-launch only: rendezvous port (0 = pick a free one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, rank 0, at most "
+                         "64 MB): render workloads the returned log-likelihoods and a fixed seeded sample of the model images "
+                         "(model_images_sample_index holds the flat indices), fields8_2048 the same per field, gibbs10k the "
+                         "chain's state.  The inputs are seeded: the same arguments give the same inputs on every run")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -1392,6 +1441,8 @@ def main():
     if args.of:
         if world != 1 or args.scaling != "strong":
             raise SystemExit("--of N plays the ranks of a strong-scaling job on ONE GPU: use it with --scaling strong and without --gpus")
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs is not supported with --of (a projection, not a timed job)")
         run_projection(args, env)
         return
     {"render": run_render, "fields": run_fields, "gibbs": run_gibbs}[kind](args, env)
