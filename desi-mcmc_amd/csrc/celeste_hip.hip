@@ -46,11 +46,13 @@
 #include <cstring>
 #include <algorithm>
 #include <atomic>
+#include <memory>
 #include <new>
 #include <vector>
 #include <type_traits>
 
 #include "../../include/celeste_hip.h"
+#include "host_buf.h"
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -146,27 +148,23 @@ struct cel_ctx {
     int tile_layout = 1;      // 0: 64 x tile_rows tiles, one lane per column (k_render)
                               // 1: 32 x 64 tiles, two component groups per column (k_render_hw)
     Prof prof;
-    double *pinned = nullptr;   // MAX_BANDS + 16 doubles of pinned host memory for readbacks
+    PinnedBuf<double> pinned;   // MAX_BANDS + 16 doubles of pinned host memory for readbacks
     hipEvent_t slice_ev[2] = {nullptr, nullptr};     // cel_slice_locations: one per batch of rounds in flight
     // grow-only device scratch for the small per-call buffers of the stamp / patch-ll entry
-    // points (a hipMalloc + hipFree pair per call costs more than the kernels they bracket)
-    void *scratch[8] = {nullptr};
-    size_t scratch_cap[8] = {0};
+    // points (an allocation + free pair per call costs more than the kernels they bracket)
+    DevBuf<char> scratch[8];
 };
 
 static int scratch_get(cel_ctx *c, int slot, size_t bytes, void **out) {
     if (bytes == 0) bytes = 8;
-    if (bytes > c->scratch_cap[slot]) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->scratch[slot]) (void)hipFree(c->scratch[slot]);
-        c->scratch[slot] = nullptr; c->scratch_cap[slot] = 0;
-        size_t cap = bytes + bytes / 2 + 256;
-        HIP_TRY(hipMalloc(&c->scratch[slot], cap));
-        c->scratch_cap[slot] = cap;
-    }
+    HIP_TRY(c->scratch[slot].grow(bytes, bytes + bytes / 2 + 256, c->stream));
     *out = c->scratch[slot];
     return CEL_OK;
 }
+
+struct SourcesDeleter {
+    void operator()(cel_sources *s) const { cel_sources_destroy(s); }
+};
 
 struct cel_images {
     cel_ctx *ctx = nullptr;
@@ -175,18 +173,17 @@ struct cel_images {
     int noise_y0 = 0, noise_y1 = 0x7fffffff;     // window rows whose sky photons cel_photon_split's noise sums count
     int TW = 64, TH = 32, ntx = 0, nty = 0;   // render tile geometry (fixed at creation)
     cel_band hb[MAX_BANDS];
-    BandDev *d_bands = nullptr;
-    double *d_nelec = nullptr, *d_lambda = nullptr, *d_partials = nullptr, *d_llband = nullptr;
+    DevBuf<BandDev> d_bands;
+    DevBuf<double> d_nelec, d_lambda, d_partials, d_llband;
     bool have_nelec = false;
     // per-render scratch, grown on demand
-    double *d_slabs = nullptr;       // k_render_hw<, PARTS>: PARTS accumulator slabs per render tile, allocated with the first such launch
-    int *d_part_cnt = nullptr;       // ... and the tiles' arrival counters
-    int slabs_parts = 0;
-    SrcRec *d_recs = nullptr;
-    int4 *d_boxes = nullptr;
-    int *d_kind = nullptr;
-    int *d_status = nullptr;       // per (band, source): 1 has a stamp, 0 empty box, -1 overlap-test miss
-    int64_t recs_cap = 0;
+    DevBuf<double> d_slabs;          // k_render_hw<, PARTS>: PARTS accumulator slabs per render tile, allocated with the first such launch
+    DevBuf<int> d_part_cnt;          // ... and the tiles' arrival counters
+    // grown together (ensure_recs); d_recs is allocated last, so its capacity is the group's
+    DevBuf<SrcRec> d_recs;
+    DevBuf<int4> d_boxes;
+    DevBuf<int> d_kind;
+    DevBuf<int> d_status;          // per (band, source): 1 has a stamp, 0 empty box, -1 overlap-test miss
     // which sources the records on the device belong to (cel_sources::gen, unique per cel_sources_set),
     // and the host copy of their boxes / status that cel_stamp_boxes / cel_source_boxes hand out:
     // a stamp call (boxes, then stamps) runs k_prep and the D2H once, not twice
@@ -194,68 +191,61 @@ struct cel_images {
     // which sources the model image in d_lambda (full boxes, the current sky levels) and the tile lists belong to: what lets
     // the photon split take its totals from that image (k_border.h); 0 = not valid
     uint64_t lambda_gen = 0, lists_gen = 0;
-    unsigned long long *d_massfx = nullptr;   // the split's integer stamp-mass sums (k_split.h, k_border.h), per (source, band)
-    int64_t massfx_cap = 0;
+    DevBuf<unsigned long long> d_massfx;      // the split's integer stamp-mass sums (k_split.h, k_border.h), per (source, band)
     uint64_t massfx_gen = 0;                  // ... hold the masses of the catalogue of this generation (0: of none)
-    int *d_mass_todo = nullptr;               // (source, band) jobs the mass kernel proper still has to do + their count behind them
+    DevBuf<int> d_mass_todo;                  // (source, band) jobs the mass kernel proper still has to do + their count behind them
     std::vector<int4> h_boxes;
     std::vector<int> h_status;
-    int *d_tile_cnt = nullptr, *d_tile_nstar = nullptr, *d_tile_work = nullptr, *d_order = nullptr;
-    int *d_tile_cost = nullptr;   // measured duration of every tile in the last render (the next render's launch order)
+    DevBuf<int> d_tile_cnt, d_tile_nstar, d_tile_work, d_order;
+    DevBuf<int> d_tile_cost;      // measured duration of every tile in the last render (the next render's launch order)
     int64_t cost_S = -1;          // number of sources that render had (-1: nothing measured yet)
     bool bin_two_level = false;   // a super-tile once held more than BIN_CH candidates: coarse lists in global memory from then on
     int64_t mass_pending = -1;       // doubles waiting in d_mass between cel_stamp_mass_begin and _end (-1: none)
     int64_t mass_todo_S = -1;        // >= 0: that _begin took the short cut on a catalogue of so many sources; _end finishes its leftovers
     uint64_t mass_gen = 0;           // ... of the catalogue of this generation, with the to-do list at mass_todo_ptr: what _end checks
     const int *mass_todo_ptr = nullptr; //  before it launches on the leftovers (a call in between may have re-run k_prep for another
-                                     //     catalogue or re-allocated the split's buffers)
-    double *d_mass = nullptr;        // (a scratch slot of the context: not owned)
-    long long *d_btot = nullptr;     // per-1024-entries totals of the patch / list layout scans
+                                     //     catalogue or re-allocated the split's buffers; points into d_mass_todo: not owned)
+    double *d_mass = nullptr;        // (points into a scratch slot of the context: not owned)
+    DevBuf<long long> d_btot;        // per-1024-entries totals of the patch / list layout scans
     bool nelec_u16 = false;          // every observed pixel in 0 ... 65 535: the split's 16-bit photons-left plane
     bool star_one_segment = false;   // every band passes star_setup's test: k_render_stars may take star tiles
     int64_t order_S = -1;         // d_order already holds the heaviest-first order of those costs (sorted behind that render's readback)
     hipEvent_t ev_step = nullptr; // marks a step's readback copy: the host waits for it, not for the sort queued behind it
-    int64_t *d_tile_off = nullptr;
-    unsigned long long *d_cursor = nullptr;   // fine cursor, fine overflow, coarse cursor, coarse overflow
-    int *d_lists = nullptr;
-    int64_t lists_cap = 0;
+    DevBuf<int64_t> d_tile_off;
+    unsigned long long *d_cursor = nullptr;   // fine cursor, fine overflow, coarse cursor, coarse overflow (inside d_llband)
+    DevBuf<int> d_lists;
     int nsx = 0, nsy = 0;                     // 256 x 256 super-tiles of the coarse binning level
-    int *d_sup_cnt = nullptr;
-    int64_t *d_sup_off = nullptr;
-    int *d_clist = nullptr;
-    int64_t clist_cap = 0;
-    unsigned long long *d_timing = nullptr;   // CEL_OPT_TILE_TIMING diagnostic stamps, 3 per tile
+    DevBuf<int> d_sup_cnt;
+    DevBuf<int64_t> d_sup_off;
+    DevBuf<int> d_clist;
+    DevBuf<unsigned long long> d_timing;      // CEL_OPT_TILE_TIMING diagnostic stamps, 3 per tile
     // device-resident sample patches of the last resident photon split (source-major, index s*B+b)
-    int *d_samp = nullptr;      // the resident photon split's sample patches: int32 photon counts, source-major
-    int4 *d_snz = nullptr;      // nonzero rectangles of the resident sample patches (k_patch_nzbox)
-    double *d_ssum = nullptr;   // photons per (source, band) of the resident split, summed by the split kernel itself
+    DevBuf<int> d_samp;         // the resident photon split's sample patches: int32 photon counts, source-major
     bool ssum_valid = false;
     // host copies of the last resident split's sums and patch offsets (pinned), made INSIDE cel_photon_split before its last
     // wait: cel_samples_fetch hands them over without touching the stream, on which the photon lists are still being compacted
-    double *h_ssum = nullptr;
-    int64_t *h_soff = nullptr;
-    int64_t hsum_cap = 0;
+    // (grown together; h_ssum is allocated last, so its capacity is the pair's)
+    PinnedBuf<double> h_ssum;
+    PinnedBuf<int64_t> h_soff;
     bool hsum_valid = false;
-    // photon lists of the resident split (k_nz_layout / k_nz_compact): per patch the pixels that hold a photon
-    int *d_nnz = nullptr, *d_nzmode = nullptr;
-    int64_t *d_nzoff = nullptr;
-    NzEntry *d_nzlist = nullptr;
-    int64_t nzlist_cap = 0;
+    DevBuf<NzEntry> d_nzlist;   // photon lists of the resident split (k_nz_layout / k_nz_compact): per patch the pixels that hold a photon
     bool nz_valid = false;
-    double *d_rate = nullptr;   // per-pixel total rates of the photon split (strict boxes), B*H*W, on first use
+    DevBuf<double> d_rate;      // per-pixel total rates of the photon split (strict boxes), B*H*W, on first use
     bool rate_in_lambda = false;    // the last split read its totals from the model image itself (CEL_OPT_SPLIT_FULL_BOX with a current image)
-    int64_t samp_cap = 0;
-    int4 *d_sbox = nullptr;
-    int64_t *d_soff = nullptr;
-    int64_t slay_cap = 0, samp_S = 0, samp_total = 0;
-    double *d_stats = nullptr;
+    // the resident split's patch layout, grown together (cel_photon_split); d_sbox is allocated last, so its capacity is the group's
+    DevBuf<int4> d_sbox;
+    DevBuf<int4> d_snz;         // nonzero rectangles of the resident sample patches (k_patch_nzbox)
+    DevBuf<int64_t> d_soff;
+    DevBuf<double> d_ssum;      // photons per (source, band) of the resident split, summed by the split kernel itself
+    DevBuf<int> d_nnz, d_nzmode;   // ... and its photon lists' per-patch counts, modes and offsets
+    DevBuf<int64_t> d_nzoff;
+    int64_t samp_S = 0, samp_total = 0;
+    DevBuf<double> d_stats;
     // device-resident slice sampler (cel_slice_locations): chain state, proposal set, per-round outputs
-    void *d_slice = nullptr;
-    size_t slice_cap = 0;
-    cel_sources *slice_prop = nullptr;
-    void *d_sgen = nullptr;     // the general slice sampler's state (cel_slice_sample)
-    size_t sgen_cap = 0;
-    cel_sources *sgen_prop = nullptr;
+    DevBuf<char> d_slice;
+    std::unique_ptr<cel_sources, SourcesDeleter> slice_prop;
+    DevBuf<char> d_sgen;        // the general slice sampler's state (cel_slice_sample)
+    std::unique_ptr<cel_sources, SourcesDeleter> sgen_prop;
     int64_t last_S = 0;
     double last_entries = 0;
     bool counted = false;            // in ctx->live
@@ -264,11 +254,12 @@ struct cel_images {
     uint64_t lambda_uid = 0;         // the catalogue OBJECT whose generation lambda_gen is (the incremental render compares row stamps of the same object only)
     double lambda_T = -1.0;          // ... and the drop threshold that image was rendered at
     int lambda_parts = 0;            // ... with so many blocks per tile
-    int *d_dirty = nullptr;          // per tile: touched by a changed source's box (the incremental render)
+    DevBuf<int> d_dirty;             // per tile: touched by a changed source's box (the incremental render)
     int64_t last_dirty = -1;         // tiles the last render rendered incrementally (-1: it rendered every tile)
     // the one-launch path of a small star field (k_small_stars.h): per-block partials + per-band arrival counters
-    double *d_small = nullptr, *h_small = nullptr;      // one buffer: pinned host memory and its device address
-    double *d_small_consts = nullptr;
+    MappedBuf<double> h_small;
+    double *d_small = nullptr;       // the device address of h_small (not owned)
+    DevBuf<double> d_small_consts;
     unsigned long long small_seq = 0;
     bool llband_on_host = false;  // the last render's per-band sums were formed on the host (the small path): in h_llband
     double h_llband[MAX_BANDS] = {0};
@@ -287,8 +278,8 @@ struct cel_sources {
     uint64_t full_gen = 0;         // ... the generation of the last change of the WHOLE catalogue (cel_sources_set, a sampler's update)
     std::vector<uint64_t> row_gen; // per row: the generation of its last change by cel_sources_set_rows (empty: none since full_gen)
     int64_t n_gal = -1;            // entries that are not stars (type != 0); -1 = unknown (types set from device memory)
-    int *d_type = nullptr;
-    double *d_radec = nullptr, *d_counts = nullptr, *d_shape = nullptr;
+    DevBuf<int> d_type;
+    DevBuf<double> d_radec, d_counts, d_shape;
     std::vector<int32_t> h_type;   // the types as last set from host memory (cel_sources_set_rows keeps n_gal exact with them)
 };
 
@@ -365,11 +356,18 @@ static void prof_end(cel_ctx *c, int i) {
 // queue (rocprofv3 kernel trace): four of them per 1.6 ms step were 2 % of what was being measured.
 #define EV0(c, i) ((i) >= 0 ? (c)->prof.ev[(i)] : (hipEvent_t) nullptr)
 #define EV1(c, i) ((i) >= 0 ? (c)->prof.ev[(i) + 1] : (hipEvent_t) nullptr)
-// launch with optional start / stop events attached to the dispatch
+// launch with optional start / stop events attached to the dispatch.  hipExtLaunchKernelGGL takes its arguments by their
+// own types, so a buffer is handed over as its pointer (ext_arg)
+template <class T> static inline T ext_arg(const T &v) { return v; }
+template <class T, unsigned F> static inline T *ext_arg(const Buf<T, F> &b) { return b.get(); }
+template <class K, class... A>
+static inline void ext_launch(K kernel, dim3 grid, dim3 block, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const A &...a) {
+    hipExtLaunchKernelGGL(kernel, grid, block, 0, st, e0, e1, 0, ext_arg(a)...);
+}
 #define LAUNCH_EV(kernel, grid, block, st, e0, e1, ...)                                              \
     do {                                                                                             \
         hipEvent_t e0_ = (e0), e1_ = (e1);                                                           \
-        if (e0_ || e1_) hipExtLaunchKernelGGL(kernel, grid, block, 0, st, e0_, e1_, 0, __VA_ARGS__); \
+        if (e0_ || e1_) ext_launch(kernel, grid, block, st, e0_, e1_, __VA_ARGS__);                  \
         else hipLaunchKernelGGL(kernel, grid, block, 0, st, __VA_ARGS__);                            \
     } while (0)
 static void prof_collect(cel_ctx *c) {   // after a stream synchronise: everything outstanding has completed
@@ -461,8 +459,8 @@ int cel_ctx_create(int device, void *stream, cel_ctx **out) {
         int ncu = 0;
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) c->n_cu = ncu;
     }
-    hipError_t e = hipHostMalloc((void **)&c->pinned, sizeof(double) * (MAX_BANDS + 16), hipHostMallocDefault);
-    if (e != hipSuccess) { delete c; return fail(CEL_ERR_HIP, "hipHostMalloc: %s", hipGetErrorString(e)); }
+    hipError_t e = c->pinned.grow(MAX_BANDS + 16, MAX_BANDS + 16, c->stream);
+    if (e != hipSuccess) { delete c; return fail(CEL_ERR_HIP, "pinned readback buffer: %s", hipGetErrorString(e)); }
     // profile constants, normalised as mixture_profiles.py:13,19
     double amp[K_PROF], var[K_PROF], se = 0.0, sd = 0.0;
     for (int i = 0; i < 6; i++) se += H_EXP_AMP[i];
@@ -497,9 +495,6 @@ int cel_ctx_destroy(cel_ctx *c) {
             if (c->prof.ev[i]) (void)hipEventDestroy(c->prof.ev[i]);
     free(c->prof.ev);
     for (int k = 0; k < 2; k++) if (c->slice_ev[k]) (void)hipEventDestroy(c->slice_ev[k]);
-    if (c->pinned) (void)hipHostFree(c->pinned);
-    for (void *p : c->scratch)
-        if (p) (void)hipFree(p);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return CEL_OK;
@@ -632,25 +627,9 @@ int cel_images_destroy(cel_images *im) {
     if (!im) return CEL_OK;
     (void)hipSetDevice(im->ctx->device);
     (void)hipStreamSynchronize(im->ctx->stream);
-    void *ptrs[] = {im->d_bands, im->d_nelec, im->d_lambda, im->d_partials, im->d_llband, im->d_recs,
-                    im->d_boxes, im->d_kind, im->d_status, im->d_tile_cnt, im->d_tile_nstar, im->d_tile_work, im->d_tile_cost, im->d_order, im->d_tile_off, im->d_lists, im->d_stats,
-                    im->d_sup_cnt, im->d_sup_off, im->d_clist, im->d_timing, im->d_samp, im->d_sbox, im->d_soff, im->d_rate, im->d_snz, im->d_ssum,
-                    im->d_nnz, im->d_nzmode, im->d_nzoff, im->d_nzlist, im->d_btot, im->d_slabs, im->d_part_cnt, im->d_dirty};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (im->d_slice) (void)hipFree(im->d_slice);
-    if (im->slice_prop) cel_sources_destroy(im->slice_prop);
-    if (im->sgen_prop) cel_sources_destroy(im->sgen_prop);
-    if (im->d_sgen) (void)hipFree(im->d_sgen);
-    if (im->h_small) (void)hipHostFree(im->h_small);
-    if (im->d_small_consts) (void)hipFree(im->d_small_consts);
-    if (im->d_massfx) (void)hipFree(im->d_massfx);
-    if (im->h_ssum) (void)hipHostFree(im->h_ssum);
-    if (im->h_soff) (void)hipHostFree(im->h_soff);
-    if (im->d_mass_todo) (void)hipFree(im->d_mass_todo);
     if (im->ev_step) (void)hipEventDestroy(im->ev_step);
     if (im->counted) im->ctx->live--;
-    delete im;
+    delete im;                            // (the buffers and the proposal sets free themselves)
     return CEL_OK;
 }
 
@@ -659,7 +638,7 @@ int cel_images_create(cel_ctx *c, int B, int H, int W, const cel_band *bands, ce
     if (B < 1 || B > MAX_BANDS) return fail(CEL_ERR_INVALID, "B=%d out of range [1,%d]", B, MAX_BANDS);
     if (H < 1 || W < 1 || (int64_t)H * W > (int64_t)1 << 34) return fail(CEL_ERR_INVALID, "bad image size %dx%d", H, W);
     HIP_TRY(hipSetDevice(c->device));
-    cel_images *im = new (std::nothrow) cel_images();
+    std::unique_ptr<cel_images> im(new (std::nothrow) cel_images());   // (a failed creation frees what it allocated)
     if (!im) return fail(CEL_ERR_NOMEM, "out of host memory");
     im->ctx = c; im->B = B; im->H = H; im->W = W;
     im->full_H = H; im->win_y0 = 0;
@@ -676,10 +655,8 @@ int cel_images_create(cel_ctx *c, int B, int H, int W, const cel_band *bands, ce
         for (int k = 0; k < K_PSF; k++) {
             const double *cv = bands[b].cov + 4 * k;
             double det = cv[0] * cv[3] - cv[1] * cv[2];
-            if (!(cv[0] > 0) || !(cv[3] > 0) || !(det > 0)) {
-                delete im;
+            if (!(cv[0] > 0) || !(cv[3] > 0) || !(det > 0))
                 return fail(CEL_ERR_INVALID, "band %d: PSF component %d covariance is not positive definite", b, k);
-            }
         }
         if (!(im->hb[b].R > 0.0))
             im->hb[b].R = host_bounding_radius(bands[b].mu, bands[b].cov, K_PSF, 0.001, nullptr);
@@ -695,44 +672,31 @@ int cel_images_create(cel_ctx *c, int B, int H, int W, const cel_band *bands, ce
                                                        -rb_ - d.muy[k], rb_ - d.muy[k]);
             if (!(emax <= 0.999 * STAR_EMAX)) im->star_one_segment = false;
         }
-    size_t npix = (size_t)B * H * W;
-    int T = B * im->ntx * im->nty;
-    int rc = CEL_OK;
-#define IM_TRY(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            rc = fail(e_ == hipErrorOutOfMemory ? CEL_ERR_NOMEM : CEL_ERR_HIP, "%s: %s", #expr, \
-                      hipGetErrorString(e_));                                                 \
-            goto bad;                                                                         \
-        }                                                                                     \
-    } while (0)
-    IM_TRY(hipMalloc((void **)&im->d_bands, sizeof(BandDev) * B));
-    IM_TRY(hipMemcpy(im->d_bands, hb, sizeof(BandDev) * B, hipMemcpyHostToDevice));
-    IM_TRY(hipMalloc((void **)&im->d_nelec, sizeof(double) * npix));
-    IM_TRY(hipMalloc((void **)&im->d_lambda, sizeof(double) * npix));
-    IM_TRY(hipMalloc((void **)&im->d_partials, sizeof(double) * T));
-    // per-band sums and the binning cursors share one buffer: they ride back to the host in one copy
-    IM_TRY(hipMalloc((void **)&im->d_llband, sizeof(double) * MAX_BANDS + sizeof(unsigned long long) * 4));
+    const int64_t npix = (int64_t)B * H * W;
+    const int T = B * im->ntx * im->nty, NS = B * im->nsx * im->nsy;
+    hipStream_t st = c->stream;
+    HIP_TRY(im->d_bands.grow(B, B, st));
+    HIP_TRY(hipMemcpy(im->d_bands, hb, sizeof(BandDev) * B, hipMemcpyHostToDevice));
+    HIP_TRY(im->d_nelec.grow(npix, npix, st));
+    HIP_TRY(im->d_lambda.grow(npix, npix, st));
+    HIP_TRY(im->d_partials.grow(T, T, st));
+    // per-band sums and the binning cursors (4 x u64) share one buffer: they ride back to the host in one copy
+    HIP_TRY(im->d_llband.grow(MAX_BANDS + 4, MAX_BANDS + 4, st));
     im->d_cursor = reinterpret_cast<unsigned long long *>(im->d_llband + MAX_BANDS);
-    IM_TRY(hipMalloc((void **)&im->d_tile_cnt, sizeof(int) * T));
-    IM_TRY(hipMalloc((void **)&im->d_tile_nstar, sizeof(int) * T));
-    IM_TRY(hipMalloc((void **)&im->d_tile_work, sizeof(int) * T));
-    IM_TRY(hipMalloc((void **)&im->d_tile_cost, sizeof(int) * T));
-    IM_TRY(hipMalloc((void **)&im->d_order, sizeof(int) * T));
-    IM_TRY(hipMalloc((void **)&im->d_tile_off, sizeof(int64_t) * T));
-    IM_TRY(hipMalloc((void **)&im->d_sup_cnt, sizeof(int) * B * im->nsx * im->nsy));
-    IM_TRY(hipMalloc((void **)&im->d_sup_off, sizeof(int64_t) * B * im->nsx * im->nsy));
-    IM_TRY(hipMalloc((void **)&im->d_stats, sizeof(double) * 2));
-    IM_TRY(hipMemsetAsync(im->d_lambda, 0, sizeof(double) * npix, c->stream));
-#undef IM_TRY
+    HIP_TRY(im->d_tile_cnt.grow(T, T, st));
+    HIP_TRY(im->d_tile_nstar.grow(T, T, st));
+    HIP_TRY(im->d_tile_work.grow(T, T, st));
+    HIP_TRY(im->d_tile_cost.grow(T, T, st));
+    HIP_TRY(im->d_order.grow(T, T, st));
+    HIP_TRY(im->d_tile_off.grow(T, T, st));
+    HIP_TRY(im->d_sup_cnt.grow(NS, NS, st));
+    HIP_TRY(im->d_sup_off.grow(NS, NS, st));
+    HIP_TRY(im->d_stats.grow(2, 2, st));
+    HIP_TRY(hipMemsetAsync(im->d_lambda, 0, sizeof(double) * npix, st));
     im->counted = true;
     c->live++;
-    *out = im;
+    *out = im.release();
     return CEL_OK;
-bad:
-    cel_images_destroy(im);
-    return rc;
 }
 
 int cel_images_set_nelec(cel_images *im, const double *nelec, int mem) {
@@ -746,15 +710,13 @@ int cel_images_set_nelec(cel_images *im, const double *nelec, int mem) {
     im->nelec_u16 = false;
     {
         const int NB = 512;
-        double *d_rng = nullptr;
-        HIP_TRY(hipMalloc((void **)&d_rng, sizeof(double) * 3 * NB));
+        DevBuf<double> d_rng;
+        HIP_TRY(d_rng.grow(3 * NB, 3 * NB, im->ctx->stream));
         hipLaunchKernelGGL(k_nelec_range, dim3(NB), dim3(256), 0, im->ctx->stream, (const double *)im->d_nelec,
                            (int64_t)im->B * im->H * im->W, d_rng);
         std::vector<double> h((size_t)3 * NB);
-        hipError_t e = hipMemcpyAsync(h.data(), d_rng, sizeof(double) * 3 * NB, hipMemcpyDeviceToHost, im->ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(im->ctx->stream);
-        (void)hipFree(d_rng);
-        HIP_TRY(e);
+        HIP_TRY(hipMemcpyAsync(h.data(), d_rng, sizeof(double) * 3 * NB, hipMemcpyDeviceToHost, im->ctx->stream));
+        HIP_TRY(hipStreamSynchronize(im->ctx->stream));
         double lo = INFINITY, hi = -INFINITY, bad = 0.0;
         for (int k = 0; k < NB; k++) { lo = fmin(lo, h[3 * k]); hi = fmax(hi, h[3 * k + 1]); bad += h[3 * k + 2]; }
         im->nelec_u16 = (bad == 0.0) && (lo >= 0.0) && (hi <= 65535.0);
@@ -835,9 +797,6 @@ int cel_sources_destroy(cel_sources *s) {
     if (!s) return CEL_OK;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    void *ptrs[] = {s->d_type, s->d_radec, s->d_counts, s->d_shape};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
     if (s->counted) s->ctx->live--;
     delete s;
     return CEL_OK;
@@ -848,21 +807,17 @@ int cel_sources_create(cel_ctx *c, int64_t capacity, int B, cel_sources **out) {
     if (capacity < 1 || capacity > ((int64_t)1 << 30)) return fail(CEL_ERR_INVALID, "bad capacity");
     if (B < 1 || B > MAX_BANDS) return fail(CEL_ERR_INVALID, "B=%d out of range", B);
     HIP_TRY(hipSetDevice(c->device));
-    cel_sources *s = new (std::nothrow) cel_sources();
+    std::unique_ptr<cel_sources> s(new (std::nothrow) cel_sources());   // (a failed creation frees what it allocated)
     if (!s) return fail(CEL_ERR_NOMEM, "out of host memory");
     s->ctx = c; s->cap = capacity; s->B = B;
     s->uid = ++g_source_gen;
-    hipError_t e;
-    if ((e = hipMalloc((void **)&s->d_type, sizeof(int) * capacity)) != hipSuccess ||
-        (e = hipMalloc((void **)&s->d_radec, sizeof(double) * 2 * capacity)) != hipSuccess ||
-        (e = hipMalloc((void **)&s->d_counts, sizeof(double) * B * capacity)) != hipSuccess ||
-        (e = hipMalloc((void **)&s->d_shape, sizeof(double) * 4 * capacity)) != hipSuccess) {
-        cel_sources_destroy(s);
-        return fail(CEL_ERR_NOMEM, "hipMalloc(sources): %s", hipGetErrorString(e));
-    }
+    HIP_TRY(s->d_type.grow(capacity, capacity, c->stream));
+    HIP_TRY(s->d_radec.grow(2 * capacity, 2 * capacity, c->stream));
+    HIP_TRY(s->d_counts.grow(B * capacity, B * capacity, c->stream));
+    HIP_TRY(s->d_shape.grow(4 * capacity, 4 * capacity, c->stream));
     s->counted = true;
     s->ctx->live++;
-    *out = s;
+    *out = s.release();
     return CEL_OK;
 }
 
@@ -950,40 +905,15 @@ int cel_sources_set_rows(cel_sources *s, int64_t n, const int32_t *idx, const in
 
 // ---- prep + bin (shared by field and stamps) ------------------------------------------------
 static int ensure_recs(cel_images *im, int64_t n) {
-    if (n <= im->recs_cap) return CEL_OK;
+    if (n <= im->d_recs.cap) return CEL_OK;
     HIP_TRY(hipStreamSynchronize(im->ctx->stream));
-    if (im->d_recs) (void)hipFree(im->d_recs);
-    if (im->d_boxes) (void)hipFree(im->d_boxes);
-    if (im->d_kind) (void)hipFree(im->d_kind);
-    if (im->d_status) (void)hipFree(im->d_status);
-    im->d_recs = nullptr; im->d_boxes = nullptr; im->d_kind = nullptr; im->d_status = nullptr; im->recs_cap = 0;
+    im->d_recs.reset(); im->d_boxes.reset(); im->d_kind.reset(); im->d_status.reset();
     im->recs_gen = im->hbox_gen = 0;
-    int64_t cap = n + n / 4 + 64;
-    HIP_TRY(hipMalloc((void **)&im->d_recs, sizeof(SrcRec) * cap));
-    HIP_TRY(hipMalloc((void **)&im->d_boxes, sizeof(int4) * cap));
-    HIP_TRY(hipMalloc((void **)&im->d_kind, sizeof(int) * cap));
-    HIP_TRY(hipMalloc((void **)&im->d_status, sizeof(int) * cap));
-    im->recs_cap = cap;
-    return CEL_OK;
-}
-
-static int ensure_lists(cel_images *im, int64_t n) {
-    if (n <= im->lists_cap) return CEL_OK;
-    HIP_TRY(hipStreamSynchronize(im->ctx->stream));
-    if (im->d_lists) (void)hipFree(im->d_lists);
-    im->d_lists = nullptr; im->lists_cap = 0;
-    HIP_TRY(hipMalloc((void **)&im->d_lists, sizeof(int) * n));
-    im->lists_cap = n;
-    return CEL_OK;
-}
-
-static int ensure_clist(cel_images *im, int64_t n) {
-    if (n <= im->clist_cap) return CEL_OK;
-    HIP_TRY(hipStreamSynchronize(im->ctx->stream));
-    if (im->d_clist) (void)hipFree(im->d_clist);
-    im->d_clist = nullptr; im->clist_cap = 0;
-    HIP_TRY(hipMalloc((void **)&im->d_clist, sizeof(int) * n));
-    im->clist_cap = n;
+    const int64_t cap = n + n / 4 + 64;
+    HIP_TRY(im->d_boxes.grow(n, cap, im->ctx->stream));
+    HIP_TRY(im->d_kind.grow(n, cap, im->ctx->stream));
+    HIP_TRY(im->d_status.grow(n, cap, im->ctx->stream));
+    HIP_TRY(im->d_recs.grow(n, cap, im->ctx->stream));
     return CEL_OK;
 }
 
@@ -1055,11 +985,11 @@ static int render_small_stars(cel_images *im, cel_sources *src, int flags, bool 
         // the blocks' partials and the overflow word behind them live in pinned, device-mapped, coherent HOST memory: the
         // kernel stores them over PCIe itself (5 KB at configs[1]) and the step needs no copy command behind the kernel
         // -- a D2H copy of this size cost the step ~8 us of queue latency
-        HIP_TRY(hipHostMalloc((void **)&im->h_small, sizeof(double) * (nblk + 1), hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(im->h_small.grow(nblk + 1, nblk + 1, st));
         memset(im->h_small, 0, sizeof(double) * (nblk + 1));
         HIP_TRY(hipHostGetDevicePointer((void **)&im->d_small, im->h_small, 0));
         // the bands' star-pass constants, once (the PSF and the WCS of an image set do not change)
-        HIP_TRY(hipMalloc((void **)&im->d_small_consts, sizeof(double) * SMALL_CONSTS * B));
+        HIP_TRY(im->d_small_consts.grow(SMALL_CONSTS * B, SMALL_CONSTS * B, st));
         hipLaunchKernelGGL(k_small_consts, dim3(B), dim3(64), 0, st, (const BandDev *)im->d_bands, im->d_small_consts);
     }
     RenderArgs a;
@@ -1088,8 +1018,8 @@ static int render_small_stars(cel_images *im, cel_sources *src, int flags, bool 
     // block's duration correlates with its star count at 0.3 only.  Removed.)
     x.stamps = nullptr;
     static const char *stamp_path = getenv("CEL_SMALL_STAMPS");     // diagnostic: dump every block's phase stamps of each call
-    unsigned long long *d_stamps = nullptr;
-    if (stamp_path) { HIP_TRY(hipMalloc((void **)&d_stamps, sizeof(unsigned long long) * 8 * nblk)); x.stamps = d_stamps; }
+    DevBuf<unsigned long long> d_stamps;
+    if (stamp_path) { HIP_TRY(d_stamps.grow(8 * nblk, 8 * nblk, st)); x.stamps = d_stamps; }
     int pi = prof_slot(c, CEL_K_SMALL_STARS);
     LAUNCH_EV(k_small_stars, dim3((unsigned)nblk), dim3(64 * SMALL_NWV), st, EV0(c, pi), EV1(c, pi), a, x);
     const bool ll = (flags & CEL_RENDER_LOGLIK) != 0;
@@ -1098,7 +1028,6 @@ static int render_small_stars(cel_images *im, cel_sources *src, int flags, bool 
     if (d_stamps) {
         std::vector<unsigned long long> hs((size_t)8 * nblk);
         (void)hipMemcpy(hs.data(), d_stamps, sizeof(unsigned long long) * 8 * nblk, hipMemcpyDeviceToHost);
-        (void)hipFree(d_stamps);
         if (FILE *fp = fopen(stamp_path, "wb")) { fwrite(hs.data(), sizeof(unsigned long long), hs.size(), fp); fclose(fp); }
     }
     unsigned long long cur0;
@@ -1213,7 +1142,7 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         if (delta.n == 0) incr = false;
     }
     if (incr) {
-        if (!im->d_dirty) HIP_TRY(hipMalloc((void **)&im->d_dirty, sizeof(int) * (size_t)T));
+        HIP_TRY(im->d_dirty.grow(T, T, st));
         HIP_TRY(hipMemsetAsync(im->d_dirty, 0, sizeof(int) * (size_t)T, st));
         // the tiles the changed sources' OLD boxes touch (before k_prep rewrites the boxes) ...
         hipLaunchKernelGGL(k_mark_dirty, dim3((unsigned)((delta.n * im->B + 255) / 256)), dim3(256), 0, st, delta, (const int4 *)im->d_boxes, S, im->B,
@@ -1229,21 +1158,21 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
                            im->ntx, im->nty, im->TW, im->TH, im->d_dirty);
     im->last_dirty = -1;
     int parts_used = 1;
-    if (im->lists_cap == 0) {
+    if (im->d_lists.cap == 0) {
         // first guess: every (band, source) touches ~6 tiles; grown on overflow below
-        rc = ensure_lists(im, (S * im->B) * 6 + 1024);
-        if (rc) return rc;
+        const int64_t n = (S * im->B) * 6 + 1024;
+        HIP_TRY(im->d_lists.grow(n, n, st));
     }
-    if (im->clist_cap == 0) {
+    if (im->d_clist.cap == 0) {
         // first guess: every (band, source) touches ~3 super-tiles; grown on overflow below
-        rc = ensure_clist(im, (S * im->B) * 3 + 1024);
-        if (rc) return rc;
+        const int64_t n = (S * im->B) * 3 + 1024;
+        HIP_TRY(im->d_clist.grow(n, n, st));
     }
     const int NS = im->B * im->nsx * im->nsy;
     const int tile_order = tile_order_of(c, im);
     // a small catalogue is binned by one wave per tile into per-tile segments of S entries (k_bin_direct)
     const bool bin_direct = S > 0 && S <= BIN_DIRECT_MAX_S && (int64_t)T * S <= ((int64_t)1 << 25);
-    if (bin_direct && (rc = ensure_lists(im, (int64_t)T * S))) return rc;
+    if (bin_direct) HIP_TRY(im->d_lists.grow((int64_t)T * S, (int64_t)T * S, st));
     for (int attempt = 0; attempt < 8; attempt++) {
         // d_cursor: [0] fine cursor, [1] fine overflow, [2] coarse cursor, [3] coarse overflow;
         // zeroed by k_prep (no memset in the queue), by hand only when that did not run or on a retry
@@ -1261,31 +1190,31 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
                       im->d_tile_cnt, im->d_tile_nstar, im->d_tile_work, im->d_tile_off, im->d_cursor, im->d_lists);
         } else if (im->bin_two_level) {
             LAUNCH_EV(k_bin_coarse, dim3(NS), dim3(64 * COARSE_WAVES), st, EV0(c, pi), (hipEvent_t) nullptr, im->d_boxes, S, im->nsx, im->nsy,
-                      im->d_sup_cnt, im->d_sup_off, im->d_cursor + 2, im->d_clist, im->clist_cap, (int *)(im->d_cursor + 3));
+                      im->d_sup_cnt, im->d_sup_off, im->d_cursor + 2, im->d_clist, im->d_clist.cap, (int *)(im->d_cursor + 3));
             // (16-wave blocks while every super-tile gets a CU of its own, 8-wave blocks -- two to a CU -- beyond that: k_bin2.h)
             if (NS > c->n_cu)
                 LAUNCH_EV((k_bin_fine_blk<false, 8>), dim3(NS), dim3(64 * 8), st, (hipEvent_t) nullptr, bin_ev1,
                           im->d_boxes, im->d_kind, S, im->ntx, im->nty, im->TH, im->TW,
-                          im->nsx, im->nsy, im->d_sup_cnt, im->d_sup_off, im->d_clist, im->clist_cap, im->d_tile_cnt,
-                          im->d_tile_nstar, im->d_tile_work, im->d_tile_off, im->d_cursor, im->d_lists, im->lists_cap,
+                          im->nsx, im->nsy, im->d_sup_cnt, im->d_sup_off, im->d_clist, im->d_clist.cap, im->d_tile_cnt,
+                          im->d_tile_nstar, im->d_tile_work, im->d_tile_off, im->d_cursor, im->d_lists, im->d_lists.cap,
                           (int *)(im->d_cursor + 1), (int *)(im->d_cursor + 3));
             else
                 LAUNCH_EV((k_bin_fine_blk<false, 16>), dim3(NS), dim3(64 * 16), st, (hipEvent_t) nullptr, bin_ev1,
                           im->d_boxes, im->d_kind, S, im->ntx, im->nty, im->TH, im->TW,
-                          im->nsx, im->nsy, im->d_sup_cnt, im->d_sup_off, im->d_clist, im->clist_cap, im->d_tile_cnt,
-                          im->d_tile_nstar, im->d_tile_work, im->d_tile_off, im->d_cursor, im->d_lists, im->lists_cap,
+                          im->nsx, im->nsy, im->d_sup_cnt, im->d_sup_off, im->d_clist, im->d_clist.cap, im->d_tile_cnt,
+                          im->d_tile_nstar, im->d_tile_work, im->d_tile_off, im->d_cursor, im->d_lists, im->d_lists.cap,
                           (int *)(im->d_cursor + 1), (int *)(im->d_cursor + 3));
         } else if (NS > c->n_cu) {
             LAUNCH_EV((k_bin_fine_blk<true, 8>), dim3(NS), dim3(64 * 8), st, EV0(c, pi), bin_ev1,
                       im->d_boxes, im->d_kind, S, im->ntx, im->nty, im->TH, im->TW,
-                      im->nsx, im->nsy, im->d_sup_cnt, im->d_sup_off, im->d_clist, im->clist_cap, im->d_tile_cnt,
-                      im->d_tile_nstar, im->d_tile_work, im->d_tile_off, im->d_cursor, im->d_lists, im->lists_cap,
+                      im->nsx, im->nsy, im->d_sup_cnt, im->d_sup_off, im->d_clist, im->d_clist.cap, im->d_tile_cnt,
+                      im->d_tile_nstar, im->d_tile_work, im->d_tile_off, im->d_cursor, im->d_lists, im->d_lists.cap,
                       (int *)(im->d_cursor + 1), (int *)(im->d_cursor + 3));
         } else {
             LAUNCH_EV((k_bin_fine_blk<true, 16>), dim3(NS), dim3(64 * 16), st, EV0(c, pi), bin_ev1,
                       im->d_boxes, im->d_kind, S, im->ntx, im->nty, im->TH, im->TW,
-                      im->nsx, im->nsy, im->d_sup_cnt, im->d_sup_off, im->d_clist, im->clist_cap, im->d_tile_cnt,
-                      im->d_tile_nstar, im->d_tile_work, im->d_tile_off, im->d_cursor, im->d_lists, im->lists_cap,
+                      im->nsx, im->nsy, im->d_sup_cnt, im->d_sup_off, im->d_clist, im->d_clist.cap, im->d_tile_cnt,
+                      im->d_tile_nstar, im->d_tile_work, im->d_tile_off, im->d_cursor, im->d_lists, im->d_lists.cap,
                       (int *)(im->d_cursor + 1), (int *)(im->d_cursor + 3));
         }
         if (tile_order && !order_ready)
@@ -1298,13 +1227,13 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         a.bands = im->d_bands; a.recs = im->d_recs; a.lists = im->d_lists; a.tile_cnt = im->d_tile_cnt;
         a.tile_nstar = im->d_tile_nstar;
         a.tile_off = im->d_tile_off; a.nelec = im->d_nelec; a.lambda = lambda_out ? lambda_out : im->d_lambda; a.partials = im->d_partials;
-        a.S = S; a.capacity = im->lists_cap; a.B = im->B; a.H = im->H; a.W = im->W; a.ntx = im->ntx; a.nty = im->nty;
+        a.S = S; a.capacity = im->d_lists.cap; a.B = im->B; a.H = im->H; a.W = im->W; a.ntx = im->ntx; a.nty = im->nty;
         a.flags = flags | (c->debug << 8); a.variant = c->variant; a.tail_T = c->render_T; a.order = tile_order ? im->d_order : nullptr;
         a.timing = nullptr;
         a.dirty = incr ? im->d_dirty : nullptr;
         a.cost = (im->TW == HW_TW || im->TW == QW_TW) ? im->d_tile_cost : nullptr;
         if (c->tile_timing) {
-            if (!im->d_timing) HIP_TRY(hipMalloc((void **)&im->d_timing, sizeof(unsigned long long) * 3 * T));
+            HIP_TRY(im->d_timing.grow(3 * T, 3 * T, st));
             a.timing = im->d_timing;
         }
         // a catalogue without galaxies: the star-tile kernel (k_render_stars.h), when the frame has more tiles than the
@@ -1315,16 +1244,11 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         parts_used = (im->TW == HW_TW && !diag) ? parts : 1;
         a.slabs = nullptr; a.part_cnt = nullptr;
         if (parts > 1) {
-            if (im->slabs_parts < parts) {
-                HIP_TRY(hipStreamSynchronize(st));
-                if (im->d_slabs) (void)hipFree(im->d_slabs);
-                im->d_slabs = nullptr; im->slabs_parts = 0;
-                HIP_TRY(hipMalloc((void **)&im->d_slabs, sizeof(double) * HW_TH * HW_TW * (size_t)T * parts));
-                if (!im->d_part_cnt) {
-                    HIP_TRY(hipMalloc((void **)&im->d_part_cnt, sizeof(int) * (size_t)T));
-                    HIP_TRY(hipMemsetAsync(im->d_part_cnt, 0, sizeof(int) * (size_t)T, st));
-                }
-                im->slabs_parts = parts;
+            const int64_t slabs = (int64_t)HW_TH * HW_TW * T * parts;
+            HIP_TRY(im->d_slabs.grow(slabs, slabs, st));
+            if (!im->d_part_cnt) {
+                HIP_TRY(im->d_part_cnt.grow(T, T, st));
+                HIP_TRY(hipMemsetAsync(im->d_part_cnt, 0, sizeof(int) * (size_t)T, st));
             }
             a.slabs = im->d_slabs; a.part_cnt = im->d_part_cnt;
         }
@@ -1375,9 +1299,9 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         }
         unsigned long long cur[4];
         memcpy(cur, c->pinned + MAX_BANDS, sizeof(cur));
-        const bool fine_ok = (cur[1] & 0xffffffffull) == 0 && (int64_t)cur[0] <= im->lists_cap;
+        const bool fine_ok = (cur[1] & 0xffffffffull) == 0 && (int64_t)cur[0] <= im->d_lists.cap;
         const bool too_dense = (cur[3] & 2ull) != 0;        // a super-tile with more candidates than the one-kernel form stages
-        const bool coarse_ok = (cur[3] & 0xffffffffull) == 0 && (int64_t)cur[2] <= im->clist_cap;
+        const bool coarse_ok = (cur[3] & 0xffffffffull) == 0 && (int64_t)cur[2] <= im->d_clist.cap;
         if (coarse_ok) im->last_entries = (double)cur[0];
         if (fine_ok && coarse_ok) {
             im->cost_S = a.cost ? S : -1; im->order_S = post_order ? S : -1;
@@ -1400,9 +1324,9 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         im->order_S = -1;
         // rerun with room (a truncated coarse list also truncates the fine counts)
         if (too_dense) { im->bin_two_level = true; continue; }
-        if (!coarse_ok) rc = ensure_clist(im, (int64_t)cur[2] + (int64_t)cur[2] / 4 + 1024);
-        if (!rc && !fine_ok) rc = ensure_lists(im, (int64_t)cur[0] + (int64_t)cur[0] / 4 + 1024);
-        if (rc) return rc;
+        const int64_t nc = (int64_t)cur[2] + (int64_t)cur[2] / 4 + 1024, nf = (int64_t)cur[0] + (int64_t)cur[0] / 4 + 1024;
+        if (!coarse_ok) HIP_TRY(im->d_clist.grow(nc, nc, st));
+        if (!fine_ok) HIP_TRY(im->d_lists.grow(nf, nf, st));
         if (attempt == 7) return fail(CEL_ERR_HIP, "tile lists kept overflowing");
     }
     if (flags & CEL_RENDER_LOGLIK) {
@@ -1738,7 +1662,7 @@ int cel_patch_loglik(cel_images *im, cel_sources *src, const int32_t *boxes, con
 int cel_stamp_mass_ready(cel_images *im, cel_sources *src, int *ready) {
     if (!im || !src || !ready) return fail(CEL_ERR_INVALID, "cel_stamp_mass_ready: null argument");
     *ready = (src->ctx == im->ctx && src->B == im->B && im->ctx->mass_reuse_of() && src->gen != 0 && im->massfx_gen == src->gen &&
-              src->S * im->B <= im->massfx_cap) ? 1 : 0;
+              src->S * im->B <= im->d_massfx.cap) ? 1 : 0;
     return CEL_OK;
 }
 
@@ -1753,7 +1677,7 @@ int cel_stamp_mass_begin(cel_images *im, cel_sources *src) {
     im->mass_todo_S = -1;
     if (S == 0) { im->mass_pending = 0; return CEL_OK; }
     int rc = CEL_OK;
-    const bool from_split = c->mass_reuse_of() && src->gen != 0 && im->massfx_gen == src->gen && S * B <= im->massfx_cap;
+    const bool from_split = c->mass_reuse_of() && src->gen != 0 && im->massfx_gen == src->gen && S * B <= im->d_massfx.cap;
     if (!from_split || im->recs_gen != src->gen) rc = run_prep(im, src);
     if (rc) return rc;
     double *d_out = nullptr;
@@ -1762,7 +1686,7 @@ int cel_stamp_mass_begin(cel_images *im, cel_sources *src) {
     if (from_split) {
         // the photon split that has just run on this catalogue (with k_strict_totals before it) summed every unit stamp it
         // evaluated: those sums are the masses; the mass kernel proper runs on the few jobs the short cut does not vouch for
-        int *d_ntodo = im->d_mass_todo + im->massfx_cap;
+        int *d_ntodo = im->d_mass_todo + im->d_massfx.cap;
         HIP_TRY(hipMemsetAsync(d_ntodo, 0, sizeof(int), c->stream));
         hipLaunchKernelGGL(k_mass_from_fx, dim3((unsigned)((S * B + 255) / 256)), dim3(256), 0, c->stream, S * B, B,
                            (const unsigned long long *)im->d_massfx, (const double *)src->d_counts, (const int *)src->d_type, (const BandDev *)im->d_bands, d_out,
@@ -1919,20 +1843,15 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
     const int SLICE_SPLIT = PLL_PARTS, SLICE_SPLIT_JOBS = 8192;
     const size_t per_chain = 2 * 8 + 10 * 8 + 4 * 4 + 4 + (size_t)B * 8 * SLICE_SPLIT + 4 + (size_t)B * 4 * 6 * SLICE_SPLIT + 3 * 4;
     const size_t need = per_chain * (size_t)S + 128 + 2 * sizeof(SliceFuse) + 16;
-    if (need > im->slice_cap) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (im->d_slice) (void)hipFree(im->d_slice);
-        im->d_slice = nullptr; im->slice_cap = 0;
-        HIP_TRY(hipMalloc(&im->d_slice, need + need / 4));
-        im->slice_cap = need + need / 4;
-    }
+    HIP_TRY(im->d_slice.grow(need, need + need / 4, st));
     if (!im->slice_prop || im->slice_prop->cap < S) {
-        if (im->slice_prop) cel_sources_destroy(im->slice_prop);
-        im->slice_prop = nullptr;
-        int rc0 = cel_sources_create(c, S + S / 4 + 16, B, &im->slice_prop);
+        im->slice_prop.reset();
+        cel_sources *np = nullptr;
+        int rc0 = cel_sources_create(c, S + S / 4 + 16, B, &np);
         if (rc0) return rc0;
+        im->slice_prop.reset(np);
     }
-    cel_sources *prop = im->slice_prop;
+    cel_sources *prop = im->slice_prop.get();
     char *p = (char *)im->d_slice;
     SliceState ss;
     ss.key = (unsigned long long *)p; p += 8 * S;
@@ -2049,14 +1968,14 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
     pa.recs = im->d_recs; pa.boxes = im->d_boxes; pa.kind = im->d_kind; pa.status = im->d_status;
     // the fused rounds' arguments, in device memory: [0] for the full lists, [1] for the live lists (they differ in `need`)
     SliceFuse *d_fz = reinterpret_cast<SliceFuse *>(((uintptr_t)(d_flags + 13) + 15) & ~(uintptr_t)15);
+    SliceFuse fz[2];        // the source of an asynchronous copy: alive until the stream is synchronised at the end of the call
     if (fuse_ok) {
-        SliceFuse fz[2];
         memset(fz, 0, sizeof(fz));
         for (int k = 0; k < 2; k++) {
             fz[k].tick = d_tick; fz[k].need = k ? d_need_live : d_need_full; fz[k].st = ss; fz[k].ll_pb = d_ll; fz[k].nparts = SLICE_SPLIT;
             fz[k].B = B; fz[k].sigma = sigma; fz[k].flags = d_flags; fz[k].prop_radec = prop->d_radec; fz[k].owner = d_owner; fz[k].pa = pa;
         }
-        HIP_TRY(hipMemcpyAsync(d_fz, fz, sizeof(fz), hipMemcpyHostToDevice, st));      // (pageable: staged before the call returns)
+        HIP_TRY(hipMemcpyAsync(d_fz, fz, sizeof(fz), hipMemcpyHostToDevice, st));
     }
     if (!c->slice_ev[0]) {
         HIP_TRY(hipEventCreateWithFlags(&c->slice_ev[0], hipEventDisableTiming));
@@ -2203,20 +2122,15 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
     const size_t per_chain = 2 * 8 + (size_t)(3 * D + 13) * 8 + (size_t)(4 + D) * 4 + (size_t)ndir * D * 8 + 2 * 4 + (size_t)2 * B * ostr * 8 + 4 +
                              (size_t)2 * 2 * B * PLL_PARTS * 4;
     const size_t need = per_chain * (size_t)S + 256;
-    if (need > im->sgen_cap) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (im->d_sgen) (void)hipFree(im->d_sgen);
-        im->d_sgen = nullptr; im->sgen_cap = 0;
-        HIP_TRY(hipMalloc(&im->d_sgen, need + need / 4));
-        im->sgen_cap = need + need / 4;
-    }
+    HIP_TRY(im->d_sgen.grow(need, need + need / 4, st));
     if (!im->sgen_prop || im->sgen_prop->cap < 2 * S) {
-        if (im->sgen_prop) cel_sources_destroy(im->sgen_prop);
-        im->sgen_prop = nullptr;
-        int rc0 = cel_sources_create(c, 2 * S + S / 2 + 16, B, &im->sgen_prop);
+        im->sgen_prop.reset();
+        cel_sources *np = nullptr;
+        int rc0 = cel_sources_create(c, 2 * S + S / 2 + 16, B, &np);
         if (rc0) return rc0;
+        im->sgen_prop.reset(np);
     }
-    cel_sources *prop = im->sgen_prop;
+    cel_sources *prop = im->sgen_prop.get();
     char *p = (char *)im->d_sgen;
     SliceGen g;
     SliceState rs;
@@ -2378,7 +2292,8 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
     int rc;
     if (!hw) im->partials_gen = 0;              // (the direct form keeps its noise partials in the render's buffer)
     if (hw) {
-        if (!im->d_rate) HIP_TRY(hipMalloc((void **)&im->d_rate, sizeof(double) * (size_t)im->B * im->H * im->W));
+        const int64_t npix = (int64_t)im->B * im->H * im->W;
+        HIP_TRY(im->d_rate.grow(npix, npix, c->stream));
         im->massfx_gen = 0;
         const bool current = src->gen != 0 && im->lambda_gen == src->gen && im->lists_gen == src->gen && im->recs_gen == src->gen;
         if (c->split_full) {
@@ -2390,15 +2305,12 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
             const int64_t nm = src->S * im->B;
             if (resident && c->mass_reuse_of() && nm > 0) {
                 // both kernels of this path also sum every unit stamp they evaluate: together the stamps' masses (cel_stamp_mass)
-                if (nm > im->massfx_cap) {
+                if (nm > im->d_massfx.cap) {     // the two grow together; d_massfx, allocated last, holds the pair's capacity
                     HIP_TRY(hipStreamSynchronize(c->stream));
-                    if (im->d_massfx) (void)hipFree(im->d_massfx);
-                    if (im->d_mass_todo) (void)hipFree(im->d_mass_todo);
-                    im->d_massfx = nullptr; im->d_mass_todo = nullptr; im->massfx_cap = 0;
+                    im->d_massfx.reset(); im->d_mass_todo.reset();
                     const int64_t cap = nm + nm / 4 + 64;
-                    HIP_TRY(hipMalloc((void **)&im->d_massfx, sizeof(unsigned long long) * cap));
-                    HIP_TRY(hipMalloc((void **)&im->d_mass_todo, sizeof(int) * (cap + 1)));
-                    im->massfx_cap = cap;
+                    HIP_TRY(im->d_mass_todo.grow(cap + 1, cap + 1, c->stream));
+                    HIP_TRY(im->d_massfx.grow(nm, cap, c->stream));
                 }
                 HIP_TRY(hipMemsetAsync(im->d_massfx, 0, sizeof(unsigned long long) * nm, c->stream));
                 use_massfx = true;
@@ -2408,7 +2320,7 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
             RenderArgs a;
             memset(&a, 0, sizeof(a));
             a.bands = im->d_bands; a.recs = im->d_recs; a.lists = im->d_lists; a.tile_cnt = im->d_tile_cnt; a.tile_off = im->d_tile_off;
-            a.lambda = im->d_lambda; a.S = src->S; a.capacity = im->lists_cap; a.B = im->B; a.H = im->H; a.W = im->W;
+            a.lambda = im->d_lambda; a.S = src->S; a.capacity = im->d_lists.cap; a.B = im->B; a.H = im->H; a.W = im->W;
             a.ntx = im->ntx; a.nty = im->nty;
             int pi = prof_slot(c, CEL_K_TOTALS);
             LAUNCH_EV(k_strict_totals, dim3((unsigned)(im->B * im->ntx * im->nty)), dim3(64), c->stream, EV0(c, pi), EV1(c, pi), a, im->d_rate,
@@ -2430,29 +2342,19 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
     void *d_samp = nullptr;             // resident: int32 photon counts; a caller's buffer: doubles
     if (resident) {
         // patch boxes + offsets laid out on the device; only the total size comes back
-        if (n + 1 > im->slay_cap) {
+        if (n + 1 > im->d_sbox.cap) {
             HIP_TRY(hipStreamSynchronize(c->stream));
-            if (im->d_sbox) (void)hipFree(im->d_sbox);
-            if (im->d_soff) (void)hipFree(im->d_soff);
-            if (im->d_snz) (void)hipFree(im->d_snz);
-            if (im->d_ssum) (void)hipFree(im->d_ssum);
-            if (im->d_nnz) (void)hipFree(im->d_nnz);
-            if (im->d_nzmode) (void)hipFree(im->d_nzmode);
-            if (im->d_nzoff) (void)hipFree(im->d_nzoff);
-            im->d_nnz = nullptr; im->d_nzmode = nullptr; im->d_nzoff = nullptr;
-            im->d_sbox = nullptr; im->d_soff = nullptr; im->d_snz = nullptr; im->d_ssum = nullptr; im->slay_cap = 0;
-            int64_t cap = n + n / 4 + 64;
-            HIP_TRY(hipMalloc((void **)&im->d_sbox, sizeof(int4) * cap));
-            HIP_TRY(hipMalloc((void **)&im->d_snz, sizeof(int4) * cap));
-            HIP_TRY(hipMalloc((void **)&im->d_soff, sizeof(int64_t) * cap));
-            HIP_TRY(hipMalloc((void **)&im->d_ssum, sizeof(double) * cap));
-            HIP_TRY(hipMalloc((void **)&im->d_nnz, sizeof(int) * cap));
-            HIP_TRY(hipMalloc((void **)&im->d_nzmode, sizeof(int) * cap));
-            HIP_TRY(hipMalloc((void **)&im->d_nzoff, sizeof(int64_t) * cap));
-            if (im->d_btot) (void)hipFree(im->d_btot);
-            im->d_btot = nullptr;
-            HIP_TRY(hipMalloc((void **)&im->d_btot, sizeof(long long) * (size_t)(cap / 1024 + 2)));
-            im->slay_cap = cap;
+            im->d_sbox.reset(); im->d_snz.reset(); im->d_soff.reset(); im->d_ssum.reset();
+            im->d_nnz.reset(); im->d_nzmode.reset(); im->d_nzoff.reset(); im->d_btot.reset();
+            const int64_t cap = n + n / 4 + 64, nb = cap / 1024 + 2;
+            HIP_TRY(im->d_snz.grow(n + 1, cap, c->stream));
+            HIP_TRY(im->d_soff.grow(n + 1, cap, c->stream));
+            HIP_TRY(im->d_ssum.grow(n + 1, cap, c->stream));
+            HIP_TRY(im->d_nnz.grow(n + 1, cap, c->stream));
+            HIP_TRY(im->d_nzmode.grow(n + 1, cap, c->stream));
+            HIP_TRY(im->d_nzoff.grow(n + 1, cap, c->stream));
+            HIP_TRY(im->d_btot.grow(nb, nb, c->stream));
+            HIP_TRY(im->d_sbox.grow(n + 1, cap, c->stream));
         }
         {
             const unsigned nblk = (unsigned)((n + 1023) / 1024);
@@ -2463,13 +2365,7 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
         HIP_TRY(hipMemcpyAsync(c->pinned + MAX_BANDS + 2, im->d_soff + n, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         memcpy(&total, c->pinned + MAX_BANDS + 2, sizeof(total));
-        if (total > im->samp_cap) {
-            if (im->d_samp) (void)hipFree(im->d_samp);
-            im->d_samp = nullptr; im->samp_cap = 0;
-            int64_t cap = total + total / 8 + 1024;
-            HIP_TRY(hipMalloc((void **)&im->d_samp, sizeof(int) * cap));
-            im->samp_cap = cap;
-        }
+        HIP_TRY(im->d_samp.grow(total, total + total / 8 + 1024, c->stream));
         d_off = im->d_soff;
         d_samp = im->d_samp;
         im->samp_S = S;
@@ -2512,7 +2408,7 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
         SplitArgs a;
         a.bands = im->d_bands; a.recs = im->d_recs; a.lists = im->d_lists; a.tile_cnt = im->d_tile_cnt;
         a.tile_off = im->d_tile_off; a.nelec = im->d_nelec; a.offsets = d_off; a.samp = d_samp;
-        a.partials = im->d_partials; a.S = S; a.capacity = im->lists_cap; a.B = B; a.H = im->H; a.W = im->W;
+        a.partials = im->d_partials; a.S = S; a.capacity = im->d_lists.cap; a.B = B; a.H = im->H; a.W = im->W;
         a.ntx = im->ntx; a.nty = im->nty; a.TW = im->TW; a.TH = im->TH; a.seed = seed;
         a.win_y0 = im->win_y0; a.full_H = im->full_H;
         a.noise_y0 = im->noise_y0; a.noise_y1 = im->noise_y1;
@@ -2555,14 +2451,11 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
     if (fused_nz) {
         // what a Gibbs sweep asks for next (the photons per source: the flux and sky steps; the patch areas) rides back now:
         // cel_samples_fetch then needs no wait of its own, and the list compaction queued below runs under the host's work
-        if (n + 1 > im->hsum_cap) {
-            if (im->h_ssum) (void)hipHostFree(im->h_ssum);
-            if (im->h_soff) (void)hipHostFree(im->h_soff);
-            im->h_ssum = nullptr; im->h_soff = nullptr; im->hsum_cap = 0;
+        if (n + 1 > im->h_ssum.cap) {
+            im->h_ssum.reset(); im->h_soff.reset();
             const int64_t cap = n + n / 4 + 64;
-            HIP_TRY(hipHostMalloc((void **)&im->h_ssum, sizeof(double) * cap, hipHostMallocDefault));
-            HIP_TRY(hipHostMalloc((void **)&im->h_soff, sizeof(int64_t) * cap, hipHostMallocDefault));
-            im->hsum_cap = cap;
+            HIP_TRY(im->h_soff.grow(n + 1, cap, c->stream));
+            HIP_TRY(im->h_ssum.grow(n + 1, cap, c->stream));
         }
         HIP_TRY(hipMemcpyAsync(im->h_ssum, im->d_ssum, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(im->h_soff, im->d_soff, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, c->stream));
@@ -2577,13 +2470,7 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
     if (lists) {
         int64_t nn = 0;
         memcpy(&nn, c->pinned + MAX_BANDS + 2, sizeof(nn));
-        if (nn > im->nzlist_cap) {
-            if (im->d_nzlist) (void)hipFree(im->d_nzlist);
-            im->d_nzlist = nullptr; im->nzlist_cap = 0;
-            const int64_t cap = nn + nn / 4 + 1024;
-            HIP_TRY(hipMalloc((void **)&im->d_nzlist, sizeof(NzEntry) * cap));
-            im->nzlist_cap = cap;
-        }
+        HIP_TRY(im->d_nzlist.grow(nn, nn + nn / 4 + 1024, c->stream));
         // stream-ordered: whatever scores against these patches next runs behind it
         hipLaunchKernelGGL(k_nz_compact, dim3((unsigned)n), dim3(64), 0, c->stream, (const int4 *)im->d_sbox, (const int64_t *)im->d_soff,
                            (const int *)im->d_samp, (const int4 *)im->d_snz, (const int64_t *)im->d_nzoff, im->d_nzlist);
@@ -2607,7 +2494,7 @@ int cel_samples_fetch(cel_images *im, int32_t *boxes, int64_t *offsets, double *
     HIP_TRY(hipSetDevice(c->device));
     const int64_t n = im->samp_S * im->B;
     int rc = CEL_OK;
-    if (!boxes && !data && im->hsum_valid && n + 1 <= im->hsum_cap) {        // host copies made by the split itself: no wait
+    if (!boxes && !data && im->hsum_valid && n + 1 <= im->h_ssum.cap) {        // host copies made by the split itself: no wait
         if (offsets) memcpy(offsets, im->h_soff, sizeof(int64_t) * (n + 1));
         if (sums) memcpy(sums, im->h_ssum, sizeof(double) * n);
         return CEL_OK;
@@ -2660,13 +2547,11 @@ int cel_debug_binomial(cel_ctx *c, int64_t n, double p, uint64_t seed, int64_t N
     if (!c || !out || N < 0 || n < 0) return fail(CEL_ERR_INVALID, "cel_debug_binomial: bad argument");
     if (N == 0) return CEL_OK;
     HIP_TRY(hipSetDevice(c->device));
-    long long *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, sizeof(long long) * N));
+    DevBuf<long long> d;
+    HIP_TRY(d.grow(N, N, c->stream));
     hipLaunchKernelGGL(k_binomial_draws, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, (long long)n, p,
                        (unsigned long long)seed, N, d);
-    int rc = copy_out(out, d, sizeof(long long) * N, CEL_HOST, c->stream);
-    (void)hipFree(d);
-    return rc;
+    return copy_out(out, d, sizeof(long long) * N, CEL_HOST, c->stream);
 }
 
 // ---- E-step statistics -------------------------------------------------------------------------
@@ -2694,10 +2579,10 @@ int cel_estep_stats(cel_images *im, cel_sources *src, double *xtilde, double *ma
         if (e != hipSuccess) { rc = fail(CEL_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e)); goto done; } \
     } while (0)
     if (S > 0) {
-        // the context's scratch arena (slots 4/5), not a hipMalloc per call: EM iterates this
+        // the context's scratch arena (slots 4/5), not an allocation per call: EM iterates this
         if ((rc = scratch_get(c, 4, sizeof(double) * S * B, (void **)&d_x)) ||
             (rc = scratch_get(c, 5, sizeof(double) * S * B, (void **)&d_m))) goto done;
-        if (tiles && (rc = scratch_get(c, 6, sizeof(double) * 2 * (size_t)im->lists_cap, (void **)&d_part))) goto done;
+        if (tiles && (rc = scratch_get(c, 6, sizeof(double) * 2 * (size_t)im->d_lists.cap, (void **)&d_part))) goto done;
         int pi = prof_begin(c, CEL_K_ESTEP);
         if (c->variant == 0)
             hipLaunchKernelGGL(k_estep_src, dim3((unsigned)(S * B)), dim3(256), 0, c->stream, im->d_bands, B, im->H, im->W,
@@ -2709,11 +2594,11 @@ int cel_estep_stats(cel_images *im, cel_sources *src, double *xtilde, double *ma
             ea.bands = im->d_bands; ea.recs = im->d_recs; ea.lists = im->d_lists; ea.tile_cnt = im->d_tile_cnt;
             ea.tile_off = im->d_tile_off; ea.order = tile_order_of(c, im) ? im->d_order : nullptr;
             ea.nelec = im->d_nelec; ea.lambda = im->d_lambda; ea.partial = d_part; ea.noise_partial = im->d_partials;
-            ea.S = S; ea.capacity = im->lists_cap; ea.B = B; ea.H = im->H; ea.W = im->W; ea.ntx = im->ntx; ea.nty = im->nty;
+            ea.S = S; ea.capacity = im->d_lists.cap; ea.B = B; ea.H = im->H; ea.W = im->W; ea.ntx = im->ntx; ea.nty = im->nty;
             ea.tail_T = c->tail_T;
             hipLaunchKernelGGL(k_estep_tiles, dim3((unsigned)(B * nblk)), dim3(64), 0, c->stream, ea);
             hipLaunchKernelGGL(k_estep_gather, dim3((unsigned)((S * B + 255) / 256)), dim3(256), 0, c->stream, im->d_boxes, im->d_kind,
-                               S, B, im->ntx, im->nty, im->d_tile_cnt, im->d_tile_nstar, im->d_tile_off, im->d_lists, im->lists_cap,
+                               S, B, im->ntx, im->nty, im->d_tile_cnt, im->d_tile_nstar, im->d_tile_off, im->d_lists, im->d_lists.cap,
                                d_part, d_x, d_m);
         } else
             hipLaunchKernelGGL(k_estep_src_hw, dim3((unsigned)(S * B)), dim3(64), 0, c->stream, im->d_bands, B, im->H, im->W,
@@ -2758,41 +2643,25 @@ int cel_gmm_like_2d(cel_ctx *c, const double *x, int64_t N, const double *ws, co
         comp[6 * k + 4] = -1 * s[1] / det;
         comp[6 * k + 5] = s[0] / det;
     }
-    double *d_comp = nullptr, *d_x = nullptr, *d_p = nullptr;
-    int rc = CEL_OK;
-    hipError_t e;
-#define G_TRY(expr)                                                                      \
-    do {                                                                                 \
-        e = (expr);                                                                      \
-        if (e != hipSuccess) { rc = fail(CEL_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e)); goto done; } \
-    } while (0)
-    G_TRY(hipMalloc((void **)&d_comp, sizeof(double) * 6 * K));
-    G_TRY(hipMemcpyAsync(d_comp, comp.data(), sizeof(double) * 6 * K, hipMemcpyHostToDevice, c->stream));
-    if (mem == CEL_DEVICE) {
-        d_x = const_cast<double *>(x);
-        d_p = probs;
-    } else {
-        G_TRY(hipMalloc((void **)&d_x, sizeof(double) * 2 * N));
-        G_TRY(hipMalloc((void **)&d_p, sizeof(double) * N));
-        G_TRY(hipMemcpyAsync(d_x, x, sizeof(double) * 2 * N, hipMemcpyHostToDevice, c->stream));
+    DevBuf<double> d_comp, bx, bp;      // per call; a caller's host arrays are staged in bx / bp
+    HIP_TRY(d_comp.grow(6 * K, 6 * K, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_comp, comp.data(), sizeof(double) * 6 * K, hipMemcpyHostToDevice, c->stream));
+    double *d_x = const_cast<double *>(x), *d_p = probs;
+    if (mem != CEL_DEVICE) {
+        HIP_TRY(bx.grow(2 * N, 2 * N, c->stream));
+        HIP_TRY(bp.grow(N, N, c->stream));
+        HIP_TRY(hipMemcpyAsync(bx, x, sizeof(double) * 2 * N, hipMemcpyHostToDevice, c->stream));
+        d_x = bx; d_p = bp;
     }
     {
         int pi = prof_begin(c, CEL_K_GMM);
         hipLaunchKernelGGL(k_gmm, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, d_x, N, d_comp, K, d_p);
         prof_end(c, pi);
     }
-    G_TRY(hipGetLastError());
-    if (mem != CEL_DEVICE) G_TRY(hipMemcpyAsync(probs, d_p, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream));
-    G_TRY(hipStreamSynchronize(c->stream));
-#undef G_TRY
-done:
-    (void)hipStreamSynchronize(c->stream);
-    if (d_comp) (void)hipFree(d_comp);
-    if (mem != CEL_DEVICE) {
-        if (d_x) (void)hipFree(d_x);
-        if (d_p) (void)hipFree(d_p);
-    }
-    return rc;
+    HIP_TRY(hipGetLastError());
+    if (mem != CEL_DEVICE) HIP_TRY(hipMemcpyAsync(probs, d_p, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CEL_OK;
 }
 
 int cel_mog_loglike(cel_ctx *c, const double *x, int64_t N, const double *means, const double *icovs,

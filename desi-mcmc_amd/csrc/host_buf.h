@@ -1,0 +1,59 @@
+// host_buf.h -- the owner of every device and pinned host allocation of the host side (host code only).
+//
+// A Buf is a grow-only array: grow(need, alloc, stream) does nothing while `need` elements fit, and otherwise synchronises
+// `stream`, frees the old block and allocates `alloc` elements.  The capacity rule stays with the caller.  A failed grow
+// leaves the buffer empty (capacity 0) and returns the HIP error, for HIP_TRY.  The destructor frees.
+//
+// A buffer that is a function's local (a per-call temporary) is freed when the function returns, without a synchronise of
+// its own: every path out of such a function has synchronised the stream first (the success paths explicitly, HIP_TRY's
+// error path with hipDeviceSynchronize).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+static constexpr unsigned BUF_DEVICE = ~0u;      // Flags of a device buffer; anything else is hipHostMalloc's flags
+
+template <class T, unsigned Flags>
+class Buf {
+public:
+    T *p = nullptr;
+    int64_t cap = 0;            // elements
+
+    Buf() = default;
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    Buf(Buf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    Buf &operator=(Buf &&o) noexcept {
+        if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~Buf() { reset(); }
+
+    operator T *() const { return p; }
+    T *get() const { return p; }
+
+    // free now (the caller has synchronised whatever used the block)
+    void reset() {
+        if (p) (void)(Flags == BUF_DEVICE ? hipFree(p) : hipHostFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+
+    hipError_t grow(int64_t need, int64_t alloc, hipStream_t stream) {
+        if (need <= cap) return hipSuccess;
+        if (p) {
+            hipError_t e = hipStreamSynchronize(stream);
+            if (e != hipSuccess) return e;
+            reset();
+        }
+        const size_t bytes = sizeof(T) * (size_t)alloc;
+        hipError_t e = Flags == BUF_DEVICE ? hipMalloc((void **)&p, bytes) : hipHostMalloc((void **)&p, bytes, Flags);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        cap = alloc;
+        return hipSuccess;
+    }
+};
+
+template <class T> using DevBuf = Buf<T, BUF_DEVICE>;
+template <class T, unsigned Flags = hipHostMallocDefault> using PinnedBuf = Buf<T, Flags>;
+template <class T> using MappedBuf = PinnedBuf<T, hipHostMallocMapped | hipHostMallocCoherent>;   // pinned, device-mapped, coherent
