@@ -27,7 +27,7 @@ CEL_OPT_TAIL_LOG_SOURCE, CEL_OPT_TILE_PARTS, CEL_OPT_INCREMENTAL, CEL_OPT_SPLIT_
 #: the per-source kernels keep 32 (CEL_OPT_TAIL_LOG_SOURCE reads / sets theirs alone).  TAIL_LOG_STRICT = 32 for both: the
 #: strict variants of the parity tests (conftest.tail_log); the suite itself runs at these shipping defaults.
 TAIL_LOG_DEFAULT, TAIL_LOG_STRICT, TAIL_LOG_FAST = 24.0, 32.0, 20.0
-KERNELS = {"prep": 0, "bin": 1, "render": 2, "reduce": 3, "stamps": 4, "gmm": 5, "patch_ll": 6, "split": 7, "mass": 8, "estep": 9, "render_stars": 10, "small_stars": 11, "totals": 12}
+KERNELS = {"prep": 0, "bin": 1, "render": 2, "reduce": 3, "stamps": 4, "gmm": 5, "patch_ll": 6, "split": 7, "mass": 8, "estep": 9, "render_stars": 10, "small_stars": 11, "totals": 12, "grad": 13}
 BAND_DOUBLES = 37
 MAX_BANDS = 16
 
@@ -89,6 +89,7 @@ SYMBOLS = [
     ("cel_samples_photon_rects", C.c_int, [C.c_void_p, c_int32_p]),
     ("cel_debug_binomial", C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_uint64, C.c_int64, c_int64_p]),
     ("cel_estep_stats", C.c_int, [C.c_void_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    ("cel_loglik_grad", C.c_int, [C.c_void_p, C.c_void_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     ("cel_gmm_like_2d", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, c_double_p, c_double_p, c_double_p, C.c_int,
                                   C.c_void_p, C.c_int]),
     ("cel_mog_loglike", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, c_double_p, c_double_p, c_double_p, C.c_int,

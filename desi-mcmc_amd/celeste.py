@@ -682,3 +682,53 @@ def celeste_likelihood_multi_image(srcs, images):
         ll += total
         i = j
     return ll
+
+
+def _counts_per_flux(srcs, images):
+    """(S, N) d counts / d flux of expected_photons' conventions: kappa / calib (nmgy2counts: stars and galaxies), kappa
+    (a is None, fluxes given); NaN for a star given by temperature (its counts do not come from its fluxes)"""
+    from .celeste_src import SrcCatalog
+    calib = np.array([im.calib for im in images], dtype=np.float64)
+    kappa = np.array([im.kappa for im in images], dtype=np.float64)
+    if isinstance(srcs, SrcCatalog):
+        a = np.asarray(srcs.a)
+        return np.where((a >= 0)[:, None], (kappa / calib)[None, :], kappa[None, :])
+    out = np.empty((len(srcs), len(images)))
+    for s, src in enumerate(srcs):
+        if src.a == 0 and src.t:
+            out[s] = np.nan
+        elif src.a is None:
+            out[s] = kappa
+        else:
+            out[s] = kappa / calib
+    return out
+
+
+def celeste_likelihood_multi_image_grad(srcs, images):
+    """celeste_likelihood_multi_image and its gradient with every source's box held fixed (cel_loglik_grad), images grouped
+    as celeste_likelihood_multi_image groups them.  -> (ll, {"u": (S, 2) per degree, "counts": (S, N) per image,
+    "fluxes": (S, 5) through expected_photons' convention, "shape": (S, 4) theta, sigma, phi, rho})"""
+    images = list(images)
+    S = len(srcs)
+    ll = 0
+    g_u, g_shape = np.zeros((S, 2)), np.zeros((S, 4))
+    g_counts = np.zeros((S, len(images)))
+    i = 0
+    while i < len(images):
+        j = i + 1
+        while j < len(images) and j - i < 16 and images[j].nelec.shape == images[i].nelec.shape:
+            j += 1
+        group = tuple(images[i:j])
+        iset = _image_set(group)
+        typ, radec, counts, shape = _source_arrays(srcs, group)
+        total, gr, gc, gs = iset.loglik_grad(_device_sources(iset, (typ, radec, counts, shape)))
+        ll += total
+        g_u += gr
+        g_shape += gs
+        g_counts[:, i:j] = gc
+        i = j
+    g_flux = np.zeros((S, len(BANDS)))
+    per = _counts_per_flux(srcs, images)
+    for n, im in enumerate(images):
+        g_flux[:, list(BANDS).index(im.band)] += g_counts[:, n] * per[:, n]
+    return ll, {"u": g_u, "counts": g_counts, "fluxes": g_flux, "shape": g_shape}

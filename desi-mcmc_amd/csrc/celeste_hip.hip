@@ -93,6 +93,7 @@ static int fail(int code, const char *fmt, ...) {
 #include "k_patch_ll.h"
 #include "k_slice_gen.h"
 #include "k_estep.h"
+#include "k_grad.h"
 #include "k_split.h"
 #include "k_slice.h"
 
@@ -2621,6 +2622,50 @@ int cel_estep_stats(cel_images *im, cel_sources *src, double *xtilde, double *ma
 done:
     (void)hipStreamSynchronize(c->stream);
     return rc;
+}
+
+// ---- gradient of the field log-likelihood (k_grad.h) --------------------------------------------
+int cel_loglik_grad(cel_images *im, cel_sources *src, double *ll_total, double *g_radec, double *g_counts, double *g_shape,
+                    int mem) {
+    if (!im || !src) return fail(CEL_ERR_INVALID, "cel_loglik_grad: null argument");
+    if (!im->have_nelec) return fail(CEL_ERR_INVALID, "cel_loglik_grad needs cel_images_set_nelec first");
+    if (im->win_y0 != 0 || im->full_H != im->H)
+        return fail(CEL_ERR_INVALID, "cel_loglik_grad: an image set with a row window (cel_images_set_window) is not supported");
+    if (mem != CEL_HOST && mem != CEL_DEVICE) return fail(CEL_ERR_INVALID, "cel_loglik_grad: bad mem");
+    cel_ctx *c = im->ctx;
+    // lambda, records and boxes of exactly these sources; the log-likelihood is cel_render_field's own
+    double ll = 0.0;
+    int rc = render_impl(im, src, CEL_RENDER_LOGLIK, nullptr, &ll, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const int B = im->B;
+    const int64_t S = src->S;
+    if (S > 0 && (g_radec || g_counts || g_shape)) {
+        double *d_sums = nullptr, *d_out = nullptr;
+        if ((rc = scratch_get(c, 4, sizeof(double) * GRAD_NS * S * B, (void **)&d_sums))) return rc;
+        double *o_radec = g_radec, *o_counts = g_counts, *o_shape = g_shape;
+        if (mem != CEL_DEVICE) {
+            if ((rc = scratch_get(c, 5, sizeof(double) * (size_t)S * (6 + B), (void **)&d_out))) return rc;
+            o_radec = g_radec ? d_out : nullptr;
+            o_shape = g_shape ? d_out + 2 * S : nullptr;
+            o_counts = g_counts ? d_out + 6 * S : nullptr;
+        }
+        int pi = prof_begin(c, CEL_K_GRAD);
+        hipLaunchKernelGGL(k_grad_src, dim3((unsigned)(S * B)), dim3(64), 0, c->stream, im->d_bands, B, im->H, im->W, S,
+                           im->d_recs, im->d_nelec, im->d_lambda, c->tail_T, d_sums);
+        hipLaunchKernelGGL(k_grad_chain, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, c->stream, im->d_bands, B, S,
+                           im->d_recs, src->d_type, src->d_shape, src->d_counts, d_sums, o_radec, o_counts, o_shape);
+        prof_end(c, pi);
+        HIP_TRY(hipGetLastError());
+        if (mem != CEL_DEVICE) {
+            if (g_radec) HIP_TRY(hipMemcpyAsync(g_radec, o_radec, sizeof(double) * 2 * S, hipMemcpyDeviceToHost, c->stream));
+            if (g_shape) HIP_TRY(hipMemcpyAsync(g_shape, o_shape, sizeof(double) * 4 * S, hipMemcpyDeviceToHost, c->stream));
+            if (g_counts) HIP_TRY(hipMemcpyAsync(g_counts, o_counts, sizeof(double) * S * B, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (ll_total) *ll_total = ll;
+    return CEL_OK;
 }
 
 // ---- generic evaluator ------------------------------------------------------------------------

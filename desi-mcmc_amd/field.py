@@ -491,6 +491,16 @@ class ImageSet(object):
         L.check(L.lib().cel_estep_stats(self._h, sources._h, L.dptr(xt), L.dptr(ms), L.dptr(nz)))
         return xt, ms, nz
 
+    def loglik_grad(self, sources):
+        """Gradient of the field log-likelihood with every source's box held fixed (cel_loglik_grad)
+        -> (ll, g_radec[S,2] per degree, g_counts[S,B], g_shape[S,4]).  ll is render(sources, loglik=True)'s total."""
+        S = sources.S
+        gr, gc, gs = np.zeros((S, 2)), np.zeros((S, self.B)), np.zeros((S, 4))
+        ll = C.c_double(0.0)
+        L.check(L.lib().cel_loglik_grad(self._h, sources._h, C.byref(ll), gr.ctypes.data, gc.ctypes.data, gs.ctypes.data,
+                                        L.CEL_HOST))
+        return ll.value, gr, gc, gs
+
     def patch_loglik(self, sources, boxes, patches, isolated=False, mode=None):
         """Conditional log-likelihood of each of the P proposals in `sources` on fixed patches.
         boxes: (B,4) int y0,y1,x0,x1 (empty box = band without a sample image);

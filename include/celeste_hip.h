@@ -164,7 +164,8 @@ enum {
     CEL_K_RENDER_STARS = 10,/* k_render_stars: the field render of a catalogue without galaxies (CEL_OPT_STAR_TILES) */
     CEL_K_SMALL_STARS = 11,/* k_small_stars: a small star field's whole step in one launch (CEL_OPT_STAR_TILES = 1) */
     CEL_K_TOTALS = 12,     /* k_strict_totals: the photon split's totals image from the model image on the device (CEL_OPT_SPLIT_REUSE) */
-    CEL_K_COUNT = 13
+    CEL_K_GRAD = 13,       /* k_grad_src + k_grad_chain: cel_loglik_grad */
+    CEL_K_COUNT = 14
 };
 
 typedef struct cel_ctx cel_ctx;
@@ -449,6 +450,29 @@ int cel_debug_binomial(cel_ctx *ctx, int64_t n, double p, uint64_t seed, int64_t
  *   noise[b]      = sum_pixels nelec * eps / lambda      (celeste_em.py:62, before the / size)
  * Renders lambda for `src` first.  Host outputs; any of them may be NULL. */
 int cel_estep_stats(cel_images *img, cel_sources *src, double *xtilde, double *mass, double *noise);
+
+/* ---- gradient of the field log-likelihood ------------------------------------------------------ */
+/* For the catalogue in `src` and the image set `img`:
+ *     ll = sum_b sum_p  nelec log(lambda) - lambda,    lambda_b(p) = eps_b + sum_s counts[s][b] unit_stamp(s, b)(p)
+ * The gradient is taken with every source's integer box held fixed (the box the render uses): lambda is piecewise smooth in
+ * the parameters and the boxes are where it is not.  Outputs (any may be NULL) are the partial derivatives of ll with
+ * respect to what cel_sources_set takes, in its units, summed over the bands:
+ *   g_radec[s*2 + i]   d ll / d ra, d ll / d dec, per degree (the mean through equa2pixel and, for galaxies, W through
+ *                      cd_at_pixel's cos(dec) term, Q9)
+ *   g_counts[s*B + b]  d ll / d counts[s][b]
+ *   g_shape[s*4 + i]   type 1: d ll / d (theta, sigma [arcsec], phi [degrees], rho); 0 for sigma where k_prep's floor
+ *                      max(1/30, sigma) holds.  Type 2: d ll / d (theta, W00, W01, W11).  Stars: zeros.
+ * ll_total (host, may be NULL) is the value cel_render_field(CEL_RENDER_LOGLIK) returns for the same call, bit for bit.
+ * Renders lambda for `src` first, as cel_estep_stats does.  g_* follow `mem` (CEL_DEVICE: device pointers, e.g. an
+ * optimiser's state); the stream is synchronised before the call returns.  Sums run in a fixed order (no atomics): two calls
+ * give the same bits.  Drop rule and its error bound: desi-mcmc_amd/csrc/k_grad.h (per-source threshold
+ * CEL_OPT_TAIL_LOG_SOURCE; the gradient's relative error stays below ~K T_k e^-T, 4e-11 at the default T = 32).  At the
+ * shipping defaults the render's T = 24 moves every r(p) = nelec / lambda - 1 by at most n e^-24 nelec / lambda as well: every
+ * entry then stays within 1e-7 of the largest |entry| of its column of the gradient with nothing dropped (T = 0).
+ * CEL_ERR_INVALID without cel_images_set_nelec and on an image set with a row window (cel_images_set_window): partitioned
+ * (strip / windowed) gradients are not provided. */
+int cel_loglik_grad(cel_images *img, cel_sources *src, double *ll_total, double *g_radec, double *g_counts, double *g_shape,
+                    int mem);
 
 /* ---- generic evaluator ------------------------------------------------------------------ */
 /* gmm_like_2d (util/like/gmm_like_fast.pyx:130-176; wrapper util/like/__init__.py:7-11):
