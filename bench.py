@@ -30,7 +30,13 @@ kernel's live-measured duration, PMC traffic from the committed counter passes o
 `roofline.binding`: the roof that actually binds these kernels -- fp64 vector issue -- with achieved,
 peak, frac, the useful (recurrence) share and VALU busy.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--kernel direct|recurrence] [--dump-outputs DIR]
+A plain run does only what the headline needs: set-up, the W warm-up and K timed steps, --dump-outputs, the line.
+--full adds everything measured after the timed region: the untimed per-kernel pass (kernels_ms of k_prep, k_bin,
+k_reduce), the extra legs of the render workloads (evaluated-Gaussian count and useful_frac, the fast tail preset,
+source-upload and one-source-changed steps, the Python-API calls), `secondary`, `sustained` and the CPU baselines.
+Without it those fields are null or absent; the timed steps and every headline field are the same either way.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--kernel direct|recurrence] [--dump-outputs DIR] [--full]
 """
 import argparse
 import json
@@ -508,12 +514,14 @@ def run_render(args, env):
                                          "model_images_sample": lam[idx], "model_images_sample_index": idx})
         del lam
     t_render, n_render, render_kernel = ctx.profile_render()
-    ctx.profile(1)
-    for _ in range(20):                 # untimed: prep / binning / reduction durations for `kernels_ms`
-        field.images.render(field.sources, loglik=True)
-    t_bin, _ = ctx.profile_get("bin")
-    t_prep, _ = ctx.profile_get("prep")
-    t_red, _ = ctx.profile_get("reduce")
+    t_prep = t_bin = t_red = None
+    if args.full:
+        ctx.profile(1)
+        for _ in range(20):                 # untimed: prep / binning / reduction durations for `kernels_ms`
+            field.images.render(field.sources, loglik=True)
+        t_bin, _ = ctx.profile_get("bin")
+        t_prep, _ = ctx.profile_get("prep")
+        t_red, _ = ctx.profile_get("reduce")
     ctx.profile(False)
     stats = field.images.stats()
     if strong:   # total work is the one field's, whoever renders which rows: count it once (rank 0)
@@ -591,7 +599,7 @@ def run_render(args, env):
     out["roofline"]["binding"] = {"bound": "fp64_valu_issue", "achieved": fp["achieved"], "peak": FP64_LANE_OPS_PEAK,
                                   "unit": fp["unit"], "frac": fp["frac"], "useful_frac": None,
                                   "valu_busy_frac": fp.get("valu_busy_frac_pmc"), "pmc_source": fp.get("pmc_source") or pmc_note}
-    if world == 1 and not strong and args.legs == "all":
+    if args.full and world == 1 and not strong and args.legs == "all":
         extra_render_legs(args, env, field, out)
         ev = out["work"].get("n_gauss_evaluated_per_step")
         if ev:
@@ -610,7 +618,7 @@ def run_render(args, env):
                 ctx.profile(False)
                 out["sustained"] = {"mixed10k_2048": sustained_leg(torch, lambda: field.images.render(field.sources, loglik=True), seconds=args.sustained)}
                 out["sustained"]["gibbs10k_200"] = out["secondary"].pop("gibbs10k_200_sustained", None)
-    if world == 1 and args.cpu_sample > 0:
+    if args.full and world == 1 and args.cpu_sample > 0:
         from oracle import oracle as orc      # cpu_baseline leg only
         out["cpu_baseline"] = cpu_baseline(field, min(args.cpu_sample, S), orc)
     else:
@@ -619,7 +627,7 @@ def run_render(args, env):
 
 
 def extra_render_legs(args, env, field, out):
-    """Untimed-by-the-contract extras, measured after the timed region on rank 0 of a 1-GPU run: the
+    """Untimed-by-the-contract extras, measured after the timed region on rank 0 of a 1-GPU --full run: the
     Gaussian-pixels the kernel really evaluates, the step with the catalogue uploaded from host
     memory every time (a chain changes it before every evaluation), and the reference-API call."""
     torch, cel, synth, _lib, ctx = env["torch"], env["cel"], env["synth"], env["_lib"], env["ctx"]
@@ -767,8 +775,8 @@ def extra_render_legs(args, env, field, out):
 
 
 def secondary_legs(args, env, field):
-    """After the timed region of the default run (N = 1): bounded measurements of the OTHER configurations, so that the
-    driver's one line carries them too -- BASELINE configs[4] (Gibbs sweeps over this same field: samples/s and the
+    """After the timed region of a --full mixed10k_2048 run (N = 1): bounded measurements of the OTHER configurations, so that the
+    --full line carries them too -- BASELINE configs[4] (Gibbs sweeps over this same field: samples/s and the
     sweep's phases), configs[1] (stars1k_512) and the star-only regimes where the HBM roof binds (stars10k_2048: a star on
     every tile; stars2k_4096: a sparse 4096^2 frame, 1.34 GB of image traffic per launch -- `north_star`'s 60 %-of-HBM regime).
     Each is what `bench.py --workload NAME` reports, on fewer steps; none of them touches the headline fields."""
@@ -1122,7 +1130,7 @@ def run_fields(args, env):
                      "algorithmic_bytes_per_launch": alg_bytes},
         "work": {"n_srcpix_per_step": srcpix_all, "n_gauss_per_step_nominal": gauss_all},
         "loglik": float(np.sum(last["llb"])),
-        "cpu_baseline": _fields_cpu_baseline(args, fields[0], S) if (world == 1 and args.cpu_sample > 0) else None}))
+        "cpu_baseline": _fields_cpu_baseline(args, fields[0], S) if (args.full and world == 1 and args.cpu_sample > 0) else None}))
 
 
 def _fields_cpu_baseline(args, field, S):
@@ -1304,7 +1312,7 @@ def run_gibbs(args, env):
                    "ranks_seen_by_collective": env["roll_call"]["ranks_seen_by_collective"], "device_uuid": env["roll_call"]["device_uuid"]},
         "loglik_before": ll0, "loglik_trace_tail": trace[-3:]}
     out.update(rep)
-    if world == 1 and args.cpu_sample > 0:
+    if args.full and world == 1 and args.cpu_sample > 0:
         from oracle import oracle as orc      # cpu_baseline leg only
         out["cpu_baseline"] = gibbs_cpu_baseline(field, g, gf, orc)
     else:
@@ -1325,7 +1333,11 @@ def main():
     ap.add_argument("--tile-order", type=int, default=1, choices=[0, 1, 2])
     ap.add_argument("--layout", type=int, default=1, choices=[0, 1, 2],
                     help="render tile geometry: 0 = 64x32 (k_render), 1 = 32x64 half-wave (k_render_hw)")
-    ap.add_argument("--cpu-sample", type=int, default=400, help="sources in the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure everything the headline does not need: the per-kernel pass, the "
+                         "extra legs, `secondary`, `sustained` and the CPU baselines (--legs, --sustained, --no-projection and "
+                         "--cpu-sample shape these).  Off by default: a plain run sets up, times its steps and prints the line")
+    ap.add_argument("--cpu-sample", type=int, default=400, help="with --full: sources in the CPU baseline sample (0 = skip)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak (default, what the driver runs): one field (gibbs10k: one chain) per GPU.  strong: ONE "
                          "field cut into row strips, one per GPU (cel_images_set_window), total work fixed; gibbs10k: ONE "
@@ -1359,16 +1371,15 @@ def main():
                          "4 tile rows, one row is a quarter of it, and a tile's duration in a full launch (heaviest first: the light "
                          "tiles run last on a half-empty chip) understates the light rows")
     ap.add_argument("--legs", default="all", choices=["all", "none"],
-                    help="render workloads at N=1: 'all' (default) adds the untimed-by-the-contract extras after the timed region "
-                         "(evaluated-Gaussian count, fast tail preset, source-upload step, Python-API call); 'none' runs the "
-                         "timed region only -- what the committed rocprofv3 summaries profile, so that their per-kernel "
-                         "averages are those of the timed launches")
+                    help="render workloads at N=1 with --full: 'all' (default) adds the untimed-by-the-contract extras after the "
+                         "timed region (evaluated-Gaussian count, fast tail preset, source-upload step, Python-API call, and for "
+                         "mixed10k_2048 `secondary` and `sustained`); 'none' leaves them out")
     ap.add_argument("--sustained", type=float, default=5.0,
-                    help="default run at N = 1: seconds of back-to-back mixed10k_2048 steps after the timed region (ms per step in "
+                    help="--full run of mixed10k_2048 at N = 1: seconds of back-to-back steps after the timed region (ms per step in "
                          "0.5-s buckets + SMI clock / power samples), and 200 Gibbs sweeps likewise -> `sustained`; 0 = skip")
     ap.add_argument("--no-projection", dest="projection", action="store_false",
-                    help="default run at N = 1: skip `secondary.projected_strong_N8` (the ranks of the 8-GPU strong-scaling jobs played "
-                         "one at a time on this GPU: ~10 s)")
+                    help="--full run of mixed10k_2048 at N = 1: skip `secondary.projected_strong_N8` (the ranks of the 8-GPU "
+                         "strong-scaling jobs played one at a time on this GPU: ~10 s)")
     ap.add_argument("--master-port", type=int, default=0, help="self-launch only: rendezvous port (0 = pick a free one)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, rank 0, at most "

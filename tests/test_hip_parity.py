@@ -2144,9 +2144,8 @@ def test_binning_forms_at_the_small_catalogue_limit(cel, ctx, orc, S):
         assert n_super >= n_direct > 0
 
 
-def test_bench_line_contract_on_the_small_star_workload():
-    """bench.py end to end on BASELINE configs[1] (stars1k_512): one JSON line with the contract's keys,
-    a roofline object measured live, the extra legs, and a bounded cpu_baseline"""
+def _bench_line(*argv):
+    """bench.py run as a child process (no rank variables inherited) -> its one JSON line as a dict"""
     import json
     import os
     import subprocess
@@ -2155,27 +2154,56 @@ def test_bench_line_contract_on_the_small_star_workload():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "stars1k_512", "--steps", "10", "--warmup", "2",
-                        "--cpu-sample", "50"], capture_output=True, text=True, timeout=900, env=env)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + list(argv), capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
-    d = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+def _check_bench_contract(d, steps):
+    """the contract's keys and the live roofline of a stars1k_512 line, plain or --full alike"""
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
-    assert d["n_gpus"] == 1 and d["steps"] == 10 and d["dtype"] == "f64" and d["vs_baseline"] is None
+    assert d["n_gpus"] == 1 and d["steps"] == steps and d["dtype"] == "f64" and d["vs_baseline"] is None
+    assert d["unit"] == "source-pixel evals/s" and d["higher_is_better"] is True and d["value"] > 1e9
     assert d["config"]["workload"] == "stars1k_512" and "model" not in d["config"]
     rf = d["roofline"]
-    assert rf["bound"] == "hbm" and rf["unit"] == "GB/s" and rf["peak"] == 8000.0 and rf["launches"] == 10
+    assert rf["bound"] == "hbm" and rf["unit"] == "GB/s" and rf["peak"] == 8000.0 and rf["launches"] == steps
     np.testing.assert_allclose(rf["frac"], rf["achieved"] / rf["peak"], rtol=1e-12)
     np.testing.assert_allclose(rf["achieved"], rf["algorithmic_bytes_per_launch"] / (rf["kernel_ms"] * 1e-3) / 1e9, rtol=1e-9)
     assert 0 < rf["kernel_ms"] < d["ms_per_step"]
-    assert d["value"] > 1e9 and d["work"]["n_gauss_evaluated_per_step"] > 0
+
+
+def test_bench_line_contract_on_the_small_star_workload():
+    """bench.py --full end to end on BASELINE configs[1] (stars1k_512): one JSON line with the contract's keys,
+    a roofline object measured live, the extra legs, and a bounded cpu_baseline"""
+    d = _bench_line("--workload", "stars1k_512", "--steps", "10", "--warmup", "2", "--cpu-sample", "50", "--full")
+    _check_bench_contract(d, 10)
+    assert d["work"]["n_gauss_evaluated_per_step"] > 0
+    assert all(d["kernels_ms"][k] is not None for k in ("k_prep", "k_bin", "k_reduce")), d["kernels_ms"]      # the per-kernel pass ran
     assert d["ms_per_step_with_source_upload"] > 0 and d["python_api_ms"] > 0 and d["python_api_loglik_rel_diff"] < 1e-12
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and cb["one_thread"]["cores"] == 1
     assert "reference_semantics_fullframe" in cb
+
+
+def test_bench_plain_line_is_the_headline_only(tmp_path):
+    """bench.py without --full: the same contract line and --dump-outputs, and nothing measured after the timed region --
+    no per-kernel pass, no extra legs, no CPU baseline"""
+    out = tmp_path / "dump"
+    d = _bench_line("--workload", "stars1k_512", "--steps", "10", "--warmup", "2", "--dump-outputs", str(out))
+    _check_bench_contract(d, 10)
+    assert d["cpu_baseline"] is None
+    assert d["kernels_ms"]["k_render"] == d["roofline"]["kernel_ms"]
+    assert all(d["kernels_ms"][k] is None for k in ("k_prep", "k_bin", "k_reduce")), d["kernels_ms"]
+    for k in ("ms_per_step_with_source_upload", "python_api_ms", "tail_log_fast_preset", "secondary", "sustained"):
+        assert k not in d, k
+    assert "n_gauss_evaluated_per_step" not in d["work"] and d["roofline"]["binding"]["useful_frac"] is None
+    assert sorted(p.name for p in out.iterdir()) == ["loglik.npy", "loglik_band.npy", "model_images_sample.npy",
+                                                      "model_images_sample_index.npy"]
+    assert np.isfinite(np.load(str(out / "loglik.npy"))).all()
 
 
 def test_rccl_collective_path_in_a_one_rank_group():

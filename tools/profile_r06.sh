@@ -61,9 +61,10 @@ if [ $what = proj ] || [ $what = all ]; then
   echo "== projections"; ls $root/gpurun_out/r06_proj_*.json
 fi
 if [ $what = diag ] || [ $what = all ]; then
-  # where the split's time goes and what its queue looks like; the render's work counters; the default line as the driver runs it
+  # where the split's time goes and what its queue looks like; the render's work counters; the default line with every leg (--full)
   (cd $root && python3 tools/ablate_split.py > gpurun_out/r06_split_ablation.txt 2>&1)
   (cd $root && python3 tools/tile_timeline.py --workload mixed10k_2048 --tail-log 24 > gpurun_out/r06_render_work.txt 2>&1)
-  (cd $root && python3 bench.py --steps 20 --warmup 5 > gpurun_out/r06_default_bench_line.json 2> gpurun_out/r06_default_bench_line.log)
+  (cd $root && python3 bench.py --full --steps 20 --warmup 5 > /tmp/r06_default_bench_line.json 2> /tmp/r06_default_bench_line.log)
+  cp /tmp/r06_default_bench_line.json $root/profiles/      # what DESIGN.md section 8 quotes; only a run that exited 0 gets here (set -e)
   echo "== diag"; head -20 $root/gpurun_out/r06_split_ablation.txt; head -4 $root/gpurun_out/r06_render_work.txt
 fi

@@ -1,7 +1,7 @@
 #!/bin/bash
-# usage: sweep.sh "<flags1>" "<flags2>" ...   (each run prints kernel ms)
+# usage: sweep.sh "<flags1>" "<flags2>" ...   (each run prints kernel ms: --full, for the per-kernel pass)
 for f in "$@"; do
-  timeout -k 10 200 python bench.py --steps 10 --warmup 2 --cpu-sample 0 $f 2>/dev/null | python3 -c "
+  timeout -k 10 200 python bench.py --full --steps 10 --warmup 2 --cpu-sample 0 $f 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
