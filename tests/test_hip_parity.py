@@ -707,6 +707,15 @@ def test_full_size_gibbs_kernels_properties(cel, ctx, big_field):
     np.testing.assert_allclose(xt, xt_d, rtol=3e-10, atol=1e-12)
     np.testing.assert_allclose(mass, mass_d, rtol=1e-10)
     np.testing.assert_allclose(nz, nz_d, rtol=1e-10)                # (the sky term is nelec * eps / lambda summed: lambda at the render's threshold)
+    # the same cross-check at the strict threshold (T = 32 for the field render too): the 3e-10 above is the T = 24 leg's alone
+    with tail_log(ctx, "strict"):
+        xt_s, _, _ = f.images.estep_stats(f.sources)
+        ctx.set_kernel("direct")
+        try:
+            xt_sd, _, _ = f.images.estep_stats(f.sources)
+        finally:
+            ctx.set_kernel("recurrence")
+    np.testing.assert_allclose(xt_s, xt_sd, rtol=1e-10, atol=1e-12)
 
 
 @pytest.mark.parametrize("world,frac_gal,tail", [(2, 0.5, "default"), (2, 0.5, "strict"), (3, 0.5, "default"), (3, 0.0, "default")])
