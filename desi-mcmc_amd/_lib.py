@@ -61,6 +61,7 @@ SYMBOLS = [
     ("cel_sources_destroy", C.c_int, [C.c_void_p]),
     ("cel_sources_set", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     ("cel_sources_set_rows", C.c_int, [C.c_void_p, C.c_int64, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p]),
+    ("cel_sources_get", C.c_int, [C.c_void_p, c_int32_p, c_double_p, c_double_p, c_double_p]),
     ("cel_render_field", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_double_p, c_double_p]),
     ("cel_field_stats", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
     ("cel_gamma_streams", C.c_int, [C.c_void_p, C.c_int64, c_double_p, C.c_uint64, c_double_p]),

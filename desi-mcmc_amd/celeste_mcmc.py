@@ -439,8 +439,12 @@ class ModelGibbs(object):
             if not np.array_equal(act, self.active):
                 raise RuntimeError("cel_flux_conditionals: the device's patches are not those of the split this chain made")
             self.fluxes = np.where(self.active[:, None], new, self.fluxes)
-            # the device's catalogue holds the new counts already: what _sources compares with is brought up to date, not uploaded
-            f._uploaded = (f._uploaded[0], f._uploaded[1], self.counts(f), f._uploaded[3])
+            # the device's catalogue holds the new counts of the ACTIVE sources already: what _sources compares with is brought up
+            # to date for those rows, not uploaded.  The kernel left the other rows alone, so their record stays what the device
+            # holds: had their fluxes been changed on the host since the last upload, the next _sources sees it and uploads.
+            cnt = f._uploaded[2].copy()
+            cnt[self.active] = self.counts(f)[self.active]
+            f._uploaded = (f._uploaded[0], f._uploaded[1], cnt, f._uploaded[3])
             self.timing["flux"] += time.perf_counter() - t0
             return self.fluxes
         band_counts = np.zeros((self.S, 5))

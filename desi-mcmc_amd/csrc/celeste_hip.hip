@@ -849,6 +849,24 @@ int cel_sources_set(cel_sources *s, int64_t S, const int32_t *type, const double
     return CEL_OK;
 }
 
+// the catalogue as the device holds it, copied to host arrays (any may be NULL): the device samplers rewrite it in place
+// (cel_flux_conditionals the counts, the slice samplers the locations and shapes), and this is how a caller or a test sees what
+// they left
+int cel_sources_get(cel_sources *s, int32_t *type, double *radec, double *counts, double *shape) {
+    if (!s) return fail(CEL_ERR_INVALID, "cel_sources_get: null argument");
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    const int64_t S = s->S;
+    if (S > 0) {
+        if (type) HIP_TRY(hipMemcpyAsync(type, s->d_type, sizeof(int) * S, hipMemcpyDeviceToHost, st));
+        if (radec) HIP_TRY(hipMemcpyAsync(radec, s->d_radec, sizeof(double) * 2 * S, hipMemcpyDeviceToHost, st));
+        if (counts) HIP_TRY(hipMemcpyAsync(counts, s->d_counts, sizeof(double) * s->B * S, hipMemcpyDeviceToHost, st));
+        if (shape) HIP_TRY(hipMemcpyAsync(shape, s->d_shape, sizeof(double) * 4 * S, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return CEL_OK;
+}
+
 // n rows of the catalogue replaced (host arrays, packed: idx[n], type[n], radec[n][2], counts[n][B], shape[n][4]): what a
 // caller that changed ONE source between two evaluations uploads instead of the whole catalogue (the RJ moves and slice
 // steps of CelestePy/util/infer/mcmc_transitions.py:37-152 call celeste_likelihood after every such change)

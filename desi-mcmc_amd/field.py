@@ -166,6 +166,14 @@ class SourceSet(object):
                                              L.dptr(radec), L.dptr(counts), L.dptr(shape)))
         return self
 
+    def get(self):
+        """the catalogue as the device holds it now (cel_sources_get) -> (type[S], radec[S,2], counts[S,B], shape[S,4]): the device
+        samplers rewrite counts, locations and shapes in place"""
+        S = self.S
+        typ, radec, counts, shape = np.zeros(S, dtype=np.int32), np.zeros((S, 2)), np.zeros((S, self.B)), np.zeros((S, 4))
+        L.check(L.lib().cel_sources_get(self._h, typ.ctypes.data_as(L.c_int32_p), L.dptr(radec), L.dptr(counts), L.dptr(shape)))
+        return typ, radec, counts, shape
+
     def set_device(self, S, typ_ptr, radec_ptr, counts_ptr, shape_ptr):
         """Same, from raw device pointers (e.g. torch tensors' data_ptr())."""
         L.check(L.lib().cel_sources_set(self._h, int(S), C.c_void_p(typ_ptr), C.c_void_p(radec_ptr),

@@ -261,6 +261,10 @@ int cel_sources_set(cel_sources *src, int64_t S, const int32_t *type, const doub
  * CelestePy/util/infer/mcmc_transitions.py:37-152 call celeste_likelihood(list of SrcParams) after every such change. */
 int cel_sources_set_rows(cel_sources *src, int64_t n, const int32_t *idx, const int32_t *type, const double *radec,
                          const double *counts, const double *shape);
+/* The catalogue as the device holds it now, to host arrays laid out as cel_sources_set takes them (any may be NULL).  The
+ * device samplers rewrite it in place -- cel_flux_conditionals the counts of the sources that have a patch, the slice samplers
+ * the locations and shapes -- and this reads back what they left. */
+int cel_sources_get(cel_sources *src, int32_t *type, double *radec, double *counts, double *shape);
 
 /* ---- the hot path --------------------------------------------------------------------- */
 /* gen_model_image (celeste.py:203-219) for every band + celeste_likelihood /

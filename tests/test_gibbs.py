@@ -1308,6 +1308,7 @@ def test_device_gamma_streams_are_the_host_sampler(cel):
     per-element SplitMix64 streams, the same Marsaglia-Tsang decisions: values equal to rounding (cos and log are the
     device's), shapes from 0.05 (the boosted branch) to 1e7, order-free; bad shapes are refused."""
     from desi_mcmc_amd.celeste_mcmc import gamma_by_stream
+    from test_flux_law import MARGIN, MARGIN_SHARE, SplitMixSource, restated_gamma
     ctx = cel.default_context(0)
     rs = np.random.RandomState(0)
     a = np.concatenate([np.exp(rs.uniform(np.log(0.05), np.log(1e7), 60000)), [1.0, 0.999999, 1.0 / 3.0 + 1e-9, 5.0, 1e-3]])
@@ -1315,8 +1316,16 @@ def test_device_gamma_streams_are_the_host_sampler(cel):
         dev = ctx.gamma_streams(a, seed)
         host = gamma_by_stream(a, seed, np.arange(a.shape[0]))
         assert np.all(dev[a >= 0.05] > 0) and np.all(np.isfinite(dev)) and np.all(dev >= 0)      # (a = 1e-3: u^1000 may underflow, on the host too)
-        close = np.abs(dev - host) <= 1e-12 * np.abs(host)
-        assert close.mean() > 0.99999, close.mean()          # (an accept / reject decision within rounding of its boundary may differ)
+        close = np.abs(dev - host) <= 1e-12 * np.abs(host) + 2e-323          # (a denormal carries fewer bits: four of its steps)
+        # an accept / reject decision within rounding of its boundary may differ, and nothing else may: every mismatch has to be an
+        # element whose smallest decision margin, by the sampler restated in test_flux_law, is at most 1e-9 -- and at most a 1e-6
+        # share of the elements may have one (these seeds have none).  Below the vouched range (a = 1e-3) the value is the host's.
+        vouched = np.nonzero(a >= 0.05)[0]
+        margin = restated_gamma(a[vouched], SplitMixSource(seed, vouched))[2]
+        small = margin <= MARGIN
+        assert small.sum() <= MARGIN_SHARE * vouched.size, small.sum()
+        assert np.all(close[vouched] | small), np.nonzero(~(close[vouched] | small))
+        assert np.all(close[a < 0.05])
     assert np.array_equal(ctx.gamma_streams(a, 11), ctx.gamma_streams(a, 11))
     assert np.array_equal(ctx.gamma_streams(a[:100], 11), ctx.gamma_streams(a, 11)[:100])     # element i depends on (seed, i) only
     big = ctx.gamma_streams(np.full(200000, 2.5), 3)
