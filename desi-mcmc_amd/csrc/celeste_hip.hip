@@ -41,6 +41,7 @@
 
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -112,6 +113,50 @@ struct Prof {
     unsigned seen[CEL_K_COUNT] = {0};   // launches of each kernel since the reset (level 3 times every fourth)
 };
 
+// The context's scratch slots (scratch_get), by purpose.  A slot's contents are dead when the call that took it returns --
+// except SCR_VALUES after cel_stamp_mass_begin: the masses WAIT there (im->d_mass) for cel_stamp_mass_end, and none of the calls
+// the header allows in between (cel_gamma_streams, cel_samples_fetch, cel_images_set_epsilon) takes that slot.
+enum ScratchSlot {
+    SCR_PLL_BOXES,    // cel_patch_loglik_multi: the caller's boxes, their photon rectangles, the owners
+    SCR_OFFSETS,      // cel_patch_loglik_multi, cel_photon_split: a caller's patch offsets
+    SCR_VALUES,       // cel_patch_loglik_multi: the jobs' sums; cel_photon_split: the noise partials; cel_stamp_mass_begin: the masses (PENDING)
+    SCR_PATCH_DATA,   // cel_patch_loglik_multi, cel_photon_split: a caller's patch pixels, staged; cel_samples_fetch: sums the split did not form
+    SCR_TMP_A,        // cel_render_stamps: jobs; cel_estep_stats: xtilde; cel_loglik_grad: sums; cel_mog_loglike: components; cel_galaxy_mixture_params: inputs
+    SCR_TMP_B,        // cel_render_stamps: boxes; cel_estep_stats: masses; cel_loglik_grad: staged gradients; cel_mog_loglike: points; cel_galaxy_mixture_params: outputs
+    SCR_TMP_C,        // cel_render_stamps: offsets; cel_estep_stats: per-entry sums; cel_mog_loglike: outputs; cel_flux_conditionals, cel_gamma_streams: inputs + outputs
+    SCR_HOST_IO,      // cel_sources_set_rows: the staged rows; cel_render_stamps: the stamps on their way to the host
+    SCR_COUNT
+};
+static_assert(SCR_COUNT == 8, "eight scratch slots");
+
+// The context's pinned mailbox: where the entry points' small readbacks land, at fixed offsets.  The union's words are shared on
+// purpose: one call uses them at a time and nothing in the union outlives its call.
+union MailShared {
+    unsigned long long bin_coarse[2];    // render_impl: coarse cursor, coarse overflow -- behind bin_fine, in the same copy
+    int64_t scan_total;                  // cel_photon_split: the total of its patch-layout scan, then of its photon-list scan
+    int slice_flags[12];                 // flag slot 0 (11 ints): cel_slice_locations' two job counts, then its even batches; cel_slice_sample's six flags
+    struct {
+        unsigned long long flags_[3];
+        unsigned long long slice_bytes;  // cel_slice_locations' byte counter: over flags [6..7], once the last batch has been read
+        double field_stats[2];           // cel_field_stats' pair
+    } w;
+};
+struct Mailbox {
+    double ll_band[MAX_BANDS];           // the bands' sums: render_impl, cel_photon_split, cel_estep_stats
+    unsigned long long bin_fine[2];      // + 0: fine cursor, fine overflow of the binning pass (render_impl)
+    MailShared sh;                       // + 2
+    int slice_flags1[12];                // + 8: cel_slice_locations' flag slot 1 (11 ints): its odd batches, the fused rounds' totals
+    int mass_todo;                       // + 14: the mass short cut's to-do count, PENDING from cel_stamp_mass_begin to _end
+    int unused_[3];
+};
+static_assert(sizeof(Mailbox) == sizeof(double) * (MAX_BANDS + 16), "the mailbox is MAX_BANDS + 16 doubles");
+static_assert(offsetof(Mailbox, bin_fine) == sizeof(double) * MAX_BANDS && offsetof(Mailbox, sh) == sizeof(double) * (MAX_BANDS + 2) &&
+              offsetof(MailShared, w.slice_bytes) == sizeof(int) * 6 && offsetof(MailShared, w.field_stats) == sizeof(double) * 4 &&
+              offsetof(Mailbox, slice_flags1) == sizeof(double) * (MAX_BANDS + 8) && offsetof(Mailbox, mass_todo) == sizeof(double) * (MAX_BANDS + 14),
+              "the mailbox members keep their offsets");
+static_assert(offsetof(Mailbox, mass_todo) >= offsetof(Mailbox, slice_flags1) + sizeof(int) * 11 && sizeof(MailShared) <= sizeof(double) * 6,
+              "the pending to-do count shares no word: flag slot 1 ends before it, the shared words before flag slot 1");
+
 #ifndef SLICE_FUSE_DEFAULT
 #define SLICE_FUSE_DEFAULT 0       // CEL_OPT_SLICE_FUSE: off.  Built and measured in round 6 (cel_slice_locations): no gain at any threshold
 #endif
@@ -149,14 +194,14 @@ struct cel_ctx {
     int tile_layout = 1;      // 0: 64 x tile_rows tiles, one lane per column (k_render)
                               // 1: 32 x 64 tiles, two component groups per column (k_render_hw)
     Prof prof;
-    PinnedBuf<double> pinned;   // MAX_BANDS + 16 doubles of pinned host memory for readbacks
+    PinnedBuf<Mailbox> mail;    // MAX_BANDS + 16 doubles of pinned host memory for readbacks
     hipEvent_t slice_ev[2] = {nullptr, nullptr};     // cel_slice_locations: one per batch of rounds in flight
     // grow-only device scratch for the small per-call buffers of the stamp / patch-ll entry
     // points (an allocation + free pair per call costs more than the kernels they bracket)
-    DevBuf<char> scratch[8];
+    DevBuf<char> scratch[SCR_COUNT];
 };
 
-static int scratch_get(cel_ctx *c, int slot, size_t bytes, void **out) {
+static int scratch_get(cel_ctx *c, ScratchSlot slot, size_t bytes, void **out) {
     if (bytes == 0) bytes = 8;
     HIP_TRY(c->scratch[slot].grow(bytes, bytes + bytes / 2 + 256, c->stream));
     *out = c->scratch[slot];
@@ -180,7 +225,7 @@ struct cel_images {
     // per-render scratch, grown on demand
     DevBuf<double> d_slabs;          // k_render_hw<, PARTS>: PARTS accumulator slabs per render tile, allocated with the first such launch
     DevBuf<int> d_part_cnt;          // ... and the tiles' arrival counters
-    // grown together (ensure_recs); d_recs is allocated last, so its capacity is the group's
+    // grown together (ensure_recs: grow_group); d_recs is named last, so its capacity is the group's
     DevBuf<SrcRec> d_recs;
     DevBuf<int4> d_boxes;
     DevBuf<int> d_kind;
@@ -225,7 +270,7 @@ struct cel_images {
     bool ssum_valid = false;
     // host copies of the last resident split's sums and patch offsets (pinned), made INSIDE cel_photon_split before its last
     // wait: cel_samples_fetch hands them over without touching the stream, on which the photon lists are still being compacted
-    // (grown together; h_ssum is allocated last, so its capacity is the pair's)
+    // (grown together; h_ssum is named last, so its capacity is the pair's)
     PinnedBuf<double> h_ssum;
     PinnedBuf<int64_t> h_soff;
     bool hsum_valid = false;
@@ -233,7 +278,7 @@ struct cel_images {
     bool nz_valid = false;
     DevBuf<double> d_rate;      // per-pixel total rates of the photon split (strict boxes), B*H*W, on first use
     bool rate_in_lambda = false;    // the last split read its totals from the model image itself (CEL_OPT_SPLIT_FULL_BOX with a current image)
-    // the resident split's patch layout, grown together (cel_photon_split); d_sbox is allocated last, so its capacity is the group's
+    // the resident split's patch layout, grown together (cel_photon_split: grow_group); d_sbox is named last, so its capacity is the group's
     DevBuf<int4> d_sbox;
     DevBuf<int4> d_snz;         // nonzero rectangles of the resident sample patches (k_patch_nzbox)
     DevBuf<int64_t> d_soff;
@@ -460,7 +505,7 @@ int cel_ctx_create(int device, void *stream, cel_ctx **out) {
         int ncu = 0;
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) c->n_cu = ncu;
     }
-    hipError_t e = c->pinned.grow(MAX_BANDS + 16, MAX_BANDS + 16, c->stream);
+    hipError_t e = c->mail.grow(1, 1, c->stream);
     if (e != hipSuccess) { delete c; return fail(CEL_ERR_HIP, "pinned readback buffer: %s", hipGetErrorString(e)); }
     // profile constants, normalised as mixture_profiles.py:13,19
     double amp[K_PROF], var[K_PROF], se = 0.0, sd = 0.0;
@@ -891,7 +936,7 @@ int cel_sources_set_rows(cel_sources *s, int64_t n, const int32_t *idx, const in
     const size_t ints = ((size_t)(2 * n) * sizeof(int) + 7) & ~(size_t)7;
     const size_t bytes = ints + sizeof(double) * (size_t)n * (2 + B + 4);
     char *d = nullptr;
-    int rc = scratch_get(c, 7, bytes, (void **)&d);
+    int rc = scratch_get(c, SCR_HOST_IO, bytes, (void **)&d);
     if (rc) return rc;
     std::vector<char> h(bytes);
     memcpy(h.data(), idx, sizeof(int) * n);
@@ -925,14 +970,9 @@ int cel_sources_set_rows(cel_sources *s, int64_t n, const int32_t *idx, const in
 // ---- prep + bin (shared by field and stamps) ------------------------------------------------
 static int ensure_recs(cel_images *im, int64_t n) {
     if (n <= im->d_recs.cap) return CEL_OK;
-    HIP_TRY(hipStreamSynchronize(im->ctx->stream));
-    im->d_recs.reset(); im->d_boxes.reset(); im->d_kind.reset(); im->d_status.reset();
     im->recs_gen = im->hbox_gen = 0;
     const int64_t cap = n + n / 4 + 64;
-    HIP_TRY(im->d_boxes.grow(n, cap, im->ctx->stream));
-    HIP_TRY(im->d_kind.grow(n, cap, im->ctx->stream));
-    HIP_TRY(im->d_status.grow(n, cap, im->ctx->stream));
-    HIP_TRY(im->d_recs.grow(n, cap, im->ctx->stream));
+    HIP_TRY(grow_group(im->ctx->stream, im->d_boxes, cap, im->d_kind, cap, im->d_status, cap, im->d_recs, cap));
     return CEL_OK;
 }
 
@@ -1073,8 +1113,8 @@ static int render_small_stars(cel_images *im, cel_sources *src, int flags, bool 
                 comp[k] = (t - sum[k]) - y;
                 sum[k] = t;
             }
-            c->pinned[b] = ((sum[0] + sum[1]) + (sum[2] + sum[3])) + ((sum[4] + sum[5]) + (sum[6] + sum[7]));
-            im->h_llband[b] = c->pinned[b];
+            c->mail->ll_band[b] = ((sum[0] + sum[1]) + (sum[2] + sum[3])) + ((sum[4] + sum[5]) + (sum[6] + sum[7]));
+            im->h_llband[b] = c->mail->ll_band[b];
         }
         im->llband_on_host = true;              // d_llband does not hold this render's sums (cel_images_loglik_device uploads them)
     }
@@ -1086,6 +1126,107 @@ static int render_small_stars(cel_images *im, cel_sources *src, int flags, bool 
     im->last_entries = 0;
     *done = true;
     return CEL_OK;
+}
+
+// What one render does, decided once from (context, images, sources, flags, lambda_out) before anything is queued.
+struct RenderPlan {
+    int flags;                      // the caller's, without the internal CEL_RENDER_KEEP_LISTS
+    bool keep_lists, own_rows;      // own_rows: the image set owns a part of its rows (cel_images_set_noise_rows) ...
+    int own_ty0, own_ty1;           // ... the tile rows a log-likelihood adds
+    bool diag, stars_only;          // the kernel: the instantiation with counters / time stamps / ablations; the star-tile kernel
+    bool small_stars, incremental;  // may be TRIED: the one-launch path of a small star field; the incremental render (the changed rows decide)
+    int parts, parts_used;          // blocks per tile launched; what the image vouches for (0: the star-tile kernel's bits)
+    int tile_order;
+    bool bin_direct;
+};
+
+static int plan_render(const cel_images *im, const cel_sources *src, int flags, const double *lambda_out, RenderPlan &p) {
+    const cel_ctx *c = im->ctx;
+    const int64_t S = src->S;
+    const int T = im->B * im->ntx * im->nty;
+    p.keep_lists = (flags & CEL_RENDER_KEEP_LISTS) != 0;
+    p.flags = flags &= ~CEL_RENDER_KEEP_LISTS;
+    // the rows this image set OWNS (cel_images_set_noise_rows; default: all): the log-likelihood adds their tiles only
+    p.own_rows = im->noise_y0 > 0 || im->noise_y1 < im->H;
+    p.own_ty0 = 0; p.own_ty1 = im->nty;
+    if (p.own_rows && (flags & CEL_RENDER_LOGLIK)) {
+        if (im->noise_y0 % im->TH != 0 || (im->noise_y1 % im->TH != 0 && im->noise_y1 < im->H))
+            return fail(CEL_ERR_INVALID, "the owned rows [%d, %d) must begin and end on render-tile rows (%d) for a log-likelihood",
+                        im->noise_y0, im->noise_y1, im->TH);
+        p.own_ty0 = im->noise_y0 / im->TH;
+        p.own_ty1 = std::min(im->nty, (im->noise_y1 + im->TH - 1) / im->TH);
+    }
+    // a catalogue without galaxies: the star-tile kernel (k_render_stars.h), when the frame has more tiles than the
+    // general kernel has wave slots (STAR_TILES_MIN; measured break-even, tools/star_tiles_threshold.py); the
+    // instantiation with counters / time stamps / ablations exists for the general kernel only
+    p.diag = c->tile_timing || (c->debug & ~64);
+    const bool stars = im->TW == HW_TW && !p.diag && c->variant != 0 && src->n_gal == 0 && im->star_one_segment;
+    p.stars_only = stars && c->star_tiles && (c->star_tiles == 2 || T > STAR_TILES_MIN);    // (1 and 3: the rule; 3 = without the one-launch small path)
+    // a small star field (configs[1]): one launch instead of four (k_small_stars.h) -- unless a caller needs the tile lists
+    // (the photon split, the E-step), an image of its own or the diagnostics
+    p.small_stars = stars && S > 0 && S <= SMALL_MAX_S && T <= STAR_TILES_MIN && c->star_tiles == 1 && !im->small_off && !lambda_out &&
+                    !p.keep_lists && !(flags & CEL_RENDER_STRICT) && !p.own_rows;
+    p.parts = p.diag ? 1 : tile_parts_of(c, im);
+    p.parts_used = (im->TW == HW_TW && !p.diag) ? p.parts : 1;
+    if (p.stars_only) p.parts_used = 0;         // (the star-tile kernel adds a pixel's stars in another order: not the general kernel's bits)
+    p.incremental = c->incremental && !lambda_out && !(flags & (CEL_RENDER_NO_STORE | CEL_RENDER_STRICT)) && im->TW == HW_TW &&
+                    c->variant != 0 && !p.diag && !p.stars_only && p.parts == 1 && S > 0 && S == im->last_S &&
+                    im->lambda_gen != 0 && im->lambda_uid == src->uid && im->lambda_T == c->render_T && im->lambda_parts == 1 && im->lambda_gen != src->gen &&
+                    im->lambda_gen >= src->full_gen &&
+                    im->lists_gen == im->lambda_gen && im->recs_gen == im->lambda_gen && (int64_t)src->row_gen.size() == S &&
+                    (!(flags & CEL_RENDER_LOGLIK) || (im->partials_gen == im->lambda_gen && !im->nelec_shared));
+    p.tile_order = tile_order_of(c, im);
+    // a small catalogue is binned by one wave per tile into per-tile segments of S entries (k_bin_direct)
+    p.bin_direct = S > 0 && S <= BIN_DIRECT_MAX_S && (int64_t)T * S <= ((int64_t)1 << 25);
+    return CEL_OK;
+}
+
+// the fine binning kernel: the one-kernel form (first event e0) or the second half of the two-level form
+static void launch_bin_fine(cel_ctx *c, cel_images *im, int64_t S, int NS, bool one_level, hipEvent_t e0, hipEvent_t e1) {
+    auto go = [&](auto kernel, int waves) {
+        LAUNCH_EV(kernel, dim3(NS), dim3(64 * waves), c->stream, e0, e1,
+                  im->d_boxes, im->d_kind, S, im->ntx, im->nty, im->TH, im->TW,
+                  im->nsx, im->nsy, im->d_sup_cnt, im->d_sup_off, im->d_clist, im->d_clist.cap, im->d_tile_cnt,
+                  im->d_tile_nstar, im->d_tile_work, im->d_tile_off, im->d_cursor, im->d_lists, im->d_lists.cap,
+                  (int *)(im->d_cursor + 1), (int *)(im->d_cursor + 3));
+    };
+    // (16-wave blocks while every super-tile gets a CU of its own, 8-wave blocks -- two to a CU -- beyond that: k_bin2.h)
+    const bool small_blocks = NS > c->n_cu;
+    if (!one_level) { if (small_blocks) go(k_bin_fine_blk<false, 8>, 8); else go(k_bin_fine_blk<false, 16>, 16); }
+    else { if (small_blocks) go(k_bin_fine_blk<true, 8>, 8); else go(k_bin_fine_blk<true, 16>, 16); }
+}
+
+// the render kernel of the image set's tile layout and the plan
+static void launch_render(cel_ctx *c, const cel_images *im, const RenderPlan &p, int T, const RenderArgs &a, hipEvent_t e0, hipEvent_t e1) {
+    hipStream_t st = c->stream;
+    if (im->TW == QW_TW)
+        LAUNCH_EV(k_render_qw, dim3(T), dim3(64), st, e0, e1, a);
+    else if (im->TW == HW_TW) {
+        // the production instantiation has no diagnostic code in it; counters, time stamps and (CEL_ABLATE
+        // builds) ablations live in the second one
+        if (p.diag) LAUNCH_EV(k_render_hw<true>, dim3(T), dim3(64), st, e0, e1, a);
+        else if (p.stars_only) LAUNCH_EV((k_render_stars<2, false>), dim3(T), dim3(64), st, e0, e1, a);
+        else if (p.parts > 1) {
+            const unsigned grid = (unsigned)(((T + 7) / 8) * 8 * p.parts);
+            if (p.parts == 4) LAUNCH_EV((k_render_hw<false, 4>), dim3(grid), dim3(64), st, e0, e1, a);
+            else LAUNCH_EV((k_render_hw<false, 2>), dim3(grid), dim3(64), st, e0, e1, a);
+        }
+        else LAUNCH_EV(k_render_hw<false>, dim3(T), dim3(64), st, e0, e1, a);
+    }
+    else if (im->TH == 64)
+        LAUNCH_EV((k_render<64>), dim3(T), dim3(64), st, e0, e1, a);
+    else
+        LAUNCH_EV((k_render<32>), dim3(T), dim3(64), st, e0, e1, a);
+}
+
+// the bands' sums in the mailbox, handed to the caller
+static void ll_from_mailbox(const cel_ctx *c, int B, double *ll_band, double *ll_total) {
+    double tot = 0.0;
+    for (int b = 0; b < B; b++) {
+        if (ll_band) ll_band[b] = c->mail->ll_band[b];
+        tot += c->mail->ll_band[b];
+    }
+    if (ll_total) *ll_total = tot;
 }
 
 static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_band, double *ll_total, double *lambda_out) {
@@ -1102,34 +1243,14 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
     const int64_t S = src->S;
     const int T = im->B * im->ntx * im->nty;
     int rc;
-    // a small star field (configs[1]): one launch instead of four (k_small_stars.h) -- unless a caller needs the tile lists
-    // (the photon split, the E-step), an image of its own or the diagnostics
-    const bool keep_lists = (flags & CEL_RENDER_KEEP_LISTS) != 0;
-    flags &= ~CEL_RENDER_KEEP_LISTS;
-    // the rows this image set OWNS (cel_images_set_noise_rows; default: all): the log-likelihood adds their tiles only
-    const bool own_rows = im->noise_y0 > 0 || im->noise_y1 < im->H;
-    int own_ty0 = 0, own_ty1 = im->nty;
-    if (own_rows && (flags & CEL_RENDER_LOGLIK)) {
-        if (im->noise_y0 % im->TH != 0 || (im->noise_y1 % im->TH != 0 && im->noise_y1 < im->H))
-            return fail(CEL_ERR_INVALID, "the owned rows [%d, %d) must begin and end on render-tile rows (%d) for a log-likelihood",
-                        im->noise_y0, im->noise_y1, im->TH);
-        own_ty0 = im->noise_y0 / im->TH;
-        own_ty1 = std::min(im->nty, (im->noise_y1 + im->TH - 1) / im->TH);
-    }
-    if (S > 0 && S <= SMALL_MAX_S && T <= STAR_TILES_MIN && im->TW == HW_TW && c->variant != 0 && c->star_tiles == 1 &&
-        !c->tile_timing && !(c->debug & ~64) && src->n_gal == 0 && im->star_one_segment && !im->small_off && !lambda_out &&
-        !keep_lists && !(flags & CEL_RENDER_STRICT) && !own_rows) {
+    RenderPlan plan;
+    if ((rc = plan_render(im, src, flags, lambda_out, plan))) return rc;
+    flags = plan.flags;
+    if (plan.small_stars) {
         bool done = false;
         if ((rc = render_small_stars(im, src, flags, &done))) return rc;
         if (done) {
-            if (flags & CEL_RENDER_LOGLIK) {
-                double tot = 0.0;
-                for (int b = 0; b < im->B; b++) {
-                    if (ll_band) ll_band[b] = c->pinned[b];
-                    tot += c->pinned[b];
-                }
-                if (ll_total) *ll_total = tot;
-            }
+            if (flags & CEL_RENDER_LOGLIK) ll_from_mailbox(c, im->B, ll_band, ll_total);
             return CEL_OK;
         }
     }
@@ -1141,17 +1262,13 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
     // render, so pixels, partials and log-likelihoods are the full render's bit for bit; every other tile's pixels and partial
     // are still valid.  Source preparation and binning run in full (66 us at configs[2]); a render with nothing changed, or
     // after a whole-catalogue upload, is a full render -- nothing is ever answered from a cache.
-    const bool diag_r = c->tile_timing || (c->debug & ~64);
-    const bool stars_only_r = im->TW == HW_TW && !diag_r && c->star_tiles && src->n_gal == 0 && im->star_one_segment &&
-                              c->variant != 0 && (c->star_tiles == 2 || T > STAR_TILES_MIN);
     DeltaRows delta;
     delta.n = 0;
-    bool incr = c->incremental && !lambda_out && !(flags & (CEL_RENDER_NO_STORE | CEL_RENDER_STRICT)) && im->TW == HW_TW &&
-                c->variant != 0 && !diag_r && !stars_only_r && tile_parts_of(c, im) == 1 && S > 0 && S == im->last_S &&
-                im->lambda_gen != 0 && im->lambda_uid == src->uid && im->lambda_T == c->render_T && im->lambda_parts == 1 && im->lambda_gen != src->gen &&
-                im->lambda_gen >= src->full_gen &&
-                im->lists_gen == im->lambda_gen && im->recs_gen == im->lambda_gen && (int64_t)src->row_gen.size() == S &&
-                (!(flags & CEL_RENDER_LOGLIK) || (im->partials_gen == im->lambda_gen && !im->nelec_shared));
+    bool incr = plan.incremental;
+    auto mark_dirty = [&] {
+        hipLaunchKernelGGL(k_mark_dirty, dim3((unsigned)((delta.n * im->B + 255) / 256)), dim3(256), 0, st, delta, (const int4 *)im->d_boxes, S, im->B,
+                           im->ntx, im->nty, im->TW, im->TH, im->d_dirty);
+    };
     if (incr) {
         for (int64_t s = 0; s < S && incr; s++)
             if (src->row_gen[(size_t)s] > im->lambda_gen) {
@@ -1163,20 +1280,15 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
     if (incr) {
         HIP_TRY(im->d_dirty.grow(T, T, st));
         HIP_TRY(hipMemsetAsync(im->d_dirty, 0, sizeof(int) * (size_t)T, st));
-        // the tiles the changed sources' OLD boxes touch (before k_prep rewrites the boxes) ...
-        hipLaunchKernelGGL(k_mark_dirty, dim3((unsigned)((delta.n * im->B + 255) / 256)), dim3(256), 0, st, delta, (const int4 *)im->d_boxes, S, im->B,
-                           im->ntx, im->nty, im->TW, im->TH, im->d_dirty);
+        mark_dirty();   // the tiles the changed sources' OLD boxes touch (before k_prep rewrites the boxes) ...
     }
     if (flags & CEL_RENDER_LOGLIK) im->partials_gen = 0;
     im->lists_gen = 0;
     if (!lambda_out && !(flags & CEL_RENDER_NO_STORE)) im->lambda_gen = 0;
     rc = run_prep(im, src);
     if (rc) return rc;
-    if (incr)       // ... and the tiles their new boxes touch
-        hipLaunchKernelGGL(k_mark_dirty, dim3((unsigned)((delta.n * im->B + 255) / 256)), dim3(256), 0, st, delta, (const int4 *)im->d_boxes, S, im->B,
-                           im->ntx, im->nty, im->TW, im->TH, im->d_dirty);
+    if (incr) mark_dirty();     // ... and the tiles their new boxes touch
     im->last_dirty = -1;
-    int parts_used = 1;
     if (im->d_lists.cap == 0) {
         // first guess: every (band, source) touches ~6 tiles; grown on overflow below
         const int64_t n = (S * im->B) * 6 + 1024;
@@ -1188,9 +1300,8 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         HIP_TRY(im->d_clist.grow(n, n, st));
     }
     const int NS = im->B * im->nsx * im->nsy;
-    const int tile_order = tile_order_of(c, im);
-    // a small catalogue is binned by one wave per tile into per-tile segments of S entries (k_bin_direct)
-    const bool bin_direct = S > 0 && S <= BIN_DIRECT_MAX_S && (int64_t)T * S <= ((int64_t)1 << 25);
+    const int tile_order = plan.tile_order, parts = plan.parts;
+    const bool bin_direct = plan.bin_direct, diag = plan.diag;
     if (bin_direct) HIP_TRY(im->d_lists.grow((int64_t)T * S, (int64_t)T * S, st));
     for (int attempt = 0; attempt < 8; attempt++) {
         // d_cursor: [0] fine cursor, [1] fine overflow, [2] coarse cursor, [3] coarse overflow;
@@ -1210,31 +1321,9 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         } else if (im->bin_two_level) {
             LAUNCH_EV(k_bin_coarse, dim3(NS), dim3(64 * COARSE_WAVES), st, EV0(c, pi), (hipEvent_t) nullptr, im->d_boxes, S, im->nsx, im->nsy,
                       im->d_sup_cnt, im->d_sup_off, im->d_cursor + 2, im->d_clist, im->d_clist.cap, (int *)(im->d_cursor + 3));
-            // (16-wave blocks while every super-tile gets a CU of its own, 8-wave blocks -- two to a CU -- beyond that: k_bin2.h)
-            if (NS > c->n_cu)
-                LAUNCH_EV((k_bin_fine_blk<false, 8>), dim3(NS), dim3(64 * 8), st, (hipEvent_t) nullptr, bin_ev1,
-                          im->d_boxes, im->d_kind, S, im->ntx, im->nty, im->TH, im->TW,
-                          im->nsx, im->nsy, im->d_sup_cnt, im->d_sup_off, im->d_clist, im->d_clist.cap, im->d_tile_cnt,
-                          im->d_tile_nstar, im->d_tile_work, im->d_tile_off, im->d_cursor, im->d_lists, im->d_lists.cap,
-                          (int *)(im->d_cursor + 1), (int *)(im->d_cursor + 3));
-            else
-                LAUNCH_EV((k_bin_fine_blk<false, 16>), dim3(NS), dim3(64 * 16), st, (hipEvent_t) nullptr, bin_ev1,
-                          im->d_boxes, im->d_kind, S, im->ntx, im->nty, im->TH, im->TW,
-                          im->nsx, im->nsy, im->d_sup_cnt, im->d_sup_off, im->d_clist, im->d_clist.cap, im->d_tile_cnt,
-                          im->d_tile_nstar, im->d_tile_work, im->d_tile_off, im->d_cursor, im->d_lists, im->d_lists.cap,
-                          (int *)(im->d_cursor + 1), (int *)(im->d_cursor + 3));
-        } else if (NS > c->n_cu) {
-            LAUNCH_EV((k_bin_fine_blk<true, 8>), dim3(NS), dim3(64 * 8), st, EV0(c, pi), bin_ev1,
-                      im->d_boxes, im->d_kind, S, im->ntx, im->nty, im->TH, im->TW,
-                      im->nsx, im->nsy, im->d_sup_cnt, im->d_sup_off, im->d_clist, im->d_clist.cap, im->d_tile_cnt,
-                      im->d_tile_nstar, im->d_tile_work, im->d_tile_off, im->d_cursor, im->d_lists, im->d_lists.cap,
-                      (int *)(im->d_cursor + 1), (int *)(im->d_cursor + 3));
+            launch_bin_fine(c, im, S, NS, false, (hipEvent_t) nullptr, bin_ev1);
         } else {
-            LAUNCH_EV((k_bin_fine_blk<true, 16>), dim3(NS), dim3(64 * 16), st, EV0(c, pi), bin_ev1,
-                      im->d_boxes, im->d_kind, S, im->ntx, im->nty, im->TH, im->TW,
-                      im->nsx, im->nsy, im->d_sup_cnt, im->d_sup_off, im->d_clist, im->d_clist.cap, im->d_tile_cnt,
-                      im->d_tile_nstar, im->d_tile_work, im->d_tile_off, im->d_cursor, im->d_lists, im->d_lists.cap,
-                      (int *)(im->d_cursor + 1), (int *)(im->d_cursor + 3));
+            launch_bin_fine(c, im, S, NS, true, EV0(c, pi), bin_ev1);
         }
         if (tile_order && !order_ready)
             // heaviest first: by the durations the tiles had in the previous render when that was
@@ -1255,12 +1344,6 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
             HIP_TRY(im->d_timing.grow(3 * T, 3 * T, st));
             a.timing = im->d_timing;
         }
-        // a catalogue without galaxies: the star-tile kernel (k_render_stars.h), when the frame has more tiles than the
-        // general kernel has wave slots (STAR_TILES_MIN; measured break-even, tools/star_tiles_threshold.py); the
-        // instantiation with counters / time stamps / ablations exists for the general kernel only
-        const bool diag = a.timing || (c->debug & ~64);
-        const int parts = diag ? 1 : tile_parts_of(c, im);
-        parts_used = (im->TW == HW_TW && !diag) ? parts : 1;
         a.slabs = nullptr; a.part_cnt = nullptr;
         if (parts > 1) {
             const int64_t slabs = (int64_t)HW_TH * HW_TW * T * parts;
@@ -1271,36 +1354,16 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
             }
             a.slabs = im->d_slabs; a.part_cnt = im->d_part_cnt;
         }
-        const bool stars_only = im->TW == HW_TW && !diag && c->star_tiles && src->n_gal == 0 && im->star_one_segment &&
-                                c->variant != 0 && (c->star_tiles == 2 || T > STAR_TILES_MIN);    // (1 and 3: the rule; 3 = without the one-launch small path)
-        if (stars_only) parts_used = 0;         // (the star-tile kernel adds a pixel's stars in another order: not the general kernel's bits)
-        pi = prof_slot(c, stars_only ? CEL_K_RENDER_STARS : CEL_K_RENDER);
-        if (im->TW == QW_TW)
-            LAUNCH_EV(k_render_qw, dim3(T), dim3(64), st, EV0(c, pi), EV1(c, pi), a);
-        else if (im->TW == HW_TW) {
-            // the production instantiation has no diagnostic code in it; counters, time stamps and (CEL_ABLATE
-            // builds) ablations live in the second one
-            if (diag) LAUNCH_EV(k_render_hw<true>, dim3(T), dim3(64), st, EV0(c, pi), EV1(c, pi), a);
-            else if (stars_only) LAUNCH_EV((k_render_stars<2, false>), dim3(T), dim3(64), st, EV0(c, pi), EV1(c, pi), a);
-            else if (parts > 1) {
-                const unsigned grid = (unsigned)(((T + 7) / 8) * 8 * parts);
-                if (parts == 4) LAUNCH_EV((k_render_hw<false, 4>), dim3(grid), dim3(64), st, EV0(c, pi), EV1(c, pi), a);
-                else LAUNCH_EV((k_render_hw<false, 2>), dim3(grid), dim3(64), st, EV0(c, pi), EV1(c, pi), a);
-            }
-            else LAUNCH_EV(k_render_hw<false>, dim3(T), dim3(64), st, EV0(c, pi), EV1(c, pi), a);
-        }
-        else if (im->TH == 64)
-            LAUNCH_EV((k_render<64>), dim3(T), dim3(64), st, EV0(c, pi), EV1(c, pi), a);
-        else
-            LAUNCH_EV((k_render<32>), dim3(T), dim3(64), st, EV0(c, pi), EV1(c, pi), a);
+        pi = prof_slot(c, plan.stars_only ? CEL_K_RENDER_STARS : CEL_K_RENDER);
+        launch_render(c, im, plan, T, a, EV0(c, pi), EV1(c, pi));
         if (flags & CEL_RENDER_LOGLIK) {
             pi = prof_slot(c, CEL_K_REDUCE);
             LAUNCH_EV(k_reduce, dim3(im->B), dim3(256), st, EV0(c, pi), EV1(c, pi), (const double *)im->d_partials, im->ntx * im->nty, im->d_llband,
-                      im->ntx, own_ty0, own_ty1);
+                      im->ntx, plan.own_ty0, plan.own_ty1);
             im->llband_on_host = false;
         }
         // the per-band sums, the total list length and the overflow flags ride back in ONE copy
-        HIP_TRY(hipMemcpyAsync(c->pinned, im->d_llband, sizeof(double) * MAX_BANDS + sizeof(unsigned long long) * 4,
+        HIP_TRY(hipMemcpyAsync(c->mail.get(), im->d_llband, offsetof(Mailbox, sh) + sizeof(MailShared::bin_coarse),
                                hipMemcpyDeviceToHost, st));
         HIP_TRY(hipGetLastError());
         im->last_S = S;
@@ -1316,12 +1379,11 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         } else {
             HIP_TRY(hipStreamSynchronize(st));
         }
-        unsigned long long cur[4];
-        memcpy(cur, c->pinned + MAX_BANDS, sizeof(cur));
-        const bool fine_ok = (cur[1] & 0xffffffffull) == 0 && (int64_t)cur[0] <= im->d_lists.cap;
-        const bool too_dense = (cur[3] & 2ull) != 0;        // a super-tile with more candidates than the one-kernel form stages
-        const bool coarse_ok = (cur[3] & 0xffffffffull) == 0 && (int64_t)cur[2] <= im->d_clist.cap;
-        if (coarse_ok) im->last_entries = (double)cur[0];
+        const unsigned long long *fine = c->mail->bin_fine, *coarse = c->mail->sh.bin_coarse;      // cursor, overflow
+        const bool fine_ok = (fine[1] & 0xffffffffull) == 0 && (int64_t)fine[0] <= im->d_lists.cap;
+        const bool too_dense = (coarse[1] & 2ull) != 0;        // a super-tile with more candidates than the one-kernel form stages
+        const bool coarse_ok = (coarse[1] & 0xffffffffull) == 0 && (int64_t)coarse[0] <= im->d_clist.cap;
+        if (coarse_ok) im->last_entries = (double)fine[0];
         if (fine_ok && coarse_ok) {
             im->cost_S = a.cost ? S : -1; im->order_S = post_order ? S : -1;
             im->lists_gen = src->gen;
@@ -1331,7 +1393,7 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
                 im->lambda_T = c->render_T;
                 // a render by the DIAG instantiation (tile timing, ablation bits) vouches for nothing: with an ablation bit set its
                 // pixels and partials are documented as wrong, and the incremental path would take them as a base
-                im->lambda_parts = diag ? 0 : parts_used;
+                im->lambda_parts = diag ? 0 : plan.parts_used;
                 // (a render WITHOUT the log-likelihood vouches for no partials: those in the buffer may be of another sky
                 // level or drop threshold although the catalogue's generation is the same -- found by tools/dbg/incremental_stress.py)
                 im->partials_gen = (flags & CEL_RENDER_LOGLIK) ? src->gen : 0;
@@ -1343,19 +1405,12 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         im->order_S = -1;
         // rerun with room (a truncated coarse list also truncates the fine counts)
         if (too_dense) { im->bin_two_level = true; continue; }
-        const int64_t nc = (int64_t)cur[2] + (int64_t)cur[2] / 4 + 1024, nf = (int64_t)cur[0] + (int64_t)cur[0] / 4 + 1024;
+        const int64_t nc = (int64_t)coarse[0] + (int64_t)coarse[0] / 4 + 1024, nf = (int64_t)fine[0] + (int64_t)fine[0] / 4 + 1024;
         if (!coarse_ok) HIP_TRY(im->d_clist.grow(nc, nc, st));
         if (!fine_ok) HIP_TRY(im->d_lists.grow(nf, nf, st));
         if (attempt == 7) return fail(CEL_ERR_HIP, "tile lists kept overflowing");
     }
-    if (flags & CEL_RENDER_LOGLIK) {
-        double tot = 0.0;
-        for (int b = 0; b < im->B; b++) {
-            if (ll_band) ll_band[b] = c->pinned[b];
-            tot += c->pinned[b];
-        }
-        if (ll_total) *ll_total = tot;
-    }
+    if (flags & CEL_RENDER_LOGLIK) ll_from_mailbox(c, im->B, ll_band, ll_total);
     return CEL_OK;
 }
 
@@ -1399,10 +1454,10 @@ int cel_field_stats(cel_images *im, double *n_srcpix, double *n_gauss, double *n
     HIP_TRY(hipMemsetAsync(im->d_stats, 0, sizeof(double) * 2, c->stream));
     if (n > 0)
         hipLaunchKernelGGL(k_stats, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, im->d_recs, n, im->d_stats);
-    HIP_TRY(hipMemcpyAsync(c->pinned + MAX_BANDS + 6, im->d_stats, sizeof(double) * 2, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->mail->sh.w.field_stats, im->d_stats, sizeof(double) * 2, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (n_srcpix) *n_srcpix = c->pinned[MAX_BANDS + 6];
-    if (n_gauss) *n_gauss = c->pinned[MAX_BANDS + 7];
+    if (n_srcpix) *n_srcpix = c->mail->sh.w.field_stats[0];
+    if (n_gauss) *n_gauss = c->mail->sh.w.field_stats[1];
     if (n_tile_entries) *n_tile_entries = im->last_entries;
     return CEL_OK;
 }
@@ -1482,26 +1537,18 @@ int cel_render_stamps(cel_images *im, cel_sources *src, int band, int scaled, co
     int4 *d_obox = nullptr;
     int64_t *d_off = nullptr;
     double *d_out = nullptr;
-    rc = CEL_OK;
-    hipError_t e;
-#define ST_TRY(expr)                                                                     \
-    do {                                                                                 \
-        e = (expr);                                                                      \
-        if (e != hipSuccess) { rc = fail(CEL_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e)); goto done; } \
-    } while (0)
-    if ((rc = scratch_get(c, 4, sizeof(StampJob) * jobs.size(), (void **)&d_jobs)) ||
-        (rc = scratch_get(c, 5, sizeof(int4) * S, (void **)&d_obox)) ||
-        (rc = scratch_get(c, 6, sizeof(int64_t) * (S + 1), (void **)&d_off)))
+    if ((rc = scratch_get(c, SCR_TMP_A, sizeof(StampJob) * jobs.size(), (void **)&d_jobs)) ||
+        (rc = scratch_get(c, SCR_TMP_B, sizeof(int4) * S, (void **)&d_obox)) ||
+        (rc = scratch_get(c, SCR_TMP_C, sizeof(int64_t) * (S + 1), (void **)&d_off)))
         return rc;
     if (mem == CEL_DEVICE) d_out = out;
-    else if ((rc = scratch_get(c, 7, sizeof(double) * (total > 0 ? total : 1), (void **)&d_out))) return rc;
+    else if ((rc = scratch_get(c, SCR_HOST_IO, sizeof(double) * (total > 0 ? total : 1), (void **)&d_out))) return rc;
     for (int64_t s : skipped)
-        ST_TRY(hipMemsetAsync(d_out + offsets[s], 0, sizeof(double) * (size_t)(offsets[s + 1] - offsets[s]), c->stream));
-    if (jobs.empty()) goto sync;
-    ST_TRY(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(StampJob) * jobs.size(), hipMemcpyHostToDevice, c->stream));
-    ST_TRY(hipMemcpyAsync(d_obox, obox.data(), sizeof(int4) * S, hipMemcpyHostToDevice, c->stream));
-    ST_TRY(hipMemcpyAsync(d_off, offsets, sizeof(int64_t) * (S + 1), hipMemcpyHostToDevice, c->stream));
-    {
+        HIP_TRY(hipMemsetAsync(d_out + offsets[s], 0, sizeof(double) * (size_t)(offsets[s + 1] - offsets[s]), c->stream));
+    if (!jobs.empty()) {
+        HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(StampJob) * jobs.size(), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_obox, obox.data(), sizeof(int4) * S, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_off, offsets, sizeof(int64_t) * (S + 1), hipMemcpyHostToDevice, c->stream));
         int pi = prof_begin(c, CEL_K_STAMPS);
         if (c->variant == 0)
             hipLaunchKernelGGL(k_stamps, dim3((unsigned)jobs.size()), dim3(64), 0, c->stream, im->d_bands, band,
@@ -1510,15 +1557,11 @@ int cel_render_stamps(cel_images *im, cel_sources *src, int band, int scaled, co
             hipLaunchKernelGGL(k_stamps_hw, dim3((unsigned)jobs.size()), dim3(64), 0, c->stream, im->d_bands, band,
                                im->d_recs + (int64_t)band * S, d_jobs, d_obox, d_off, scaled, c->tail_T, d_out);
         prof_end(c, pi);
+        HIP_TRY(hipGetLastError());
+        if (mem != CEL_DEVICE) HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * total, hipMemcpyDeviceToHost, c->stream));
     }
-    ST_TRY(hipGetLastError());
-    if (mem != CEL_DEVICE) ST_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * total, hipMemcpyDeviceToHost, c->stream));
-sync:
-    ST_TRY(hipStreamSynchronize(c->stream));
-#undef ST_TRY
-done:
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));      // (jobs, obox and the caller's arrays were the sources of asynchronous copies)
+    return CEL_OK;
 }
 
 // ---- per-source conditional log-likelihoods ---------------------------------------------------
@@ -1575,38 +1618,38 @@ int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owne
     const int nsplit = (c->variant != 0 && mode == 0 && P * B <= 8192) ? PLL_PARTS : 1;
     const int nparts = nzl ? PLL_PARTS : nsplit;
     std::vector<double> hout((size_t)(P * B * nparts));
-    hipError_t e;
-#define PL_TRY(expr)                                                                     \
-    do {                                                                                 \
-        e = (expr);                                                                      \
-        if (e != hipSuccess) { rc = fail(CEL_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e)); goto done; } \
-    } while (0)
     int4 *d_nz = nullptr;
-    if ((rc = scratch_get(c, 0, sizeof(int4) * (resident ? 0 : 2 * nb) + sizeof(int) * (owner ? P : 0), (void **)&d_box)) ||
-        (rc = scratch_get(c, 1, sizeof(int64_t) * (nb + 1), (void **)&d_off)) ||
-        (rc = scratch_get(c, 2, sizeof(double) * P * B * nparts, (void **)&d_out)))
-        goto done;
-    if (owner) {
-        d_owner = reinterpret_cast<int *>(d_box + (resident ? 0 : 2 * nb));
-        PL_TRY(hipMemcpyAsync(d_owner, owner, sizeof(int) * P, hipMemcpyHostToDevice, c->stream));
-    }
-    if (!resident) d_nz = d_box + nb;
+    // one block: a caller's boxes, their photon rectangles, the owners
+    auto carve = [&](char *base) {
+        Carver k{base};
+        d_box = k.take<int4>(resident ? 0 : nb);
+        d_nz = k.take<int4>(resident ? 0 : nb);
+        d_owner = owner ? k.take<int>(P) : nullptr;
+        return k.off;
+    };
+    char *d_blk = nullptr;
+    if ((rc = scratch_get(c, SCR_PLL_BOXES, carve(nullptr), (void **)&d_blk)) ||
+        (rc = scratch_get(c, SCR_OFFSETS, sizeof(int64_t) * (nb + 1), (void **)&d_off)) ||
+        (rc = scratch_get(c, SCR_VALUES, sizeof(double) * P * B * nparts, (void **)&d_out)))
+        return rc;
+    carve(d_blk);
+    if (owner) HIP_TRY(hipMemcpyAsync(d_owner, owner, sizeof(int) * P, hipMemcpyHostToDevice, c->stream));
     if (resident) {
         d_nz = im->d_snz;
         d_box = im->d_sbox;
         d_off = im->d_soff;
         d_data = nullptr;                                 // mode 0: the int32 patches (below); mode 1 reads nelec on the boxes
     } else {
-        PL_TRY(hipMemcpyAsync(d_box, hbox.data(), sizeof(int4) * nb, hipMemcpyHostToDevice, c->stream));
-        PL_TRY(hipMemcpyAsync(d_off, offsets, sizeof(int64_t) * (nb + 1), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_box, hbox.data(), sizeof(int4) * nb, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_off, offsets, sizeof(int64_t) * (nb + 1), hipMemcpyHostToDevice, c->stream));
     }
     if (resident) {
     } else if (mem == CEL_DEVICE) {
         d_data = const_cast<double *>(data);
     } else {
-        if ((rc = scratch_get(c, 3, sizeof(double) * (offsets[nb] > 0 ? offsets[nb] : 1), (void **)&d_data))) goto done;   // copies are queued: leave through the sync
+        if ((rc = scratch_get(c, SCR_PATCH_DATA, sizeof(double) * (offsets[nb] > 0 ? offsets[nb] : 1), (void **)&d_data))) return rc;   // (copies are queued: scratch_get fails through HIP_TRY, which drains the device)
         if (offsets[nb] > 0)
-            PL_TRY(hipMemcpyAsync(d_data, data, sizeof(double) * offsets[nb], hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(d_data, data, sizeof(double) * offsets[nb], hipMemcpyHostToDevice, c->stream));
     }
     {
         int pi = prof_begin(c, CEL_K_PATCH_LL);
@@ -1650,9 +1693,9 @@ int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owne
                                (const int *)nullptr, 1, (const int *)nullptr);
         prof_end(c, pi);
     }
-    PL_TRY(hipGetLastError());
-    PL_TRY(hipMemcpyAsync(hout.data(), d_out, sizeof(double) * P * B * nparts, hipMemcpyDeviceToHost, c->stream));
-    PL_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hout.data(), d_out, sizeof(double) * P * B * nparts, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     for (int64_t p = 0; p < P; p++) {
         double s = 0.0;
         for (int b = 0; b < B; b++) {                       // band order, like the reference's image loop
@@ -1663,10 +1706,7 @@ int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owne
         }
         ll_out[p] = s;
     }
-#undef PL_TRY
-done:
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return CEL_OK;
 }
 
 int cel_patch_loglik(cel_images *im, cel_sources *src, const int32_t *boxes, const int64_t *offsets,
@@ -1700,7 +1740,7 @@ int cel_stamp_mass_begin(cel_images *im, cel_sources *src) {
     if (!from_split || im->recs_gen != src->gen) rc = run_prep(im, src);
     if (rc) return rc;
     double *d_out = nullptr;
-    if ((rc = scratch_get(c, 2, sizeof(double) * S * B, (void **)&d_out))) return rc;
+    if ((rc = scratch_get(c, SCR_VALUES, sizeof(double) * S * B, (void **)&d_out))) return rc;
     int pi = prof_begin(c, CEL_K_MASS);
     if (from_split) {
         // the photon split that has just run on this catalogue (with k_strict_totals before it) summed every unit stamp it
@@ -1712,7 +1752,7 @@ int cel_stamp_mass_begin(cel_images *im, cel_sources *src) {
                            im->d_mass_todo, d_ntodo);
         // (how many: read in cel_stamp_mass_end, which launches the mass kernel on exactly those -- none at all in a field
         // without very faint sources; a launch of S B blocks that find nothing to do cost 0.15 ms of the flux step)
-        HIP_TRY(hipMemcpyAsync(c->pinned + MAX_BANDS + 14, d_ntodo, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(&c->mail->mass_todo, d_ntodo, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         im->mass_todo_S = S;
         im->mass_gen = src->gen; im->mass_todo_ptr = im->d_mass_todo;
     } else {
@@ -1741,8 +1781,7 @@ static int mass_finish(cel_images *im, int64_t *n_out) {
     if (n == 0) return CEL_OK;
     if (S_todo >= 0) {                  // the short cut's leftovers (cel_stamp_mass_begin)
         HIP_TRY(hipStreamSynchronize(c->stream));
-        int ntodo = 0;
-        memcpy(&ntodo, c->pinned + MAX_BANDS + 14, sizeof(int));
+        const int ntodo = c->mail->mass_todo;
         if (ntodo > 0) {
             // Calls that came between _begin and _end (the header lists what may: cel_gamma_streams, cel_samples_fetch,
             // cel_images_set_epsilon) leave the records and the to-do list alone.  Anything that re-ran k_prep for another
@@ -1792,17 +1831,26 @@ int cel_flux_conditionals(cel_images *im, cel_sources *src, uint64_t seed, doubl
     if ((rc = mass_finish(im, &n))) return rc;
     // the per-image constants ride in one small upload: letter[B] | ratio[B] | calib[B] | kappa[B], then the outputs
     char *d = nullptr;
-    const size_t cbytes = (size_t)MAX_BANDS * (sizeof(int) + 3 * sizeof(double));
-    if ((rc = scratch_get(c, 6, cbytes + sizeof(double) * 5 * S + sizeof(int) * S + 64, (void **)&d))) return rc;
+    const int *d_letter = nullptr;
+    const double *d_ratio = nullptr;
+    double *d_flux = nullptr;
+    int *d_act = nullptr;
+    auto carve = [&](char *base) {
+        Carver k{base};
+        d_letter = k.take<int>(MAX_BANDS);
+        d_ratio = k.take<double>(3 * MAX_BANDS);        // ratio, calib, kappa
+        d_flux = k.take<double>(5 * S);
+        d_act = k.take<int>(S);
+        return k.off;
+    };
+    if ((rc = scratch_get(c, SCR_TMP_C, carve(nullptr), (void **)&d))) return rc;
+    carve(d);
     struct { int letter[MAX_BANDS]; double ratio[MAX_BANDS], calib[MAX_BANDS], kappa[MAX_BANDS]; } hc;
     memset(&hc, 0, sizeof(hc));
     for (int b = 0; b < B; b++) { hc.letter[b] = band_letter[b]; hc.ratio[b] = kappa[b] / calib[b]; hc.calib[b] = calib[b]; hc.kappa[b] = kappa[b]; }
     static_assert(sizeof(hc) == MAX_BANDS * (sizeof(int) + 3 * sizeof(double)), "packed");
     HIP_TRY(hipMemcpyAsync(d, &hc, sizeof(hc), hipMemcpyHostToDevice, c->stream));      // (pageable: staged before the call returns)
-    const int *d_letter = reinterpret_cast<const int *>(d);
-    const double *d_ratio = reinterpret_cast<const double *>(d + sizeof(int) * MAX_BANDS);
-    double *d_flux = reinterpret_cast<double *>(d + cbytes);
-    int *d_act = reinterpret_cast<int *>(d + cbytes + sizeof(double) * 5 * S);
+    static_assert(offsetof(decltype(hc), ratio) == sizeof(int) * MAX_BANDS, "the upload is laid out as the block is carved");
     if (S > 0) {
         hipLaunchKernelGGL(k_flux_step, dim3((unsigned)((S * 5 + 255) / 256)), dim3(256), 0, c->stream, S, B, (const double *)im->d_ssum,
                            (const double *)im->d_mass, (const int64_t *)im->d_soff, d_letter, d_ratio, d_ratio + MAX_BANDS, d_ratio + 2 * MAX_BANDS,
@@ -1827,7 +1875,7 @@ int cel_gamma_streams(cel_ctx *c, int64_t n, const double *a, uint64_t seed, dou
         if (!(a[i] > 0.0) || !(a[i] < 1e300)) return fail(CEL_ERR_INVALID, "cel_gamma_streams: shape parameter %lld is not positive and finite", (long long)i);
     HIP_TRY(hipSetDevice(c->device));
     double *d = nullptr;
-    int rc = scratch_get(c, 6, sizeof(double) * 2 * n, (void **)&d);
+    int rc = scratch_get(c, SCR_TMP_C, sizeof(double) * 2 * n, (void **)&d);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(d, a, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_gamma_streams, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, (const double *)d,
@@ -1843,6 +1891,32 @@ int cel_stamp_mass(cel_images *im, cel_sources *src, double *mass) {
 }
 
 // ---- lock-step slice sampling of the locations, on the device -----------------------------------
+// The samplers' conditional log-likelihoods of P proposals against the resident split's patches: the blocks of `dense` score
+// their jobs densely (k_patch_ll_hw<0>), those of `nz` at their photons (k_patch_ll_nz; `fuse`: the block that finishes a
+// chain's last job steps the chain).  A list names the blocks of a round; `count` is its length where only the device knows
+// it (the launch is sized by an upper bound and the kernels stop there).  Every job fills its PLL_PARTS slots of d_ll.
+struct LlBlocks { int64_t n; const int *list, *count; };
+static void launch_resident_ll(cel_ctx *c, cel_images *im, int64_t P, const int *d_owner, double *d_ll, bool use_nz,
+                               LlBlocks dense, LlBlocks nz, const SliceFuse *fuse) {
+    const int B = im->B;
+    hipStream_t st = c->stream;
+    if (dense.n > 0) {
+        int pi = prof_slot(c, CEL_K_PATCH_LL);
+        LAUNCH_EV((k_patch_ll_hw<0, int>), dim3((unsigned)dense.n), dim3(64), st, EV0(c, pi), EV1(c, pi), im->d_bands, B, P, im->d_recs,
+                  d_owner, im->d_sbox, im->d_soff, (const int *)im->d_samp, im->d_nelec, im->H, im->W, im->d_snz, c->tail_T, d_ll,
+                  dense.list, 1, dense.count, (const int *)(use_nz ? im->d_nzmode : nullptr), 1, PLL_PARTS);
+    }
+    if (nz.n > 0) {
+        int pi = prof_slot(c, CEL_K_PATCH_LL);
+        auto go = [&](auto kernel) {
+            LAUNCH_EV(kernel, dim3((unsigned)nz.n), dim3(64), st, EV0(c, pi), EV1(c, pi), im->d_bands, B, P, im->d_recs,
+                      d_owner, (const int4 *)im->d_sbox, (const int4 *)im->d_snz, (const int *)im->d_nzmode,
+                      (const int64_t *)im->d_nzoff, (const NzEntry *)im->d_nzlist, d_ll, nz.list, nz.count, fuse);
+        };
+        if (fuse) go(k_patch_ll_nz<true>); else go(k_patch_ll_nz<false>);
+    }
+}
+
 int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_ids, double sigma, uint64_t seed,
                         int max_rounds, double *radec_out, double *llh_out, int64_t *stats) {
     if (!im || !src) return fail(CEL_ERR_INVALID, "cel_slice_locations: null argument");
@@ -1856,13 +1930,57 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
     hipStream_t st = c->stream;
     const int B = im->B;
     const int64_t S = src->S;
-    // one allocation, carved: 2 x u64, 10 x f64 (x and x0 are 2 per chain), 4 x i32 per chain + owner + ll (S*B) + chain ids + 2 ints
     // blocks per (chain, band) job in rounds with at most SLICE_SPLIT_JOBS jobs left (measured at config 3: 4 blocks
     // below 2048 jobs 29.4 ms per location step, below 8192 jobs 29.0; 8 blocks 29.4; without 30.3)
     const int SLICE_SPLIT = PLL_PARTS, SLICE_SPLIT_JOBS = 8192;
-    const size_t per_chain = 2 * 8 + 10 * 8 + 4 * 4 + 4 + (size_t)B * 8 * SLICE_SPLIT + 4 + (size_t)B * 4 * 6 * SLICE_SPLIT + 3 * 4;
-    const size_t need = per_chain * (size_t)S + 128 + 2 * sizeof(SliceFuse) + 16;
+    // one allocation, carved (Carver: once for the size, once for the pointers)
+    SliceState ss;
+    double *d_ll;
+    int *d_owner, *d_ids, *d_work, *d_jobs, *d_live, *d_work_nz, *d_jobs_nz, *d_live_nz, *d_tick, *d_need_full, *d_need_live, *d_flags;
+    SliceFuse *d_fz;
+    auto carve = [&](char *base) {
+        Carver k{base};
+        const size_t n = (size_t)S, nj = (size_t)S * B * SLICE_SPLIT;
+        ss.key = k.take<unsigned long long>(n);
+        ss.count = k.take<unsigned long long>(n);
+        ss.x = k.take<double>(2 * n);
+        ss.x0 = k.take<double>(2 * n);
+        ss.lower = k.take<double>(n);
+        ss.upper = k.take<double>(n);
+        ss.log_u = k.take<double>(n);
+        ss.llh_s = k.take<double>(n);
+        ss.new_z = k.take<double>(n);
+        ss.new_llh = k.take<double>(n);
+        d_ll = k.take<double>(nj);
+        ss.phase = k.take<int>(n);
+        ss.kdir = k.take<int>(n);
+        ss.first = k.take<int>(n);
+        ss.steps = k.take<int>(n);
+        d_owner = k.take<int>(n);
+        d_ids = k.take<int>(n);
+        // per (job, part) block entries (k_job_work): work estimates, the heaviest-first block lists of a full round, and the
+        // running chains' blocks of the late rounds -- for the jobs scored densely and for those scored at their photons
+        d_work = k.take<int>(nj);
+        d_jobs = k.take<int>(nj);
+        d_live = k.take<int>(nj);
+        d_work_nz = k.take<int>(nj);
+        d_jobs_nz = k.take<int>(nj);
+        d_live_nz = k.take<int>(nj);
+        // the fused rounds (SliceFuse, k_slice_state.h): per chain its ticket counter and the blocks the full / the live lists hold for it
+        d_tick = k.take<int>(n);
+        d_need_full = k.take<int>(n);
+        d_need_live = k.take<int>(n);
+        d_flags = k.take<int>(13);      // [0] chains still running, [1] error bits, [2] likelihood evaluations so far, [3] rounds with work,
+                                        // [4] / [5] live dense / photon-list jobs of the batch, [6..7] byte counter, [8] / [9] dense / photon-list jobs;
+                                        // a call that may fuse rounds: [6] chains still running (k_slice_live_jobs, per batch: a fused round keeps no
+                                        // count), [11] / [12] evaluations / rounds with work (k_slice_bytes, at the end)
+        // the fused rounds' arguments, in device memory: [0] for the full lists, [1] for the live lists (they differ in `need`)
+        d_fz = k.take<SliceFuse>(2, 16);
+        return k.off;
+    };
+    const size_t need = carve(nullptr);
     HIP_TRY(im->d_slice.grow(need, need + need / 4, st));
+    carve(im->d_slice);
     if (!im->slice_prop || im->slice_prop->cap < S) {
         im->slice_prop.reset();
         cel_sources *np = nullptr;
@@ -1871,41 +1989,6 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
         im->slice_prop.reset(np);
     }
     cel_sources *prop = im->slice_prop.get();
-    char *p = (char *)im->d_slice;
-    SliceState ss;
-    ss.key = (unsigned long long *)p; p += 8 * S;
-    ss.count = (unsigned long long *)p; p += 8 * S;
-    ss.x = (double *)p; p += 16 * S;
-    ss.x0 = (double *)p; p += 16 * S;
-    ss.lower = (double *)p; p += 8 * S;
-    ss.upper = (double *)p; p += 8 * S;
-    ss.log_u = (double *)p; p += 8 * S;
-    ss.llh_s = (double *)p; p += 8 * S;
-    ss.new_z = (double *)p; p += 8 * S;
-    ss.new_llh = (double *)p; p += 8 * S;
-    double *d_ll = (double *)p; p += 8 * S * B * SLICE_SPLIT;
-    ss.phase = (int *)p; p += 4 * S;
-    ss.kdir = (int *)p; p += 4 * S;
-    ss.first = (int *)p; p += 4 * S;
-    ss.steps = (int *)p; p += 4 * S;
-    int *d_owner = (int *)p; p += 4 * S;
-    int *d_ids = (int *)p; p += 4 * S;
-    // per (job, part) block entries (k_job_work): work estimates, the heaviest-first block lists of a full round, and the
-    // running chains' blocks of the late rounds -- for the jobs scored densely and for those scored at their photons
-    int *d_work = (int *)p; p += 4 * S * B * SLICE_SPLIT;
-    int *d_jobs = (int *)p; p += 4 * S * B * SLICE_SPLIT;
-    int *d_live = (int *)p; p += 4 * S * B * SLICE_SPLIT;
-    int *d_work_nz = (int *)p; p += 4 * S * B * SLICE_SPLIT;
-    int *d_jobs_nz = (int *)p; p += 4 * S * B * SLICE_SPLIT;
-    int *d_live_nz = (int *)p; p += 4 * S * B * SLICE_SPLIT;
-    // the fused rounds (SliceFuse, k_slice_state.h): per chain its ticket counter and the blocks the full / the live lists hold for it
-    int *d_tick = (int *)p; p += 4 * S;
-    int *d_need_full = (int *)p; p += 4 * S;
-    int *d_need_live = (int *)p; p += 4 * S;
-    int *d_flags = (int *)p;            // [0] chains still running, [1] error bits, [2] likelihood evaluations so far, [3] rounds with work,
-                                        // [4] / [5] live dense / photon-list jobs of the batch, [6..7] byte counter, [8] / [9] dense / photon-list jobs;
-                                        // a call that may fuse rounds: [6] chains still running (k_slice_live_jobs, per batch: a fused round keeps no
-                                        // count), [11] / [12] evaluations / rounds with work (k_slice_bytes, at the end)
     // the proposal set: this catalogue with the locations rewritten every round
     HIP_TRY(hipMemcpyAsync(prop->d_type, src->d_type, sizeof(int) * S, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(prop->d_counts, src->d_counts, sizeof(double) * B * S, hipMemcpyDeviceToDevice, st));
@@ -1940,7 +2023,7 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
             hipLaunchKernelGGL(k_list_members, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, st, d_work_nz, nent, d_live, d_live_nz, d_flags + 9);
             hipLaunchKernelGGL(k_order_compact, dim3(1), dim3(1024), 0, st, (const int *)d_live, (const int *)d_live_nz, (const int *)(d_flags + 9), d_jobs_nz);
         }
-        int *h_cnt = reinterpret_cast<int *>(c->pinned + MAX_BANDS + 2);
+        int *h_cnt = c->mail->sh.slice_flags;
         h_cnt[1] = 0;
         HIP_TRY(hipMemcpyAsync(h_cnt, d_flags + 8, sizeof(int) * (use_nz ? 2 : 1), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -1978,15 +2061,13 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
     // those of the batch before the one whose lists the launch walks; chains only retire, so those are upper bounds (times
     // PLL_PARTS where the lists in between began to deal every job), and the kernels stop at the device's own count.
     int64_t live_dense = -1, live_nz = -1;                       // < 0: no live lists read yet
-    int *h_flag_slot[2] = {reinterpret_cast<int *>(c->pinned + MAX_BANDS + 2), reinterpret_cast<int *>(c->pinned + MAX_BANDS + 8)};
+    int *h_flag_slot[2] = {c->mail->sh.slice_flags, c->mail->slice_flags1};
     PrepArgs pa;                                                 // what run_prep(im, prop, d_owner, 1) hands k_prep
     pa.bands = im->d_bands; pa.B = B; pa.H = im->full_H; pa.W = im->W; pa.win_y0 = im->win_y0; pa.win_h = im->H; pa.S = S;
     pa.type = prop->d_type; pa.counts = prop->d_counts; pa.shape = prop->d_shape; pa.rsq_gal = rsq_galaxy();
     pa.recs = im->d_recs; pa.boxes = im->d_boxes; pa.kind = im->d_kind; pa.status = im->d_status; pa.nobox = 1;
     if ((rc = ensure_recs(im, S * B > 0 ? S * B : 1))) return rc;   // (before the pointers are taken)
     pa.recs = im->d_recs; pa.boxes = im->d_boxes; pa.kind = im->d_kind; pa.status = im->d_status;
-    // the fused rounds' arguments, in device memory: [0] for the full lists, [1] for the live lists (they differ in `need`)
-    SliceFuse *d_fz = reinterpret_cast<SliceFuse *>(((uintptr_t)(d_flags + 13) + 15) & ~(uintptr_t)15);
     SliceFuse fz[2];        // the source of an asynchronous copy: alive until the stream is synchronised at the end of the call
     if (fuse_ok) {
         memset(fz, 0, sizeof(fz));
@@ -2026,28 +2107,9 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
                     LAUNCH_EV(k_patch_ll<int>, dim3((unsigned)(S * B)), dim3(256), st, EV0(c, pi), EV1(c, pi), im->d_bands, B, S, im->d_recs,
                               d_owner, im->d_sbox, im->d_soff, (const int *)im->d_samp, im->d_nelec, im->H, im->W, 0, d_ll);
                 } else {
-                    if (gd > 0) {
-                        int pi = prof_slot(c, CEL_K_PATCH_LL);
-                        LAUNCH_EV((k_patch_ll_hw<0, int>), dim3((unsigned)gd), dim3(64), st, EV0(c, pi), EV1(c, pi),
-                                  im->d_bands, B, S, im->d_recs,
-                                  d_owner, im->d_sbox, im->d_soff, (const int *)im->d_samp, im->d_nelec, im->H, im->W, im->d_snz, c->tail_T, d_ll,
-                                  (const int *)(use_live ? d_live : d_jobs), 1, (const int *)(use_live ? d_flags + 4 : nullptr),
-                                  (const int *)(use_nz ? im->d_nzmode : nullptr), 1, SLICE_SPLIT);
-                    }
-                    if (gn > 0) {
-                        int pi = prof_slot(c, CEL_K_PATCH_LL);
-                        const SliceFuse *fq = fused ? d_fz + (use_live ? 1 : 0) : nullptr;
-                        if (fq)
-                            LAUNCH_EV(k_patch_ll_nz<true>, dim3((unsigned)gn), dim3(64), st, EV0(c, pi), EV1(c, pi), im->d_bands, B, S, im->d_recs,
-                                      (const int *)d_owner, (const int4 *)im->d_sbox, (const int4 *)im->d_snz, (const int *)im->d_nzmode,
-                                      (const int64_t *)im->d_nzoff, (const NzEntry *)im->d_nzlist, d_ll,
-                                      (const int *)(use_live ? d_live_nz : d_jobs_nz), (const int *)(use_live ? d_flags + 5 : nullptr), fq);
-                        else
-                            LAUNCH_EV(k_patch_ll_nz<false>, dim3((unsigned)gn), dim3(64), st, EV0(c, pi), EV1(c, pi), im->d_bands, B, S, im->d_recs,
-                                      (const int *)d_owner, (const int4 *)im->d_sbox, (const int4 *)im->d_snz, (const int *)im->d_nzmode,
-                                      (const int64_t *)im->d_nzoff, (const NzEntry *)im->d_nzlist, d_ll,
-                                      (const int *)(use_live ? d_live_nz : d_jobs_nz), (const int *)(use_live ? d_flags + 5 : nullptr), fq);
-                    }
+                    launch_resident_ll(c, im, S, d_owner, d_ll, use_nz, {gd, use_live ? d_live : d_jobs, use_live ? d_flags + 4 : nullptr},
+                                       {gn, use_live ? d_live_nz : d_jobs_nz, use_live ? d_flags + 5 : nullptr},
+                                       fused ? d_fz + (use_live ? 1 : 0) : nullptr);
                 }
                 if (!fused)
                 hipLaunchKernelGGL(k_slice_step, dim3((unsigned)((S + 63) / 64)), dim3(64 * B), 0, st, ss, S, B, ostr, d_ll, sigma, d_flags, (int)queued, prop->d_radec, d_owner,
@@ -2103,14 +2165,14 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
         HIP_TRY(hipMemsetAsync(d_bytes, 0, sizeof(unsigned long long), st));
         hipLaunchKernelGGL(k_slice_bytes, dim3(g256), dim3(256), 0, st, ss, S, B, (const int4 *)im->d_snz, d_bytes,
                            (const int *)(use_nz ? im->d_nzmode : nullptr), (const int64_t *)im->d_nzoff, fuse_ok ? d_flags + 11 : (int *)nullptr);
-        HIP_TRY(hipMemcpyAsync(h_flag_slot[0] + 6, d_bytes, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&c->mail->sh.w.slice_bytes, d_bytes, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         if (fuse_ok) HIP_TRY(hipMemcpyAsync(h_flag_slot[1], d_flags + 11, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
     if (stats) {
         if (fuse_ok) { evals = h_flag_slot[1][0]; rounds = h_flag_slot[1][1]; }    // what the per-round counts of the unfused rounds add up to
         stats[0] = rounds; stats[1] = evals;
-        stats[2] = (int64_t)(*reinterpret_cast<unsigned long long *>(h_flag_slot[0] + 6));
+        stats[2] = (int64_t)c->mail->sh.w.slice_bytes;
         stats[3] = queued;
     }
     return CEL_OK;
@@ -2137,11 +2199,48 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
     const int B = im->B;
     const int64_t S = src->S;
     const int ostr = (c->variant != 0) ? PLL_PARTS : 1;
-    // one allocation, carved: 2 x u64, (3 D + 13) x f64, (4 + D) x i32 per chain, the directions, 2 owners, 2 B ostr log-likelihood slots
-    const size_t per_chain = 2 * 8 + (size_t)(3 * D + 13) * 8 + (size_t)(4 + D) * 4 + (size_t)ndir * D * 8 + 2 * 4 + (size_t)2 * B * ostr * 8 + 4 +
-                             (size_t)2 * 2 * B * PLL_PARTS * 4;
-    const size_t need = per_chain * (size_t)S + 256;
+    // one allocation, carved (Carver: once for the size, once for the pointers)
+    SliceGen g;
+    SliceState rs;
+    double *d_dirs, *d_ll;
+    int *d_owner, *d_ids, *d_list, *d_list_nz, *d_flags;
+    auto carve = [&](char *base) {
+        Carver k{base};
+        const size_t n = (size_t)S;
+        rs.key = k.take<unsigned long long>(n);
+        rs.count = k.take<unsigned long long>(n);
+        g.key = rs.key; g.count = rs.count;
+        g.x = k.take<double>(n * D);
+        g.x0 = k.take<double>(n * D);
+        g.dir = k.take<double>(n * D);
+        g.lower = k.take<double>(n);
+        g.upper = k.take<double>(n);
+        g.log_u = k.take<double>(n);
+        g.llh_s = k.take<double>(n);
+        g.new_z = k.take<double>(n);
+        g.new_llh = k.take<double>(n);
+        g.start_lower = k.take<double>(n);
+        g.start_upper = k.take<double>(n);
+        g.acc_L = k.take<double>(n);
+        g.acc_U = k.take<double>(n);
+        g.pri = k.take<double>(2 * n);
+        d_dirs = k.take<double>(n * ndir * D);
+        d_ll = k.take<double>(2 * n * B * ostr);
+        g.phase = k.take<int>(n);
+        g.kdir = k.take<int>(n);
+        g.l_out = k.take<int>(n);
+        g.u_out = k.take<int>(n);
+        g.order = k.take<int>(n * D);
+        d_owner = k.take<int>(2 * n);
+        d_ids = k.take<int>(n);
+        d_list = k.take<int>(2 * n * B * PLL_PARTS);          // the running chains' blocks (k_sg_live_jobs): dense, at the photons
+        d_list_nz = k.take<int>(2 * n * B * PLL_PARTS);
+        d_flags = k.take<int>(8, 16);
+        return k.off;
+    };
+    const size_t need = carve(nullptr);
     HIP_TRY(im->d_sgen.grow(need, need + need / 4, st));
+    carve(im->d_sgen);
     if (!im->sgen_prop || im->sgen_prop->cap < 2 * S) {
         im->sgen_prop.reset();
         cel_sources *np = nullptr;
@@ -2150,38 +2249,6 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
         im->sgen_prop.reset(np);
     }
     cel_sources *prop = im->sgen_prop.get();
-    char *p = (char *)im->d_sgen;
-    SliceGen g;
-    SliceState rs;
-    rs.key = (unsigned long long *)p; p += 8 * S;
-    rs.count = (unsigned long long *)p; p += 8 * S;
-    g.key = rs.key; g.count = rs.count;
-    g.x = (double *)p; p += 8 * S * D;
-    g.x0 = (double *)p; p += 8 * S * D;
-    g.dir = (double *)p; p += 8 * S * D;
-    g.lower = (double *)p; p += 8 * S;
-    g.upper = (double *)p; p += 8 * S;
-    g.log_u = (double *)p; p += 8 * S;
-    g.llh_s = (double *)p; p += 8 * S;
-    g.new_z = (double *)p; p += 8 * S;
-    g.new_llh = (double *)p; p += 8 * S;
-    g.start_lower = (double *)p; p += 8 * S;
-    g.start_upper = (double *)p; p += 8 * S;
-    g.acc_L = (double *)p; p += 8 * S;
-    g.acc_U = (double *)p; p += 8 * S;
-    g.pri = (double *)p; p += 16 * S;
-    double *d_dirs = (double *)p; p += 8 * S * ndir * D;
-    double *d_ll = (double *)p; p += 8 * 2 * S * B * ostr;
-    g.phase = (int *)p; p += 4 * S;
-    g.kdir = (int *)p; p += 4 * S;
-    g.l_out = (int *)p; p += 4 * S;
-    g.u_out = (int *)p; p += 4 * S;
-    g.order = (int *)p; p += 4 * S * D;
-    int *d_owner = (int *)p; p += 8 * S;
-    int *d_ids = (int *)p; p += 4 * S;
-    int *d_list = (int *)p; p += 4 * 2 * S * B * PLL_PARTS;          // the running chains' blocks (k_sg_live_jobs): dense, at the photons
-    int *d_list_nz = (int *)p; p += 4 * 2 * S * B * PLL_PARTS;
-    int *d_flags = (int *)(((uintptr_t)p + 15) & ~(uintptr_t)15);
     g.D = D; g.ndir = ndir; g.compwise = compwise; g.step_out = step_out ? 1 : 0; g.max_steps_out = max_steps_out; g.param = param;
     g.sigma = sigma; g.phi_max = param ? phi_max : 0.0; g.dirs = compwise ? nullptr : d_dirs;
     if (!compwise) HIP_TRY(hipMemcpyAsync(d_dirs, dirs, sizeof(double) * S * ndir * D, hipMemcpyHostToDevice, st));
@@ -2200,7 +2267,7 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
                        (unsigned long long)seed);
     const bool use_nz = im->nz_valid && c->variant != 0;
     int64_t rounds = 0, evals = 0, queued = 0;
-    int *h_flags = reinterpret_cast<int *>(c->pinned + MAX_BANDS + 2);
+    int *h_flags = c->mail->sh.slice_flags;
     int rc = CEL_OK;
     const int64_t P = 2 * S;
     const int BATCH = 4;
@@ -2228,18 +2295,7 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
                 LAUNCH_EV(k_patch_ll<int>, dim3((unsigned)(P * B)), dim3(256), st, EV0(c, pi), EV1(c, pi), im->d_bands, B, P, im->d_recs,
                           (const int *)d_owner, im->d_sbox, im->d_soff, (const int *)im->d_samp, im->d_nelec, im->H, im->W, 0, d_ll);
             } else {
-                if (n_dense > 0) {
-                    int pi = prof_slot(c, CEL_K_PATCH_LL);
-                    LAUNCH_EV((k_patch_ll_hw<0, int>), dim3((unsigned)n_dense), dim3(64), st, EV0(c, pi), EV1(c, pi), im->d_bands, B, P, im->d_recs,
-                              (const int *)d_owner, im->d_sbox, im->d_soff, (const int *)im->d_samp, im->d_nelec, im->H, im->W, im->d_snz, c->tail_T, d_ll,
-                              (const int *)d_list, 1, (const int *)nullptr, (const int *)(use_nz ? im->d_nzmode : nullptr), 1, PLL_PARTS);
-                }
-                if (n_nz > 0) {
-                    int pi = prof_slot(c, CEL_K_PATCH_LL);
-                    LAUNCH_EV(k_patch_ll_nz<false>, dim3((unsigned)n_nz), dim3(64), st, EV0(c, pi), EV1(c, pi), im->d_bands, B, P, im->d_recs,
-                              (const int *)d_owner, (const int4 *)im->d_sbox, (const int4 *)im->d_snz, (const int *)im->d_nzmode,
-                              (const int64_t *)im->d_nzoff, (const NzEntry *)im->d_nzlist, d_ll, (const int *)d_list_nz, (const int *)nullptr, (const SliceFuse *)nullptr);
-                }
+                launch_resident_ll(c, im, P, d_owner, d_ll, use_nz, {n_dense, d_list, nullptr}, {n_nz, d_list_nz, nullptr}, nullptr);
             }
             hipLaunchKernelGGL(k_sg_consume, dim3(g256), dim3(256), 0, st, g, rs, S, B, ostr, (const double *)d_ll, d_flags);
             queued++;
@@ -2324,12 +2380,9 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
             const int64_t nm = src->S * im->B;
             if (resident && c->mass_reuse_of() && nm > 0) {
                 // both kernels of this path also sum every unit stamp they evaluate: together the stamps' masses (cel_stamp_mass)
-                if (nm > im->d_massfx.cap) {     // the two grow together; d_massfx, allocated last, holds the pair's capacity
-                    HIP_TRY(hipStreamSynchronize(c->stream));
-                    im->d_massfx.reset(); im->d_mass_todo.reset();
+                if (nm > im->d_massfx.cap) {     // the two grow together; d_massfx, named last, holds the pair's capacity
                     const int64_t cap = nm + nm / 4 + 64;
-                    HIP_TRY(im->d_mass_todo.grow(cap + 1, cap + 1, c->stream));
-                    HIP_TRY(im->d_massfx.grow(nm, cap, c->stream));
+                    HIP_TRY(grow_group(c->stream, im->d_mass_todo, cap + 1, im->d_massfx, cap));
                 }
                 HIP_TRY(hipMemsetAsync(im->d_massfx, 0, sizeof(unsigned long long) * nm, c->stream));
                 use_massfx = true;
@@ -2362,18 +2415,9 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
     if (resident) {
         // patch boxes + offsets laid out on the device; only the total size comes back
         if (n + 1 > im->d_sbox.cap) {
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            im->d_sbox.reset(); im->d_snz.reset(); im->d_soff.reset(); im->d_ssum.reset();
-            im->d_nnz.reset(); im->d_nzmode.reset(); im->d_nzoff.reset(); im->d_btot.reset();
             const int64_t cap = n + n / 4 + 64, nb = cap / 1024 + 2;
-            HIP_TRY(im->d_snz.grow(n + 1, cap, c->stream));
-            HIP_TRY(im->d_soff.grow(n + 1, cap, c->stream));
-            HIP_TRY(im->d_ssum.grow(n + 1, cap, c->stream));
-            HIP_TRY(im->d_nnz.grow(n + 1, cap, c->stream));
-            HIP_TRY(im->d_nzmode.grow(n + 1, cap, c->stream));
-            HIP_TRY(im->d_nzoff.grow(n + 1, cap, c->stream));
-            HIP_TRY(im->d_btot.grow(nb, nb, c->stream));
-            HIP_TRY(im->d_sbox.grow(n + 1, cap, c->stream));
+            HIP_TRY(grow_group(c->stream, im->d_snz, cap, im->d_soff, cap, im->d_ssum, cap, im->d_nnz, cap, im->d_nzmode, cap,
+                               im->d_nzoff, cap, im->d_btot, nb, im->d_sbox, cap));
         }
         {
             const unsigned nblk = (unsigned)((n + 1023) / 1024);
@@ -2381,9 +2425,9 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
             hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(1024), 0, c->stream, im->d_btot, (int)nblk, im->d_soff + n);
             hipLaunchKernelGGL(k_scan_apply, dim3(nblk), dim3(1024), 0, c->stream, im->d_soff, n, (const long long *)im->d_btot);
         }
-        HIP_TRY(hipMemcpyAsync(c->pinned + MAX_BANDS + 2, im->d_soff + n, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(&c->mail->sh.scan_total, im->d_soff + n, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        memcpy(&total, c->pinned + MAX_BANDS + 2, sizeof(total));
+        total = c->mail->sh.scan_total;
         HIP_TRY(im->d_samp.grow(total, total + total / 8 + 1024, c->stream));
         d_off = im->d_soff;
         d_samp = im->d_samp;
@@ -2404,10 +2448,10 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
                                 (long long)sidx, b, (long long)(offsets[i + 1] - offsets[i]), (long long)area);
             }
         total = offsets[n];
-        if ((rc = scratch_get(c, 1, sizeof(int64_t) * (n + 1), (void **)&d_off))) return rc;
+        if ((rc = scratch_get(c, SCR_OFFSETS, sizeof(int64_t) * (n + 1), (void **)&d_off))) return rc;
         HIP_TRY(hipMemcpyAsync(d_off, offsets, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, c->stream));
         if (mem == CEL_DEVICE) d_samp = samp;
-        else if ((rc = scratch_get(c, 3, sizeof(double) * (total > 0 ? total : 1), &d_samp))) return rc;
+        else if ((rc = scratch_get(c, SCR_PATCH_DATA, sizeof(double) * (total > 0 ? total : 1), &d_samp))) return rc;
     }
     // resident + recurrence form: the kernel writes every interior pixel and reduces the photon
     // rectangles itself; otherwise zero the buffer and (resident) find the rectangles afterwards
@@ -2439,7 +2483,7 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
         a.nnz = lists ? im->d_nnz : nullptr;
         a.massfx = (use_massfx && hw && resident) ? im->d_massfx : nullptr;
         a.debug = c->debug;
-        if (hw && (rc = scratch_get(c, 2, sizeof(double) * 2 * (size_t)T, (void **)&a.partials))) return rc;
+        if (hw && (rc = scratch_get(c, SCR_VALUES, sizeof(double) * 2 * (size_t)T, (void **)&a.partials))) return rc;
         int pi = prof_begin(c, CEL_K_SPLIT);
         if (hw && resident) {
             if (im->nelec_u16) hipLaunchKernelGGL((k_photon_split_hw<int, unsigned short>), dim3(2 * T), dim3(64), 0, c->stream, a);
@@ -2464,17 +2508,15 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
         hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(1024), 0, c->stream, im->d_btot, (int)nblk, im->d_nzoff + n);
         hipLaunchKernelGGL(k_scan_apply, dim3(nblk), dim3(1024), 0, c->stream, im->d_nzoff, n, (const long long *)im->d_btot);
     }
-    HIP_TRY(hipMemcpyAsync(c->pinned, im->d_llband, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
-    if (lists) HIP_TRY(hipMemcpyAsync(c->pinned + MAX_BANDS + 2, im->d_nzoff + n, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->mail->ll_band, im->d_llband, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
+    if (lists) HIP_TRY(hipMemcpyAsync(&c->mail->sh.scan_total, im->d_nzoff + n, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     if (resident) im->hsum_valid = false;
     if (fused_nz) {
         // what a Gibbs sweep asks for next (the photons per source: the flux and sky steps; the patch areas) rides back now:
         // cel_samples_fetch then needs no wait of its own, and the list compaction queued below runs under the host's work
         if (n + 1 > im->h_ssum.cap) {
-            im->h_ssum.reset(); im->h_soff.reset();
             const int64_t cap = n + n / 4 + 64;
-            HIP_TRY(im->h_soff.grow(n + 1, cap, c->stream));
-            HIP_TRY(im->h_ssum.grow(n + 1, cap, c->stream));
+            HIP_TRY(grow_group(c->stream, im->h_soff, cap, im->h_ssum, cap));
         }
         HIP_TRY(hipMemcpyAsync(im->h_ssum, im->d_ssum, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(im->h_soff, im->d_soff, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, c->stream));
@@ -2484,11 +2526,10 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (fused_nz) im->hsum_valid = true;
-    if (noise) for (int b = 0; b < B; b++) noise[b] = c->pinned[b];
+    if (noise) for (int b = 0; b < B; b++) noise[b] = c->mail->ll_band[b];
     if (use_massfx && hw && resident) im->massfx_gen = src->gen;
     if (lists) {
-        int64_t nn = 0;
-        memcpy(&nn, c->pinned + MAX_BANDS + 2, sizeof(nn));
+        const int64_t nn = c->mail->sh.scan_total;
         HIP_TRY(im->d_nzlist.grow(nn, nn + nn / 4 + 1024, c->stream));
         // stream-ordered: whatever scores against these patches next runs behind it
         hipLaunchKernelGGL(k_nz_compact, dim3((unsigned)n), dim3(64), 0, c->stream, (const int4 *)im->d_sbox, (const int64_t *)im->d_soff,
@@ -2536,7 +2577,7 @@ int cel_samples_fetch(cel_images *im, int32_t *boxes, int64_t *offsets, double *
             if ((rc = copy_out(sums, im->d_ssum, sizeof(double) * n, CEL_HOST, c->stream))) return rc;
         } else {
             double *d_sums = nullptr;
-            if ((rc = scratch_get(c, 2, sizeof(double) * n, (void **)&d_sums))) return rc;
+            if ((rc = scratch_get(c, SCR_PATCH_DATA, sizeof(double) * n, (void **)&d_sums))) return rc;
             hipLaunchKernelGGL(k_patch_sums<int>, dim3((unsigned)n), dim3(256), 0, c->stream, im->d_soff, (const int *)im->d_samp, d_sums);
             if ((rc = copy_out(sums, d_sums, sizeof(double) * n, CEL_HOST, c->stream))) return rc;
         }
@@ -2591,17 +2632,11 @@ int cel_estep_stats(cel_images *im, cel_sources *src, double *xtilde, double *ma
     // lists and boxes of exactly these sources on the device); CEL_OPT_DEBUG bit 64 keeps the per-source form
     const bool tiles = (c->variant != 0) && (im->TW == HW_TW) && !(c->debug & 64) && S > 0;
     std::vector<double> hx((size_t)(S * B)), hm((size_t)(S * B));
-    hipError_t e;
-#define ES_TRY(expr)                                                                     \
-    do {                                                                                 \
-        e = (expr);                                                                      \
-        if (e != hipSuccess) { rc = fail(CEL_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e)); goto done; } \
-    } while (0)
     if (S > 0) {
-        // the context's scratch arena (slots 4/5), not an allocation per call: EM iterates this
-        if ((rc = scratch_get(c, 4, sizeof(double) * S * B, (void **)&d_x)) ||
-            (rc = scratch_get(c, 5, sizeof(double) * S * B, (void **)&d_m))) goto done;
-        if (tiles && (rc = scratch_get(c, 6, sizeof(double) * 2 * (size_t)im->d_lists.cap, (void **)&d_part))) goto done;
+        // the context's scratch arena, not an allocation per call: EM iterates this
+        if ((rc = scratch_get(c, SCR_TMP_A, sizeof(double) * S * B, (void **)&d_x)) ||
+            (rc = scratch_get(c, SCR_TMP_B, sizeof(double) * S * B, (void **)&d_m))) return rc;
+        if (tiles && (rc = scratch_get(c, SCR_TMP_C, sizeof(double) * 2 * (size_t)im->d_lists.cap, (void **)&d_part))) return rc;
         int pi = prof_begin(c, CEL_K_ESTEP);
         if (c->variant == 0)
             hipLaunchKernelGGL(k_estep_src, dim3((unsigned)(S * B)), dim3(256), 0, c->stream, im->d_bands, B, im->H, im->W,
@@ -2623,23 +2658,20 @@ int cel_estep_stats(cel_images *im, cel_sources *src, double *xtilde, double *ma
             hipLaunchKernelGGL(k_estep_src_hw, dim3((unsigned)(S * B)), dim3(64), 0, c->stream, im->d_bands, B, im->H, im->W,
                                S, im->d_recs, im->d_nelec, im->d_lambda, c->tail_T, d_x, d_m);
         prof_end(c, pi);
-        ES_TRY(hipMemcpyAsync(hx.data(), d_x, sizeof(double) * S * B, hipMemcpyDeviceToHost, c->stream));
-        ES_TRY(hipMemcpyAsync(hm.data(), d_m, sizeof(double) * S * B, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(hx.data(), d_x, sizeof(double) * S * B, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(hm.data(), d_m, sizeof(double) * S * B, hipMemcpyDeviceToHost, c->stream));
     }
     if (!tiles)      // the tile walk has left the sky term's per-tile sums in d_partials
         hipLaunchKernelGGL(k_estep_noise, dim3(B * nblk), dim3(256), 0, c->stream, im->d_bands, (int64_t)im->H * im->W, nblk,
                            im->d_nelec, im->d_lambda, im->d_partials);
     hipLaunchKernelGGL(k_reduce, dim3(B), dim3(256), 0, c->stream, im->d_partials, nblk, im->d_llband, nblk, 0, 1);
-    ES_TRY(hipMemcpyAsync(c->pinned, im->d_llband, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
-    ES_TRY(hipGetLastError());
-    ES_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpyAsync(c->mail->ll_band, im->d_llband, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
     if (xtilde) memcpy(xtilde, hx.data(), sizeof(double) * S * B);
     if (mass) memcpy(mass, hm.data(), sizeof(double) * S * B);
-    if (noise) for (int b = 0; b < B; b++) noise[b] = c->pinned[b];
-#undef ES_TRY
-done:
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    if (noise) for (int b = 0; b < B; b++) noise[b] = c->mail->ll_band[b];
+    return CEL_OK;
 }
 
 // ---- gradient of the field log-likelihood (k_grad.h) --------------------------------------------
@@ -2660,10 +2692,10 @@ int cel_loglik_grad(cel_images *im, cel_sources *src, double *ll_total, double *
     const int64_t S = src->S;
     if (S > 0 && (g_radec || g_counts || g_shape)) {
         double *d_sums = nullptr, *d_out = nullptr;
-        if ((rc = scratch_get(c, 4, sizeof(double) * GRAD_NS * S * B, (void **)&d_sums))) return rc;
+        if ((rc = scratch_get(c, SCR_TMP_A, sizeof(double) * GRAD_NS * S * B, (void **)&d_sums))) return rc;
         double *o_radec = g_radec, *o_counts = g_counts, *o_shape = g_shape;
         if (mem != CEL_DEVICE) {
-            if ((rc = scratch_get(c, 5, sizeof(double) * (size_t)S * (6 + B), (void **)&d_out))) return rc;
+            if ((rc = scratch_get(c, SCR_TMP_B, sizeof(double) * (size_t)S * (6 + B), (void **)&d_out))) return rc;
             o_radec = g_radec ? d_out : nullptr;
             o_shape = g_shape ? d_out + 2 * S : nullptr;
             o_counts = g_counts ? d_out + 6 * S : nullptr;
@@ -2744,15 +2776,15 @@ int cel_mog_loglike(cel_ctx *c, const double *x, int64_t N, const double *means,
     }
     double *d_comp = nullptr, *d_x = nullptr, *d_o = nullptr;
     int rc;
-    if ((rc = scratch_get(c, 4, sizeof(double) * 6 * K, (void **)&d_comp))) return rc;
+    if ((rc = scratch_get(c, SCR_TMP_A, sizeof(double) * 6 * K, (void **)&d_comp))) return rc;
     HIP_TRY(hipMemcpyAsync(d_comp, comp.data(), sizeof(double) * 6 * K, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));      // comp is a local
     if (mem == CEL_DEVICE) {
         d_x = const_cast<double *>(x);
         d_o = out;
     } else {
-        if ((rc = scratch_get(c, 5, sizeof(double) * 2 * N, (void **)&d_x)) ||
-            (rc = scratch_get(c, 6, sizeof(double) * N, (void **)&d_o))) return rc;
+        if ((rc = scratch_get(c, SCR_TMP_B, sizeof(double) * 2 * N, (void **)&d_x)) ||
+            (rc = scratch_get(c, SCR_TMP_C, sizeof(double) * N, (void **)&d_o))) return rc;
         HIP_TRY(hipMemcpyAsync(d_x, x, sizeof(double) * 2 * N, hipMemcpyHostToDevice, c->stream));
     }
     int pi = prof_begin(c, CEL_K_GMM);
@@ -2786,8 +2818,8 @@ int cel_galaxy_mixture_params(cel_ctx *c, int64_t N, const double *W, const doub
     memcpy(q, sigs, sizeof(double) * J);
     double *d_in = nullptr, *d_out = nullptr;
     int rc;
-    if ((rc = scratch_get(c, 4, sizeof(double) * nin, (void **)&d_in)) ||
-        (rc = scratch_get(c, 5, sizeof(double) * 7 * n, (void **)&d_out))) return rc;
+    if ((rc = scratch_get(c, SCR_TMP_A, sizeof(double) * nin, (void **)&d_in)) ||
+        (rc = scratch_get(c, SCR_TMP_B, sizeof(double) * 7 * n, (void **)&d_out))) return rc;
     HIP_TRY(hipMemcpyAsync(d_in, hin.data(), sizeof(double) * nin, hipMemcpyHostToDevice, c->stream));
     const double *dW = d_in, *dv = dW + 4 * N, *dws = dv + 2 * N, *dmu = dws + K_psf, *dcv = dmu + 2 * K_psf,
                  *damp = dcv + 4 * K_psf, *dsig = damp + J;

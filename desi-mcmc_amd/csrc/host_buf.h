@@ -30,6 +30,7 @@ public:
     ~Buf() { reset(); }
 
     operator T *() const { return p; }
+    T *operator->() const { return p; }
     T *get() const { return p; }
 
     // free now (the caller has synchronised whatever used the block)
@@ -57,3 +58,34 @@ public:
 template <class T> using DevBuf = Buf<T, BUF_DEVICE>;
 template <class T, unsigned Flags = hipHostMallocDefault> using PinnedBuf = Buf<T, Flags>;
 template <class T> using MappedBuf = PinnedBuf<T, hipHostMallocMapped | hipHostMallocCoherent>;   // pinned, device-mapped, coherent
+
+// Buffers that are grown together and share ONE capacity test: grow_group(stream, a, na, b, nb, ..., z, nz) synchronises, frees
+// every one of them and allocates them again in the order given, each with its own element count.  The caller tests the
+// capacity of the one named LAST: a failed allocation leaves every later buffer empty, so that test stays false and the next
+// call grows the whole group again.
+inline void group_reset() {}
+template <class B, class... R> void group_reset(B &b, int64_t, R &...rest) { b.reset(); group_reset(rest...); }
+inline hipError_t group_alloc(hipStream_t) { return hipSuccess; }
+template <class B, class... R> hipError_t group_alloc(hipStream_t stream, B &b, int64_t n, R &...rest) {
+    const hipError_t e = b.grow(n, n, stream);
+    return e != hipSuccess ? e : group_alloc(stream, rest...);
+}
+template <class... A> hipError_t grow_group(hipStream_t stream, A &&...bufs_and_counts) {
+    const hipError_t e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return e;
+    group_reset(bufs_and_counts...);
+    return group_alloc(stream, bufs_and_counts...);
+}
+
+// One allocation carved into arrays.  The function that names the arrays runs twice over the same code: with no base, to get
+// the arena's size (every pointer comes out null), then with the allocation -- the size and the pointers cannot disagree.
+struct Carver {
+    char *base;
+    size_t off = 0;
+    template <class T> T *take(size_t n, size_t align = alignof(T)) {
+        off = (off + align - 1) & ~(align - 1);
+        T *r = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += sizeof(T) * n;
+        return r;
+    }
+};

@@ -1202,6 +1202,32 @@ def test_stamp_masses_read_off_the_split(cel, orc):
             assert abs(quick[s, b] - want) <= 1e-10 * max(want, 1e-3), (s, b, quick[s, b], want)
 
 
+def test_sums_fetched_between_stamp_mass_begin_and_end(cel):
+    """The header allows cel_samples_fetch between cel_stamp_mass_begin and cel_stamp_mass_end.  With the direct kernels
+    (CEL_OPT_KERNEL = 0) the split does not sum its patches itself, so the fetch of the sums runs k_patch_sums into a scratch
+    buffer of its own: that buffer must not be the one the pending masses wait in.  The masses must be cel_stamp_mass's of the
+    same catalogue bit for bit, the sums the patches' own sums."""
+    from desi_mcmc_amd import _lib, synth
+    ctx = cel.default_context(0)
+    f = synth.SyntheticField(ctx, 120, 5, 192, 192, frac_gal=0.5, seed=27)
+    try:
+        ctx.set_option(_lib.CEL_OPT_KERNEL, 0)
+        f.images.photon_split_resident(f.sources, seed=5)
+        want = f.images.stamp_mass(f.sources)
+        f.images.stamp_mass_begin(f.sources)
+        sums = f.images.sample_sums()
+        got = f.images.stamp_mass_end()
+        _, offs, data = f.images.fetch_samples()
+    finally:
+        ctx.set_option(_lib.CEL_OPT_KERNEL, 1)
+    assert want.shape == got.shape == sums.shape == (120, 5)
+    assert np.array_equal(got, want)
+    run = np.concatenate([[0.0], np.cumsum(data)])          # photon counts: every partial sum is an exact integer
+    patch_sums = (run[offs[1:]] - run[offs[:-1]]).reshape(120, 5)
+    assert np.array_equal(sums, patch_sums) and patch_sums.sum() > 0
+    assert not np.array_equal(sums, want)                    # (the two are different things: nothing passes by coincidence)
+
+
 @pytest.mark.parametrize("y0,hw", [(37, 150), (64, 128), (91, 165)])
 def test_split_draws_do_not_depend_on_the_window(cel, y0, hw):
     """A pixel's draws are keyed by its FULL-FRAME coordinates -- the first test's shared Philox half-word by (column, the row with
