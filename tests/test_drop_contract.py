@@ -42,17 +42,13 @@ import numpy as np
 import pytest
 
 from conftest import tail_log
+from _exact_terms import C_R, DELTA, LD, H, W, chunk_sub, components, patch_rel_err, source_terms
 
 pytestmark = pytest.mark.gpu
 
-H = W = 256
 NB = 5
 T_ALL = (0, 4, 8, 12, 20, 24, 32)
 T_EDGE = (4, 8, 12, 20)              # thresholds whose ellipse ends are placed on integer rows
-C_R = 1e-12
-DELTA = 1e-3
-LD = np.longdouble
-PI2 = 2 * np.arccos(LD(-1))
 EDGE_BAND = 2                        # the band whose ellipses are placed (r)
 SHARP_BAND = 4                       # this band's PSF is narrowed to 0.3 pixel
 
@@ -73,40 +69,7 @@ def orc():
     return oracle
 
 
-# ---------------------------------------------------------------------------------------------------------------------
-# the exact per-term reference
-def components(orc, band, typ, u, shape):
-    """unit-flux mixture of one source in one band: (w[K], mu[K, 2] (x, y) in pixels, cov[K, 2, 2])"""
-    if typ == 0:
-        v = orc.equa2pixel(band, u)
-        return band[3:6].copy(), band[6:12].reshape(3, 2) + v[None, :], band[12:24].reshape(3, 2, 2).copy()
-    w, mu, cov, _, _ = orc.galaxy_table(band, shape, u)
-    return w, mu, cov
-
-
-def source_terms(orc, band, typ, u, shape):
-    """-> (box (y0, y1, x0, x1), terms[K, ny, nx], the oracle's own unit patch) or None outside the frame.  Each term is one
-    fp64 exp (a few ulp, plus |q| ulp for the argument: far inside C_R)"""
-    patch, (y0, y1), (x0, x1) = orc.source_patch(band, H, W, typ, u, shape)
-    if patch is None:
-        return None
-    w, mu, cov = components(orc, band, typ, u, shape)
-    det = cov[:, 0, 0] * cov[:, 1, 1] - cov[:, 0, 1] * cov[:, 1, 0]
-    ia, ib, ic = cov[:, 1, 1] / det, -0.5 * (cov[:, 0, 1] + cov[:, 1, 0]) / det, cov[:, 0, 0] / det
-    dx = np.arange(x0, x1, dtype=np.float64)[None, None, :] - mu[:, 0, None, None]
-    dy = np.arange(y0, y1, dtype=np.float64)[None, :, None] - mu[:, 1, None, None]
-    q = ia[:, None, None] * dx * dx + 2 * ib[:, None, None] * dx * dy + ic[:, None, None] * dy * dy
-    amp = w / (2 * np.pi * np.sqrt(det))
-    return (y0, y1, x0, x1), amp[:, None, None] * np.exp(-0.5 * q), patch
-
-
-def patch_rel_err(u, patch):
-    """the reference's self-check against the oracle's unit patch, where the oracle's exp(log-sum) is itself good to 1e-13
-    (|log p| < 230: its argument's rounding, |log p| ulp, stays below 5e-14)"""
-    m = patch >= 1e-100
-    return float(np.max(np.abs(u[m] - patch[m]) / patch[m])) if m.any() else 0.0
-
-
+# the exact per-term reference: components, source_terms, patch_rel_err (_exact_terms.py, shared with test_conditional_contract.py)
 class FieldRef(object):
     """lam_full, sum |t| and, per T, the sum of the terms at or below the field render's threshold -- per band and pixel; the
     unit patches for the E-step.  A source's terms are added in fp64 (<= 42 ulp of sum |t|: 1e-14, far inside C_R), the
@@ -442,20 +405,6 @@ def test_incremental_render_after_set_rows(cel, orc, geom):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # the per-source kernels (hw_source.h, HW_DROP_SELF): the threshold is the source's own smallest value on the rectangle
-def _stamp_bound(terms, box, T):
-    """S_sub and tol of a unit stamp under k_stamps_hw's rectangles (32 columns x 64 rows from the box's corner): on each, a
-    component is dropped only below e^-T times the source's floor there, the largest of the components' minima"""
-    y0, y1, x0, x1 = box
-    sub = np.zeros(terms.shape[1:])
-    for ys in range(0, y1 - y0, 64):
-        for xs in range(0, x1 - x0, 32):
-            t = terms[:, ys:ys + 64, xs:xs + 32]
-            floor = float(t.reshape(t.shape[0], -1).min(axis=1).max())
-            thr = floor * math.exp(-T) * (1 + DELTA)
-            sub[ys:ys + 64, xs:xs + 32] = np.where(np.abs(t) <= thr, t, 0).sum(axis=0).astype(np.float64)
-    return sub
-
-
 def test_unit_stamps_keep_every_term_above_the_source_floor(cel, orc, geom):
     ctx = cel.Context(0)
     f = _gdict(geom)
@@ -477,7 +426,7 @@ def test_unit_stamps_keep_every_term_above_the_source_floor(cel, orc, geom):
                 box, t, _ = r
                 assert tuple(boxes[s]) == box
                 full = t.sum(axis=0)
-                sub = _stamp_bound(t, box, T)                  # (a star's three components take the same table and drop test)
+                sub = chunk_sub(t, T)                          # (a star's three components take the same table and drop test)
                 tol = C_R * np.abs(t).sum(axis=0).astype(np.float64) + 4 * np.spacing(full.astype(np.float64))
                 lo = (full - LD(1) * st[s]).astype(np.float64)
                 r_lo, r_hi = float(np.max((lo - sub) / tol)), float(np.max(-lo / tol))
