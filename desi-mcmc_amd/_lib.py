@@ -27,7 +27,7 @@ CEL_OPT_TAIL_LOG_SOURCE, CEL_OPT_TILE_PARTS, CEL_OPT_INCREMENTAL, CEL_OPT_SPLIT_
 #: the per-source kernels keep 32 (CEL_OPT_TAIL_LOG_SOURCE reads / sets theirs alone).  TAIL_LOG_STRICT = 32 for both: the
 #: strict variants of the parity tests (conftest.tail_log); the suite itself runs at these shipping defaults.
 TAIL_LOG_DEFAULT, TAIL_LOG_STRICT, TAIL_LOG_FAST = 24.0, 32.0, 20.0
-KERNELS = {"prep": 0, "bin": 1, "render": 2, "reduce": 3, "stamps": 4, "gmm": 5, "patch_ll": 6, "split": 7, "mass": 8, "estep": 9, "render_stars": 10, "small_stars": 11, "totals": 12, "grad": 13}
+KERNELS = {"prep": 0, "bin": 1, "render": 2, "reduce": 3, "stamps": 4, "gmm": 5, "patch_ll": 6, "split": 7, "mass": 8, "estep": 9, "render_stars": 10, "small_stars": 11, "totals": 12, "grad": 13, "masked_ll": 14}
 BAND_DOUBLES = 37
 MAX_BANDS = 16
 
@@ -50,6 +50,7 @@ SYMBOLS = [
     ("cel_images_create", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, c_void_pp]),
     ("cel_images_destroy", C.c_int, [C.c_void_p]),
     ("cel_images_set_nelec", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("cel_images_mask_info", C.c_int, [C.c_void_p, c_int64_p]),
     ("cel_images_set_epsilon", C.c_int, [C.c_void_p, C.c_int, C.c_double]),
     ("cel_images_set_window", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("cel_images_set_noise_rows", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -106,6 +107,11 @@ SYMBOLS = [
 
 class CelesteHipError(RuntimeError):
     pass
+
+
+class MaskedImagesError(CelesteHipError, ValueError):
+    """a call that has not been taught about masked pixels (NaN counts, cel_images_set_nelec) was handed a masked image set:
+    the library's refusal (CEL_ERR_INVALID, hence a ValueError) raised by the Python layer before any device call"""
 
 
 _lib = None

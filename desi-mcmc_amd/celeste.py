@@ -101,7 +101,8 @@ def _image_set(images):
     H, W = images[0].nelec.shape
     ctx = _field.default_context(_DEVICE)
     bands = np.stack([im.band_record() for im in images])
-    iset = _field.ImageSet(ctx, bands, H, W, nelec=np.stack([im.nelec for im in images]))
+    # (`observed`: nelec, with NaN at the invvar == 0 pixels of an image built with mask_invvar=True)
+    iset = _field.ImageSet(ctx, bands, H, W, nelec=np.stack([getattr(im, "observed", im.nelec) for im in images]))
     try:
         refs = [weakref.ref(im) for im in images]
     except TypeError:
@@ -637,6 +638,7 @@ def estep_statistics(srcs, imgs):
     (S+1, H, W) layers -- usable at 10 000 sources x 2048^2 where the layers would need 335 GB/band:
         X_tildes[s, n] = sum(all_src_probs[n][s+1] * imgs[n].nelec)          (celeste_em.py:85)
         sum_fs[s, n]   = min(1, sum(unit stamp of source s in image n))      (celeste_em.py:89)
+                         -- over the UNMASKED pixels of its box in an image built with mask_invvar=True, as X_tildes and noise
         noise[n]       = sum(imgs[n].nelec * src_probs[0])                   (celeste_em.py:62, x size)
     -> (X_tildes (S, N), sum_fs (S, N), noise (N,))"""
     imgs = list(imgs)

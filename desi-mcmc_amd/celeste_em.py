@@ -63,12 +63,15 @@ def celeste_em(srcs, imgs, maxiter=20, debug=False, verbose=True, planck=None):
             # M-step, sky levels (:60-63): the photons the E-step left to the sky, per pixel
             for i, img in enumerate(imgs):
                 before = img.epsilon
-                img.epsilon = Z[i] / img.nelec.size
+                # ... per OBSERVED pixel: an image built with mask_invvar=True leaves its invvar == 0 pixels out of Z[i] too
+                img.epsilon = Z[i] / (img.nelec.size - getattr(img, "n_masked", 0))
                 if detail:
                     say("[%d] image %d sky %.3f -> %.3f" % (em_iter, i, before, img.epsilon))
             # M-step, sources (:113-141): temperature by a 1-D search on the profiled objective, brightness in closed form
             for s in range(len(srcs)):
                 X_tildes, sum_fs = X_all[s], F_all[s]
+                if not np.any(sum_fs > 0):
+                    continue        # every pixel of the source's boxes is masked, in every image: nothing to fit, t and b stay
 
                 def temperature_objective(temp):
                     I_ts = band_efficiency(temp)

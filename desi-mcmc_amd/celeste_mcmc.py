@@ -214,6 +214,8 @@ class ModelGibbs(object):
     def __init__(self, fields, typ, u, fluxes, shape, seed=0, flux_a_0=5., flux_b_0=.005, slice_args=None, engine="auto",
                  deal=None, shape_args=None, shape_logprior=None, phi_period=180., shape_mass="reference", conditional="reference"):
         self.fields = list(fields)
+        for f in self.fields:       # the sweep on masked data is not built (photon split, flux masses, sky step): refuse it up front
+            f.iset._refuse_masked("ModelGibbs")
         self.typ = np.ascontiguousarray(typ, dtype=np.int32)
         self.S = self.typ.shape[0]
         self.u = np.array(u, dtype=np.float64).reshape(self.S, 2)
@@ -319,6 +321,10 @@ class ModelGibbs(object):
         for img_dict in img_dicts:
             bands = [b for b in cls.BANDS if b in img_dict]
             imgs = [img_dict[b] for b in bands]
+            if any(getattr(im, "n_masked", 0) for im in imgs):
+                from ._lib import MaskedImagesError
+                raise MaskedImagesError("ModelGibbs: the images hold masked pixels (FitsImage(mask_invvar=True)) and the Gibbs "
+                                        "sweep does not honour a mask")
             iset = _celeste._image_set(tuple(imgs))
             f = GibbsField(iset, [cls.BANDS.index(b) for b in bands], [im.calib for im in imgs],
                            [im.kappa for im in imgs], imgs[0].nelec.size)

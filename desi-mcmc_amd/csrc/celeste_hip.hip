@@ -90,6 +90,7 @@ static int fail(int code, const char *fmt, ...) {
 #include "k_small_stars.h"
 #include "k_border.h"
 #include "k_render_qw.h"
+#include "k_mask.h"
 #include "k_misc.h"
 #include "k_patch_ll.h"
 #include "k_slice_gen.h"
@@ -254,6 +255,8 @@ struct cel_images {
     double *d_mass = nullptr;        // (points into a scratch slot of the context: not owned)
     DevBuf<long long> d_btot;        // per-1024-entries totals of the patch / list layout scans
     bool nelec_u16 = false;          // every observed pixel in 0 ... 65 535: the split's 16-bit photons-left plane
+    int64_t masked[MAX_BANDS] = {0}; // NaN (masked) pixels per band that the last cel_images_set_nelec found (cel_images_mask_info)
+    bool any_masked = false;         // ... at least one: a MASKED set (k_mask.h, the masked twins of the gradient and E-step kernels)
     bool star_one_segment = false;   // every band passes star_setup's test: k_render_stars may take star tiles
     int64_t order_S = -1;         // d_order already holds the heaviest-first order of those costs (sorted behind that render's readback)
     hipEvent_t ev_step = nullptr; // marks a step's readback copy: the host waits for it, not for the sort queued behind it
@@ -754,20 +757,46 @@ int cel_images_set_nelec(cel_images *im, const double *nelec, int mem) {
     im->partials_gen = 0;                 // the tiles' Poisson partials were formed against the old pixels (the incremental render keeps none of them)
     // the image's range: 0 ... 65 535 everywhere lets the photon split keep its photons-left plane in 16 bits (k_split.h)
     im->nelec_u16 = false;
+    // ... and the NaN counts per band: the mask (a block's count stays below 2^53: exact in a double)
+    im->any_masked = false;
     {
-        const int NB = 512;
+        const int nbb = std::max(1, 512 / im->B), NB = nbb * im->B;     // blocks per band
         DevBuf<double> d_rng;
         HIP_TRY(d_rng.grow(3 * NB, 3 * NB, im->ctx->stream));
         hipLaunchKernelGGL(k_nelec_range, dim3(NB), dim3(256), 0, im->ctx->stream, (const double *)im->d_nelec,
-                           (int64_t)im->B * im->H * im->W, d_rng);
+                           (int64_t)im->H * im->W, nbb, d_rng);
         std::vector<double> h((size_t)3 * NB);
         HIP_TRY(hipMemcpyAsync(h.data(), d_rng, sizeof(double) * 3 * NB, hipMemcpyDeviceToHost, im->ctx->stream));
         HIP_TRY(hipStreamSynchronize(im->ctx->stream));
-        double lo = INFINITY, hi = -INFINITY, bad = 0.0;
-        for (int k = 0; k < NB; k++) { lo = fmin(lo, h[3 * k]); hi = fmax(hi, h[3 * k + 1]); bad += h[3 * k + 2]; }
-        im->nelec_u16 = (bad == 0.0) && (lo >= 0.0) && (hi <= 65535.0);
+        double lo = INFINITY, hi = -INFINITY;
+        int64_t bad = 0;
+        for (int b = 0; b < im->B; b++) {
+            im->masked[b] = 0;
+            for (int k = b * nbb; k < (b + 1) * nbb; k++) {
+                lo = fmin(lo, h[3 * k]); hi = fmax(hi, h[3 * k + 1]);
+                im->masked[b] += (int64_t)h[3 * k + 2];
+            }
+            bad += im->masked[b];
+        }
+        im->any_masked = bad != 0;
+        im->nelec_u16 = (bad == 0) && (lo >= 0.0) && (hi <= 65535.0);
     }
     return CEL_OK;
+}
+
+int cel_images_mask_info(cel_images *im, int64_t *masked) {
+    if (!im || !masked) return fail(CEL_ERR_INVALID, "cel_images_mask_info: null argument");
+    for (int b = 0; b < im->B; b++) masked[b] = im->masked[b];
+    return CEL_OK;
+}
+
+// the entry points that have not been taught about a mask refuse a masked set, before they launch anything
+static int refuse_masked(const cel_images *im, const char *who) {
+    if (!im->any_masked) return CEL_OK;
+    int64_t n = 0;
+    for (int b = 0; b < im->B; b++) n += im->masked[b];
+    return fail(CEL_ERR_INVALID, "%s: the image set holds %lld masked pixels (NaN counts, cel_images_set_nelec) and this call does not honour a mask",
+                who, (long long)n);
 }
 
 int cel_images_set_epsilon(cel_images *im, int band, double eps) {
@@ -1138,6 +1167,7 @@ struct RenderPlan {
     int parts, parts_used;          // blocks per tile launched; what the image vouches for (0: the star-tile kernel's bits)
     int tile_order;
     bool bin_direct;
+    bool masked_ll;                 // a masked set's log-likelihood: the render without its Poisson term, then k_masked_ll (k_mask.h)
 };
 
 static int plan_render(const cel_images *im, const cel_sources *src, int flags, const double *lambda_out, RenderPlan &p) {
@@ -1146,6 +1176,10 @@ static int plan_render(const cel_images *im, const cel_sources *src, int flags, 
     const int T = im->B * im->ntx * im->nty;
     p.keep_lists = (flags & CEL_RENDER_KEEP_LISTS) != 0;
     p.flags = flags &= ~CEL_RENDER_KEEP_LISTS;
+    // a MASKED set: the kernel this render would have chosen anyway renders the model image; the Poisson term is a pass of its
+    // own over the STORED image (CEL_RENDER_NO_STORE stores anyway: the same values, bit for bit)
+    p.masked_ll = im->any_masked && (flags & CEL_RENDER_LOGLIK) && !lambda_out;
+    if (p.masked_ll) p.flags = flags &= ~CEL_RENDER_NO_STORE;
     // the rows this image set OWNS (cel_images_set_noise_rows; default: all): the log-likelihood adds their tiles only
     p.own_rows = im->noise_y0 > 0 || im->noise_y1 < im->H;
     p.own_ty0 = 0; p.own_ty1 = im->nty;
@@ -1174,7 +1208,8 @@ static int plan_render(const cel_images *im, const cel_sources *src, int flags, 
                     im->lambda_gen != 0 && im->lambda_uid == src->uid && im->lambda_T == c->render_T && im->lambda_parts == 1 && im->lambda_gen != src->gen &&
                     im->lambda_gen >= src->full_gen &&
                     im->lists_gen == im->lambda_gen && im->recs_gen == im->lambda_gen && (int64_t)src->row_gen.size() == S &&
-                    (!(flags & CEL_RENDER_LOGLIK) || (im->partials_gen == im->lambda_gen && !im->nelec_shared));
+                    (!(flags & CEL_RENDER_LOGLIK) || p.masked_ll || (im->partials_gen == im->lambda_gen && !im->nelec_shared));
+    // (masked: the dirty tiles' PIXELS are rendered incrementally, every tile's partial is formed again -- no partials are kept)
     p.tile_order = tile_order_of(c, im);
     // a small catalogue is binned by one wave per tile into per-tile segments of S entries (k_bin_direct)
     p.bin_direct = S > 0 && S <= BIN_DIRECT_MAX_S && (int64_t)T * S <= ((int64_t)1 << 25);
@@ -1219,6 +1254,19 @@ static void launch_render(cel_ctx *c, const cel_images *im, const RenderPlan &p,
         LAUNCH_EV((k_render<32>), dim3(T), dim3(64), st, e0, e1, a);
 }
 
+// a masked set's Poisson term: one partial per render tile from the stored image (k_mask.h), added by k_reduce in its fixed order
+static void launch_masked_ll(cel_ctx *c, cel_images *im, const RenderPlan &p) {
+    const int T = im->B * im->ntx * im->nty;
+    int pi = prof_slot(c, CEL_K_MASKED_LL);
+    LAUNCH_EV(k_masked_ll, dim3(T), dim3(64), c->stream, EV0(c, pi), EV1(c, pi), (const double *)im->d_nelec, (const double *)im->d_lambda,
+              im->H, im->W, im->TW, im->TH, im->ntx, im->nty, im->d_partials.get());
+    pi = prof_slot(c, CEL_K_REDUCE);
+    LAUNCH_EV(k_reduce, dim3(im->B), dim3(256), c->stream, EV0(c, pi), EV1(c, pi), (const double *)im->d_partials, im->ntx * im->nty, im->d_llband.get(),
+              im->ntx, p.own_ty0, p.own_ty1);
+    im->llband_on_host = false;
+    im->partials_gen = 0;           // (nothing vouches for these partials between renders: a masked render forms every one again)
+}
+
 // the bands' sums in the mailbox, handed to the caller
 static void ll_from_mailbox(const cel_ctx *c, int B, double *ll_band, double *ll_total) {
     double tot = 0.0;
@@ -1248,8 +1296,14 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
     flags = plan.flags;
     if (plan.small_stars) {
         bool done = false;
-        if ((rc = render_small_stars(im, src, flags, &done))) return rc;
+        if ((rc = render_small_stars(im, src, plan.masked_ll ? (flags & ~CEL_RENDER_LOGLIK) : flags, &done))) return rc;
         if (done) {
+            if (plan.masked_ll) {
+                launch_masked_ll(c, im, plan);
+                HIP_TRY(hipMemcpyAsync(c->mail->ll_band, im->d_llband, sizeof(double) * im->B, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipStreamSynchronize(st));
+            }
             if (flags & CEL_RENDER_LOGLIK) ll_from_mailbox(c, im->B, ll_band, ll_total);
             return CEL_OK;
         }
@@ -1336,7 +1390,7 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         a.tile_nstar = im->d_tile_nstar;
         a.tile_off = im->d_tile_off; a.nelec = im->d_nelec; a.lambda = lambda_out ? lambda_out : im->d_lambda; a.partials = im->d_partials;
         a.S = S; a.capacity = im->d_lists.cap; a.B = im->B; a.H = im->H; a.W = im->W; a.ntx = im->ntx; a.nty = im->nty;
-        a.flags = flags | (c->debug << 8); a.variant = c->variant; a.tail_T = c->render_T; a.order = tile_order ? im->d_order : nullptr;
+        a.flags = (plan.masked_ll ? (flags & ~CEL_RENDER_LOGLIK) : flags) | (c->debug << 8); a.variant = c->variant; a.tail_T = c->render_T; a.order = tile_order ? im->d_order : nullptr;
         a.timing = nullptr;
         a.dirty = incr ? im->d_dirty : nullptr;
         a.cost = (im->TW == HW_TW || im->TW == QW_TW) ? im->d_tile_cost : nullptr;
@@ -1356,7 +1410,8 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         }
         pi = prof_slot(c, plan.stars_only ? CEL_K_RENDER_STARS : CEL_K_RENDER);
         launch_render(c, im, plan, T, a, EV0(c, pi), EV1(c, pi));
-        if (flags & CEL_RENDER_LOGLIK) {
+        if (plan.masked_ll) launch_masked_ll(c, im, plan);
+        else if (flags & CEL_RENDER_LOGLIK) {
             pi = prof_slot(c, CEL_K_REDUCE);
             LAUNCH_EV(k_reduce, dim3(im->B), dim3(256), st, EV0(c, pi), EV1(c, pi), (const double *)im->d_partials, im->ntx * im->nty, im->d_llband,
                       im->ntx, plan.own_ty0, plan.own_ty1);
@@ -1396,7 +1451,7 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
                 im->lambda_parts = diag ? 0 : plan.parts_used;
                 // (a render WITHOUT the log-likelihood vouches for no partials: those in the buffer may be of another sky
                 // level or drop threshold although the catalogue's generation is the same -- found by tools/dbg/incremental_stress.py)
-                im->partials_gen = (flags & CEL_RENDER_LOGLIK) ? src->gen : 0;
+                im->partials_gen = ((flags & CEL_RENDER_LOGLIK) && !plan.masked_ll) ? src->gen : 0;
             }
             if (incr) im->last_dirty = -2;          // (counted on request: cel_debug_last_render)
             break;
@@ -1583,6 +1638,7 @@ int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owne
                     (long long)NB, (long long)im->samp_S);
     if (NB < 1 || (NB > 1 && !owner)) return fail(CEL_ERR_INVALID, "cel_patch_loglik: NB patch sets need an owner array");
     if (resident && mode == 1 && !im->have_nelec) return fail(CEL_ERR_INVALID, "the isolated form needs cel_images_set_nelec");
+    if (mode == 1) { int rm = refuse_masked(im, "cel_patch_loglik (isolated form)"); if (rm) return rm; }
     cel_ctx *c = im->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const int B = im->B;
@@ -1813,6 +1869,7 @@ int cel_flux_conditionals(cel_images *im, cel_sources *src, uint64_t seed, doubl
                           const double *calib, const double *kappa, double *flux_new, int32_t *active) {
     if (!im || !src || !band_letter || !calib || !kappa || !flux_new || !active) return fail(CEL_ERR_INVALID, "cel_flux_conditionals: null argument");
     if (src->B != im->B || src->ctx != im->ctx) return fail(CEL_ERR_INVALID, "sources do not match images");
+    { int rm = refuse_masked(im, "cel_flux_conditionals"); if (rm) return rm; }
     if (im->samp_S <= 0 || im->samp_S != src->S || !im->ssum_valid)
         return fail(CEL_ERR_INVALID, "cel_flux_conditionals needs a resident photon split of these %lld sources (have %lld)",
                     (long long)src->S, (long long)im->samp_S);
@@ -1920,6 +1977,7 @@ static void launch_resident_ll(cel_ctx *c, cel_images *im, int64_t P, const int 
 int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_ids, double sigma, uint64_t seed,
                         int max_rounds, double *radec_out, double *llh_out, int64_t *stats) {
     if (!im || !src) return fail(CEL_ERR_INVALID, "cel_slice_locations: null argument");
+    { int rm = refuse_masked(im, "cel_slice_locations"); if (rm) return rm; }
     if (src->B != im->B || src->ctx != im->ctx) return fail(CEL_ERR_INVALID, "sources do not match images");
     if (im->samp_S <= 0 || im->samp_S != src->S)
         return fail(CEL_ERR_INVALID, "cel_slice_locations needs a resident photon split of these %lld sources (have %lld)",
@@ -2183,6 +2241,7 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
                      int step_out, int max_steps_out, double sigma, double phi_max, uint64_t seed, int max_rounds,
                      double *x_out, double *llh_out, int64_t *stats) {
     if (!im || !src) return fail(CEL_ERR_INVALID, "cel_slice_sample: null argument");
+    { int rm = refuse_masked(im, "cel_slice_sample"); if (rm) return rm; }
     if (src->B != im->B || src->ctx != im->ctx) return fail(CEL_ERR_INVALID, "sources do not match images");
     if (im->samp_S <= 0 || im->samp_S != src->S)
         return fail(CEL_ERR_INVALID, "cel_slice_sample needs a resident photon split of these %lld sources (have %lld)",
@@ -2353,6 +2412,7 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
     const bool resident = (offsets == nullptr);
     if (!resident && !samp) return fail(CEL_ERR_INVALID, "cel_photon_split: offsets given without an output buffer");
     if (!im->have_nelec) return fail(CEL_ERR_INVALID, "cel_photon_split needs cel_images_set_nelec first");
+    { int rm = refuse_masked(im, "cel_photon_split"); if (rm) return rm; }
     if (im->TW * im->TH != 2048) return fail(CEL_ERR_INVALID, "cel_photon_split needs 2048-pixel render tiles");
     cel_ctx *c = im->ctx;
     if (src->ctx != im->ctx || src->B != im->B) return fail(CEL_ERR_INVALID, "sources do not match images");
@@ -2638,8 +2698,9 @@ int cel_estep_stats(cel_images *im, cel_sources *src, double *xtilde, double *ma
             (rc = scratch_get(c, SCR_TMP_B, sizeof(double) * S * B, (void **)&d_m))) return rc;
         if (tiles && (rc = scratch_get(c, SCR_TMP_C, sizeof(double) * 2 * (size_t)im->d_lists.cap, (void **)&d_part))) return rc;
         int pi = prof_begin(c, CEL_K_ESTEP);
+        const bool masked = im->any_masked;     // the masked twins (k_estep.h): an unmasked set takes the kernels it always took
         if (c->variant == 0)
-            hipLaunchKernelGGL(k_estep_src, dim3((unsigned)(S * B)), dim3(256), 0, c->stream, im->d_bands, B, im->H, im->W,
+            hipLaunchKernelGGL((masked ? k_estep_src_masked : k_estep_src), dim3((unsigned)(S * B)), dim3(256), 0, c->stream, im->d_bands, B, im->H, im->W,
                                S, im->d_recs, im->d_nelec, im->d_lambda, d_x, d_m);
         else if (tiles) {
             // walk the render tiles: nelec / lambda are read once, every list entry gets its pair of sums,
@@ -2650,19 +2711,19 @@ int cel_estep_stats(cel_images *im, cel_sources *src, double *xtilde, double *ma
             ea.nelec = im->d_nelec; ea.lambda = im->d_lambda; ea.partial = d_part; ea.noise_partial = im->d_partials;
             ea.S = S; ea.capacity = im->d_lists.cap; ea.B = B; ea.H = im->H; ea.W = im->W; ea.ntx = im->ntx; ea.nty = im->nty;
             ea.tail_T = c->tail_T;
-            hipLaunchKernelGGL(k_estep_tiles, dim3((unsigned)(B * nblk)), dim3(64), 0, c->stream, ea);
+            hipLaunchKernelGGL((masked ? k_estep_tiles_masked : k_estep_tiles), dim3((unsigned)(B * nblk)), dim3(64), 0, c->stream, ea);
             hipLaunchKernelGGL(k_estep_gather, dim3((unsigned)((S * B + 255) / 256)), dim3(256), 0, c->stream, im->d_boxes, im->d_kind,
                                S, B, im->ntx, im->nty, im->d_tile_cnt, im->d_tile_nstar, im->d_tile_off, im->d_lists, im->d_lists.cap,
                                d_part, d_x, d_m);
         } else
-            hipLaunchKernelGGL(k_estep_src_hw, dim3((unsigned)(S * B)), dim3(64), 0, c->stream, im->d_bands, B, im->H, im->W,
+            hipLaunchKernelGGL((masked ? k_estep_src_hw_masked : k_estep_src_hw), dim3((unsigned)(S * B)), dim3(64), 0, c->stream, im->d_bands, B, im->H, im->W,
                                S, im->d_recs, im->d_nelec, im->d_lambda, c->tail_T, d_x, d_m);
         prof_end(c, pi);
         HIP_TRY(hipMemcpyAsync(hx.data(), d_x, sizeof(double) * S * B, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(hm.data(), d_m, sizeof(double) * S * B, hipMemcpyDeviceToHost, c->stream));
     }
     if (!tiles)      // the tile walk has left the sky term's per-tile sums in d_partials
-        hipLaunchKernelGGL(k_estep_noise, dim3(B * nblk), dim3(256), 0, c->stream, im->d_bands, (int64_t)im->H * im->W, nblk,
+        hipLaunchKernelGGL((im->any_masked ? k_estep_noise_masked : k_estep_noise), dim3(B * nblk), dim3(256), 0, c->stream, im->d_bands, (int64_t)im->H * im->W, nblk,
                            im->d_nelec, im->d_lambda, im->d_partials);
     hipLaunchKernelGGL(k_reduce, dim3(B), dim3(256), 0, c->stream, im->d_partials, nblk, im->d_llband, nblk, 0, 1);
     HIP_TRY(hipMemcpyAsync(c->mail->ll_band, im->d_llband, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
@@ -2701,7 +2762,7 @@ int cel_loglik_grad(cel_images *im, cel_sources *src, double *ll_total, double *
             o_counts = g_counts ? d_out + 6 * S : nullptr;
         }
         int pi = prof_begin(c, CEL_K_GRAD);
-        hipLaunchKernelGGL(k_grad_src, dim3((unsigned)(S * B)), dim3(64), 0, c->stream, im->d_bands, B, im->H, im->W, S,
+        hipLaunchKernelGGL((im->any_masked ? k_grad_src_masked : k_grad_src), dim3((unsigned)(S * B)), dim3(64), 0, c->stream, im->d_bands, B, im->H, im->W, S,
                            im->d_recs, im->d_nelec, im->d_lambda, c->tail_T, d_sums);
         hipLaunchKernelGGL(k_grad_chain, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, c->stream, im->d_bands, B, S,
                            im->d_recs, src->d_type, src->d_shape, src->d_counts, d_sums, o_radec, o_counts, o_shape);

@@ -17,10 +17,12 @@
 #pragma once
 #include "hw_source.h"
 
-__global__ void __launch_bounds__(256)
-k_estep_src(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, const SrcRec *__restrict__ recs,
-            const double *__restrict__ nelec, const double *__restrict__ lambda,
-            double *__restrict__ xt /* S*B */, double *__restrict__ mass /* S*B */) {
+// MASKED (a masked image set: a NaN count marks a pixel that was not observed), in all three forms: the quotient nelec / lambda
+// is 0 at a masked pixel, the sky term likewise, and the mass is the unit stamp's sum over the UNMASKED pixels of the box
+template <bool MASKED>
+__device__ __forceinline__ void estep_src_body(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, const SrcRec *__restrict__ recs,
+                                               const double *__restrict__ nelec, const double *__restrict__ lambda,
+                                               double *__restrict__ xt /* S*B */, double *__restrict__ mass /* S*B */) {
     __shared__ CompTab T;
     __shared__ double red[256], red2[256];
     const int tid = threadIdx.x;
@@ -50,8 +52,11 @@ k_estep_src(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, c
         int yy = i / nx, xx = i - yy * nx;
         double u = eval_direct(T, 0, K, (double)(x0 + xx), (double)(y0 + yy), 1.0);
         int64_t idx = plane + (int64_t)(y0 + yy) * W + (x0 + xx);
-        a += nelec[idx] * (counts * u) / lambda[idx];
-        m += u;
+        const double ne = nelec[idx];
+        if (!MASKED || ne == ne) {
+            a += ne * (counts * u) / lambda[idx];
+            m += u;
+        }
     }
     red[tid] = a; red2[tid] = m;
     __syncthreads();
@@ -62,10 +67,23 @@ k_estep_src(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, c
     if (tid == 0) { xt[job] = red[0]; mass[job] = red2[0]; }
 }
 
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
-k_estep_src_hw(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, const SrcRec *__restrict__ recs,
-               const double *__restrict__ nelec, const double *__restrict__ lambda, double Tdrop,
-               double *__restrict__ xt /* S*B */, double *__restrict__ mass /* S*B */) {
+__global__ void __launch_bounds__(256)
+k_estep_src(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, const SrcRec *__restrict__ recs,
+            const double *__restrict__ nelec, const double *__restrict__ lambda,
+            double *__restrict__ xt /* S*B */, double *__restrict__ mass /* S*B */) {
+    estep_src_body<false>(bands, B, H, W, S, recs, nelec, lambda, xt, mass);
+}
+__global__ void __launch_bounds__(256)
+k_estep_src_masked(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, const SrcRec *__restrict__ recs,
+                   const double *__restrict__ nelec, const double *__restrict__ lambda,
+                   double *__restrict__ xt /* S*B */, double *__restrict__ mass /* S*B */) {
+    estep_src_body<true>(bands, B, H, W, S, recs, nelec, lambda, xt, mass);
+}
+
+template <bool MASKED>
+__device__ __forceinline__ void estep_src_hw_body(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, const SrcRec *__restrict__ recs,
+                                                  const double *__restrict__ nelec, const double *__restrict__ lambda, double Tdrop,
+                                                  double *__restrict__ xt /* S*B */, double *__restrict__ mass /* S*B */) {
     __shared__ double acc[HW_TH * HW_TW];
     __shared__ CompTab T;
     __shared__ double et[64];
@@ -109,7 +127,7 @@ k_estep_src_hw(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S
                 }
 #pragma unroll
                 for (int r = 0; r < 8; r++) {
-                    if (on && 2 * (r0 + r) + half < rb) {
+                    if (on && 2 * (r0 + r) + half < rb && (!MASKED || ne[r] == ne[r])) {
                         const double u = acc[(r0 + r) * 64 + lane];
                         a += ne[r] * (counts * u) / la[r];
                         m += u;
@@ -124,10 +142,23 @@ k_estep_src_hw(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S
     if (lane == 0) { xt[job] = a; mass[job] = m; }
 }
 
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
+k_estep_src_hw(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, const SrcRec *__restrict__ recs,
+               const double *__restrict__ nelec, const double *__restrict__ lambda, double Tdrop,
+               double *__restrict__ xt /* S*B */, double *__restrict__ mass /* S*B */) {
+    estep_src_hw_body<false>(bands, B, H, W, S, recs, nelec, lambda, Tdrop, xt, mass);
+}
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
+k_estep_src_hw_masked(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, const SrcRec *__restrict__ recs,
+                      const double *__restrict__ nelec, const double *__restrict__ lambda, double Tdrop,
+                      double *__restrict__ xt /* S*B */, double *__restrict__ mass /* S*B */) {
+    estep_src_hw_body<true>(bands, B, H, W, S, recs, nelec, lambda, Tdrop, xt, mass);
+}
+
 // sky responsibility: partial[b][blk] = sum over the block's pixel chunk of nelec * eps / lambda
-__global__ void __launch_bounds__(256)
-k_estep_noise(const BandDev *__restrict__ bands, int64_t npix, int nblk, const double *__restrict__ nelec,
-              const double *__restrict__ lambda, double *__restrict__ partial) {
+template <bool MASKED>
+__device__ __forceinline__ void estep_noise_body(const BandDev *__restrict__ bands, int64_t npix, int nblk, const double *__restrict__ nelec,
+                                                 const double *__restrict__ lambda, double *__restrict__ partial) {
     __shared__ double red[256];
     const int b = blockIdx.x / nblk, blk = blockIdx.x - b * nblk;
     const double eps = bands[b].eps;
@@ -135,7 +166,10 @@ k_estep_noise(const BandDev *__restrict__ bands, int64_t npix, int nblk, const d
     const int64_t lo = chunk * blk, hi = (lo + chunk < npix) ? lo + chunk : npix;
     const double *ne = nelec + (int64_t)b * npix, *la = lambda + (int64_t)b * npix;
     double a = 0.0;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) a += ne[i] * eps / la[i];
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+        const double n = ne[i];
+        if (!MASKED || n == n) a += n * eps / la[i];
+    }
     red[threadIdx.x] = a;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
@@ -143,6 +177,16 @@ k_estep_noise(const BandDev *__restrict__ bands, int64_t npix, int nblk, const d
         __syncthreads();
     }
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+__global__ void __launch_bounds__(256)
+k_estep_noise(const BandDev *__restrict__ bands, int64_t npix, int nblk, const double *__restrict__ nelec,
+              const double *__restrict__ lambda, double *__restrict__ partial) {
+    estep_noise_body<false>(bands, npix, nblk, nelec, lambda, partial);
+}
+__global__ void __launch_bounds__(256)
+k_estep_noise_masked(const BandDev *__restrict__ bands, int64_t npix, int nblk, const double *__restrict__ nelec,
+                     const double *__restrict__ lambda, double *__restrict__ partial) {
+    estep_noise_body<true>(bands, npix, nblk, nelec, lambda, partial);
 }
 
 // ---- the same reductions, walking TILES (round 2) ---------------------------------------------------
@@ -170,8 +214,8 @@ struct EstepArgs {
     double tail_T;
 };
 
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
-k_estep_tiles(EstepArgs a) {
+template <bool MASKED>
+__device__ __forceinline__ void estep_tiles_body(const EstepArgs &a) {
     __shared__ double acc[HW_TH * HW_TW];
     __shared__ CompTab T;
     __shared__ double et[64];
@@ -197,6 +241,10 @@ k_estep_tiles(EstepArgs a) {
 #define ESTEP_W(r) w[r]
 #endif
     double noise = 0.0;
+    // MASKED: a 32-bit mask word per lane beside its 32 quotients, bit r = the lane's pixel of row pair r was observed.  It
+    // waits in LDS (256 B) and is read once per source, behind the walk: no register is held across hw_build / hw_walk
+    __shared__ unsigned seen_l[MASKED ? 64 : 1];
+    unsigned seen = 0xffffffffu;
     {
         const int64_t base = (int64_t)b * a.H * a.W + (int64_t)(Y0 + half) * a.W + xi;
         double ne[HW_TH / 2], la[HW_TH / 2];
@@ -206,12 +254,21 @@ k_estep_tiles(EstepArgs a) {
             ne[r] = in ? a.nelec[base + (int64_t)(2 * r) * a.W] : 0.0;
             la[r] = in ? a.lambda[base + (int64_t)(2 * r) * a.W] : 1.0;
         }
+        if (MASKED) {       // a masked pixel: its bit, and a count of 0 from here on -- the sums below are then those of 0 counts there
+#pragma unroll
+            for (int r = 0; r < HW_TH / 2; r++) {
+                const bool ok = ne[r] == ne[r];
+                seen = ok ? seen : seen & ~(1u << r);
+                ne[r] = ok ? ne[r] : 0.0;
+            }
+        }
 #pragma unroll
         for (int r = 0; r < HW_TH / 2; r++) {
             ESTEP_W(r) = ne[r] / la[r];
             noise += ne[r] * eps / la[r];
         }
     }
+    if (MASKED) seen_l[lane] = seen;     // (every later read is the lane's own word, behind a barrier)
     noise = wave_sum(noise);
     if (lane == 0) a.noise_partial[tile] = noise;
     const int cnt = a.tile_cnt[tile];
@@ -243,6 +300,17 @@ k_estep_tiles(EstepArgs a) {
         hw_walk(T, et, Kk, (double)xi, Y0, ra, rb, on, direct, acc, lane);
         __syncthreads();
         double xt = 0.0, ms = 0.0;
+        if (MASKED) {
+            // the stamp's masked pixels leave the LDS tile before the sums: the reduction below is then the unmasked kernel's own
+            // (fma(0, 0, xt) = xt, ms + 0 = ms).  A loop over the lane's set bits -- masked pixels are few -- and not 32 bit tests
+            // in the unrolled loop: those, loop-invariant, are hoisted out of the source loop into 32 lane masks and spill
+            // (30 VGPR spills where the unmasked kernel has 14).  A lane touches its own pixels only.
+            unsigned miss = ~seen_l[lane];
+            while (miss) {
+                acc[(__ffs(miss) - 1) * 64 + lane] = 0.0;
+                miss &= miss - 1u;
+            }
+        }
 #pragma unroll
         for (int r = 0; r < HW_TH / 2; r++) {               // static indices: w[] stays in registers
             if (2 * r + 1 >= ra && 2 * r < rb) {            // (wave-uniform) the row pair meets the box
@@ -260,6 +328,12 @@ k_estep_tiles(EstepArgs a) {
         }
     }
 }
+
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
+k_estep_tiles(EstepArgs a) { estep_tiles_body<false>(a); }
+// ... on a masked image set: a 32-bit per-lane mask word beside the 32 quotients
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
+k_estep_tiles_masked(EstepArgs a) { estep_tiles_body<true>(a); }
 
 __global__ void __launch_bounds__(256)
 k_estep_gather(const int4 *__restrict__ boxes /* B*S: x0, x1, y0, y1 */, const int *__restrict__ kind, int64_t S, int B, int ntx,

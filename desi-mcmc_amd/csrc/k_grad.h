@@ -30,7 +30,8 @@
 #define GRAD_NS 8      // doubles per (source, band) of k_grad_src's output: S_u, S_m (2), S_W (3), S_th, 0
 
 // one wave per (source, band), job = s * B + b; the component table in LDS, the box's pixels strided over the lanes
-template <bool GAL>
+// MASKED (a masked image set, k_grad_src_masked): a NaN count marks a pixel that was not observed -- r = 0 there
+template <bool GAL, bool MASKED = false>
 __device__ __forceinline__ void grad_box(const double *__restrict__ tA, const double *__restrict__ tB,
                                          const double *__restrict__ tmx, const double *__restrict__ tmy,
                                          const double *__restrict__ tqa, const double *__restrict__ tqb,
@@ -62,7 +63,8 @@ __device__ __forceinline__ void grad_box(const double *__restrict__ tA, const do
             }
         }
         const int64_t idx = (int64_t)(y0 + yy) * W + (x0 + xx);
-        const double r = ne_p[idx] / la_p[idx] - 1.0;
+        const double ne = ne_p[idx], la = la_p[idx];
+        const double r = (!MASKED || ne == ne) ? ne / la - 1.0 : 0.0;
         acc[0] = fma(r, u, acc[0]);
         acc[1] = fma(r, m0, acc[1]);
         acc[2] = fma(r, m1, acc[2]);
@@ -75,10 +77,10 @@ __device__ __forceinline__ void grad_box(const double *__restrict__ tA, const do
     }
 }
 
-__global__ void __launch_bounds__(64)
-k_grad_src(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, const SrcRec *__restrict__ recs,
-           const double *__restrict__ nelec, const double *__restrict__ lambda, double tail_T,
-           double *__restrict__ sums /* S*B*GRAD_NS */) {
+template <bool MASKED>
+__device__ __forceinline__ void grad_src_body(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, const SrcRec *__restrict__ recs,
+                                              const double *__restrict__ nelec, const double *__restrict__ lambda, double tail_T,
+                                              double *__restrict__ sums /* S*B*GRAD_NS */) {
     __shared__ double tA[K_GAL], tB[K_GAL], tmx[K_GAL], tmy[K_GAL], tqa[K_GAL], tqb[K_GAL], tqc[K_GAL], tvar[K_GAL], tT[K_GAL];
     const int lane = threadIdx.x;
     const int64_t job = blockIdx.x;
@@ -125,9 +127,9 @@ k_grad_src(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, co
     double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     const int64_t plane = (int64_t)b * H * W;
     if (gal)
-        grad_box<true>(tA, tB, tmx, tmy, tqa, tqb, tqc, tvar, tT, K, x0, y0, nx, nx * ny, nelec + plane, lambda + plane, W, lane, acc);
+        grad_box<true, MASKED>(tA, tB, tmx, tmy, tqa, tqb, tqc, tvar, tT, K, x0, y0, nx, nx * ny, nelec + plane, lambda + plane, W, lane, acc);
     else
-        grad_box<false>(tA, tB, tmx, tmy, tqa, tqb, tqc, tvar, tT, K, x0, y0, nx, nx * ny, nelec + plane, lambda + plane, W, lane, acc);
+        grad_box<false, MASKED>(tA, tB, tmx, tmy, tqa, tqb, tqc, tvar, tT, K, x0, y0, nx, nx * ny, nelec + plane, lambda + plane, W, lane, acc);
 #pragma unroll
     for (int i = 0; i < 7; i++) acc[i] = wave_sum(acc[i]);
     if (lane == 0) {
@@ -135,6 +137,21 @@ k_grad_src(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, co
         for (int i = 0; i < 7; i++) out[i] = acc[i];
         out[7] = 0.0;
     }
+}
+
+__global__ void __launch_bounds__(64)
+k_grad_src(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, const SrcRec *__restrict__ recs,
+           const double *__restrict__ nelec, const double *__restrict__ lambda, double tail_T,
+           double *__restrict__ sums /* S*B*GRAD_NS */) {
+    grad_src_body<false>(bands, B, H, W, S, recs, nelec, lambda, tail_T, sums);
+}
+
+// the same sums on a masked image set: r(p) = 0 where nelec is NaN, nothing else differs
+__global__ void __launch_bounds__(64)
+k_grad_src_masked(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, const SrcRec *__restrict__ recs,
+                  const double *__restrict__ nelec, const double *__restrict__ lambda, double tail_T,
+                  double *__restrict__ sums /* S*B*GRAD_NS */) {
+    grad_src_body<true>(bands, B, H, W, S, recs, nelec, lambda, tail_T, sums);
 }
 
 // ---- chain rule to the public coordinates, one thread per source --------------------------------------------------------

@@ -469,14 +469,17 @@ k_binomial_draws(long long n, double p, unsigned long long seed, int64_t N, long
     out[i] = binomial_draw(n, p, g, et, lt);
 }
 
-// smallest / largest value of the observed image (and whether it holds a NaN), per block: the host finishes the
-// reduction.  Decides the photon split's instantiation (TL above).
+// smallest / largest value of a band's observed pixels and how many of them are NaN (masked), per block; block blk works on
+// band blk / nbb.  The host finishes the reduction: the range decides the photon split's instantiation (TL above), the
+// per-band counts are cel_images_mask_info's.
 __global__ void __launch_bounds__(256)
-k_nelec_range(const double *__restrict__ x, int64_t n, double *__restrict__ out /* 3 per block: min, max, nan count */) {
+k_nelec_range(const double *__restrict__ x, int64_t npix /* per band */, int nbb, double *__restrict__ out /* 3 per block: min, max, nan count */) {
     __shared__ double slo[256], shi[256], snan[256];
+    const int b = blockIdx.x / nbb, blk = blockIdx.x - b * nbb;
+    const double *xb = x + (int64_t)b * npix;
     double lo = INFINITY, hi = -INFINITY, bad = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const double v = x[i];
+    for (int64_t i = (int64_t)blk * 256 + threadIdx.x; i < npix; i += (int64_t)nbb * 256) {
+        const double v = xb[i];
         if (v == v) { lo = fmin(lo, v); hi = fmax(hi, v); } else bad += 1.0;
     }
     slo[threadIdx.x] = lo; shi[threadIdx.x] = hi; snan[threadIdx.x] = bad;

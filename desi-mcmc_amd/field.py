@@ -202,11 +202,33 @@ class ImageSet(object):
         self._finalizer()
         self._h = C.c_void_p(None)
 
-    def set_nelec(self, nelec):
+    def set_nelec(self, nelec, invvar=None):
+        """the observed counts (B, H, W).  A NaN count marks a MASKED pixel -- one that was not observed and contributes to no
+        sum of render(loglik=True), loglik_grad and estep_stats; a negative count is data.  invvar (same shape): NaN is written
+        where invvar == 0 before the upload (FitsImage.invvar: saturated cores, cosmic-ray hits, interpolated columns)."""
         nelec = L.f64(nelec)
         if nelec.size != self.B * self.H * self.W:
             raise ValueError("nelec must have B*H*W = %d elements" % (self.B * self.H * self.W))
+        if invvar is not None:
+            invvar = np.asarray(invvar)
+            if invvar.size != nelec.size:
+                raise ValueError("invvar must have as many elements as nelec")
+            nelec = np.where(invvar.reshape(nelec.shape) == 0, np.nan, nelec)
         L.check(L.lib().cel_images_set_nelec(self._h, nelec.ctypes.data, L.CEL_HOST))
+
+    @property
+    def masked(self):
+        """masked (NaN) pixels per band that the last set_nelec found -> int64[B]  (cel_images_mask_info)"""
+        out = np.zeros(self.B, dtype=np.int64)
+        L.check(L.lib().cel_images_mask_info(self._h, out.ctypes.data_as(L.c_int64_p)))
+        return out
+
+    def _refuse_masked(self, who):
+        """the calls that do not honour a mask refuse a masked set before any device call (the library refuses them as well)"""
+        n = int(self.masked.sum())
+        if n:
+            raise L.MaskedImagesError("%s: the image set holds %d masked pixels (NaN counts) and this call does not honour a mask"
+                                      % (who, n))
 
     def set_nelec_device(self, ptr):
         L.check(L.lib().cel_images_set_nelec(self._h, C.c_void_p(ptr), L.CEL_DEVICE))
@@ -315,6 +337,7 @@ class ImageSet(object):
     def photon_split(self, sources, seed):
         """Gibbs photon split (celeste_sample_sources.pyx:61-156) for every band.
         -> (patches[b][s] 2-D arrays or None, boxes[B,S,4], noise_sum[B])"""
+        self._refuse_masked("photon_split")
         S = sources.S
         boxes, status = self.source_boxes(sources)
         area = np.where(status > 0, (boxes[..., 1] - boxes[..., 0]).astype(np.int64) * (boxes[..., 3] - boxes[..., 2]), 0)
@@ -341,6 +364,7 @@ class ImageSet(object):
     def photon_split_resident(self, sources, seed):
         """The photon split with the sample patches kept in device memory as int32 (1.6 GB at 10 000
         sources x 5 bands x 2048^2 never leave the GPU).  -> noise_sum[B]"""
+        self._refuse_masked("photon_split_resident")
         noise = np.zeros(self.B)
         L.check(L.lib().cel_photon_split(self._h, sources._h, C.c_uint64(int(seed) & (2 ** 64 - 1)), None, None,
                                          L.CEL_DEVICE, L.dptr(noise)))
@@ -350,6 +374,8 @@ class ImageSet(object):
         """Conditional log-likelihoods of proposals against the resident sample patches
         (isolated=True: against the observed image on the same boxes).  owner[p] = index of the
         source (of the split) that proposal p belongs to.  -> ll[P]"""
+        if isolated:
+            self._refuse_masked("patch_loglik_resident(isolated=True)")
         owner = np.ascontiguousarray(owner, dtype=np.int32)
         if owner.shape != (proposals.S,):
             raise ValueError("owner must have one entry per proposal")
@@ -514,6 +540,8 @@ class ImageSet(object):
         boxes: (B,4) int y0,y1,x0,x1 (empty box = band without a sample image);
         patches: list of B arrays (or None) of the box shapes.  -> ll[P]
         (Source.log_likelihood / log_likelihood_isolated, sources.py:134-237)"""
+        if (isolated and mode is None) or mode == 1:
+            self._refuse_masked("patch_loglik(isolated=True)")
         boxes = np.ascontiguousarray(boxes, dtype=np.int32).reshape(self.B, 4)
         offs = np.zeros(self.B + 1, dtype=np.int64)
         flat = []
@@ -559,6 +587,8 @@ class ImageSet(object):
     def patch_loglik_multi(self, sources, owner, boxes, patches, isolated=False):
         """patch_loglik for proposals of many sources at once.  owner[p]: which patch set proposal p
         is scored on; boxes (NB, B, 4); patches[set][band] arrays or None.  -> ll[P]"""
+        if isolated:
+            self._refuse_masked("patch_loglik_multi(isolated=True)")
         boxes = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, self.B, 4)
         NB = boxes.shape[0]
         owner = np.ascontiguousarray(owner, dtype=np.int32)

@@ -52,11 +52,20 @@ class FitsImage(object):
     """One band image.  Build with FitsImage.from_header(...) / from_file(...) / from_record(...)."""
 
     def __init__(self, band, nelec, epsilon, kappa, calib, weights, means, covars, rho_n, phi_n, Ups_n,
-                 darkvar=None, header=None):
+                 darkvar=None, header=None, invvar=None, mask_invvar=False):
         self.band = band
         self.header = header
         self.nelec = np.array(nelec, dtype=np.float64)
         self.nelec.flags.writeable = False               # fits_image.py:96
+        # the inverse variance of every pixel, 0 where the pixel must not be scored (fits_image.py:73, kept as given).
+        # mask_invvar: upload those pixels as MASKED (`observed`), so that the field likelihood, its gradient and the E-step
+        # leave them out as the star <-> galaxy move already does (sources.py:283-291).  Off by default: celeste_likelihood
+        # ignores invvar, as the reference's does (celeste.py:237-240).  Fixed at construction -- the image-set cache holds an
+        # object's pixels immutable.
+        self.invvar = invvar
+        self.mask_invvar = bool(mask_invvar)
+        if self.mask_invvar and (invvar is None or np.shape(invvar) != self.nelec.shape):
+            raise ValueError("mask_invvar needs an invvar of the image's shape")
         self.shape = self.nelec.shape
         self.rho_n = np.asarray(rho_n, dtype=np.float64)  # CRPIX - 1        fits_image.py:99
         self.phi_n = np.asarray(phi_n, dtype=np.float64)  # CRVAL            fits_image.py:100
@@ -87,6 +96,22 @@ class FitsImage(object):
 
     psf = psf_mog
 
+    @property
+    def observed(self):
+        """the counts as the device gets them: nelec itself, or (mask_invvar) nelec with NaN where invvar == 0"""
+        if not self.mask_invvar:
+            return self.nelec
+        if getattr(self, "_observed", None) is None:
+            obs = np.where(np.asarray(self.invvar) == 0, np.nan, self.nelec)
+            obs.flags.writeable = False
+            self._observed = obs
+        return self._observed
+
+    @property
+    def n_masked(self):
+        """pixels that `observed` marks as masked (0 without mask_invvar); host arithmetic only"""
+        return int(np.count_nonzero(np.asarray(self.invvar) == 0)) if self.mask_invvar else 0
+
     # ---- constructors -------------------------------------------------------------------
     @classmethod
     def from_header(cls, band, header, img):
@@ -110,10 +135,11 @@ class FitsImage(object):
         return cls.from_header(band, hdr, img)
 
     @classmethod
-    def from_record(cls, band, rec, b, nelec):
+    def from_record(cls, band, rec, b, nelec, invvar=None, mask_invvar=False):
         """rec: dict of per-band stacked arrays with the keys of field.BAND_KEYS."""
         return cls(band, nelec, rec["eps"][b], rec["kappa"][b], rec["calib"][b], rec["weights"][b],
-                   rec["means"][b], rec["covars"][b], rec["rho"][b], rec["phi"][b], rec["ups"][b])
+                   rec["means"][b], rec["covars"][b], rec["rho"][b], rec["phi"][b], rec["ups"][b],
+                   invvar=invvar, mask_invvar=mask_invvar)
 
     # ---- the C-ABI record ------------------------------------------------------------------
     def band_record(self):

@@ -48,6 +48,9 @@ class Field(object):
             src.clear_sample_images()
         bands = list(self.img_dict.keys())
         imgs = [self.img_dict[b] for b in bands]
+        if any(getattr(im, "n_masked", 0) for im in imgs):
+            raise ValueError("Field.resample_photons: the field holds masked pixels (FitsImage(mask_invvar=True)) and the photon "
+                             "split does not honour a mask")
         same = all(im.nelec.shape == imgs[0].nelec.shape for im in imgs)
         groups = [imgs] if same and len(imgs) <= 16 else [[im] for im in imgs]
         noise_sums = {}

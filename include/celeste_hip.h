@@ -165,7 +165,8 @@ enum {
     CEL_K_SMALL_STARS = 11,/* k_small_stars: a small star field's whole step in one launch (CEL_OPT_STAR_TILES = 1) */
     CEL_K_TOTALS = 12,     /* k_strict_totals: the photon split's totals image from the model image on the device (CEL_OPT_SPLIT_REUSE) */
     CEL_K_GRAD = 13,       /* k_grad_src + k_grad_chain: cel_loglik_grad */
-    CEL_K_COUNT = 14
+    CEL_K_MASKED_LL = 14,  /* k_masked_ll: the Poisson term of a masked image set, a pass of its own behind the render */
+    CEL_K_COUNT = 15
 };
 
 typedef struct cel_ctx cel_ctx;
@@ -210,8 +211,19 @@ int cel_images_create(cel_ctx *ctx, int B, int H, int W, const cel_band *bands, 
 int cel_images_destroy(cel_images *img);
 /* nelec: B*H*W observed electron counts, FitsImage.nelec (fits_image.py:86-93); stays on device.  The call also reduces the
  * image's range on the device (one pass, synchronous): images within 0 ... 65 535 let cel_photon_split keep its photons-left
- * plane in 16 bits (a seventh wave per CU); any other image takes the 32-bit instantiation, with the same draws */
+ * plane in 16 bits (a seventh wave per CU); any other image takes the 32-bit instantiation, with the same draws.
+ * MASKED PIXELS.  A NaN count marks a pixel that was not observed (FitsImage.invvar == 0: a saturated core, a cosmic-ray hit,
+ * an interpolated column); a negative count is data.  The mask belongs to its band and there is no second plane: the NaNs in
+ * the device's nelec ARE the mask, so row windows and cel_images_device_ptrs carry it.  The same pass counts them per band
+ * (cel_images_mask_info); an image set with at least one is a MASKED set until the next cel_images_set_nelec.  On a masked
+ * set a masked pixel contributes to no sum of cel_render_field's log-likelihood, cel_loglik_grad and cel_estep_stats (see
+ * there); the calls that have not been taught about a mask -- cel_photon_split, the isolated forms of cel_patch_loglik[_multi]
+ * and, for want of a split, cel_flux_conditionals and cel_slice_* -- refuse a masked set with CEL_ERR_INVALID before they
+ * launch anything.  Everything that does not read nelec (stamps, boxes, masses, the mode 4 planes, which carry their own NaN
+ * mask) is unchanged, and a set without a NaN takes exactly the code it took before there was a mask. */
 int cel_images_set_nelec(cel_images *img, const double *nelec, int mem);
+/* masked[b] = the number of NaN (masked) pixels of band b that the last cel_images_set_nelec found (0 before the first) */
+int cel_images_mask_info(cel_images *img, int64_t *masked /* B */);
 /* Gibbs resamples the sky level (models.py:156-160) */
 int cel_images_set_epsilon(cel_images *img, int band, double eps);
 /* Declare that this image set holds rows [y0, y0 + H) of a full_H-row frame (row-strip partition
@@ -232,7 +244,9 @@ int cel_images_get_lambda(cel_images *img, double *out, int mem);
 /* raw device pointers of the library-owned B*H*W buffers (for zero-copy consumers).  Asking for `nelec` tells the library that
  * the caller may write the observed image in place: it stops assuming the range cel_images_set_nelec found (the photon split's
  * 16-bit photons-left plane) until the next cel_images_set_nelec, and from then on keeps no per-tile Poisson sums between
- * renders (CEL_OPT_INCREMENTAL renders every tile when a log-likelihood is asked for).  nelec = NULL asks for neither */
+ * renders (CEL_OPT_INCREMENTAL renders every tile when a log-likelihood is asked for).  nelec = NULL asks for neither.
+ * The mask state (cel_images_set_nelec) is taken when cel_images_set_nelec runs: a caller who writes pixels through this pointer
+ * must neither create nor remove NaNs */
 int cel_images_device_ptrs(cel_images *img, void **nelec, void **lambda);
 /* device pointer of the B per-band log-likelihoods of the LAST render with CEL_RENDER_LOGLIK (doubles, valid until the next
  * render, photon split or E-step call on this image set -- they reduce into the same buffer; the stream has been synchronised
@@ -273,7 +287,13 @@ int cel_sources_get(cel_sources *src, int32_t *type, double *radec, double *coun
  *   lambda[b] = eps_b + sum_s counts[s][b] * unit_stamp(s, b)     (kept on device)
  *   ll_band[b] = sum_{y,x} nelec*log(lambda) - lambda              (host, B doubles, may be NULL)
  *   ll_total   = sum_b ll_band[b]                                  (host, may be NULL)
- * Synchronises the stream when ll_band or ll_total is non-NULL. */
+ * Synchronises the stream when ll_band or ll_total is non-NULL.
+ * On a MASKED image set (a NaN in nelec, cel_images_set_nelec) the model image is unchanged, bit for bit, and
+ *   ll_band[b] = sum over the UNMASKED pixels of nelec*log(lambda) - lambda   (a band masked everywhere: 0)
+ * formed by a pass of its own behind the render (CEL_K_MASKED_LL); cel_images_loglik_device holds the same values.  That pass
+ * reads the stored image: CEL_RENDER_NO_STORE with CEL_RENDER_LOGLIK stores the image anyway on a masked set, and
+ * CEL_OPT_INCREMENTAL renders the dirty tiles' pixels only but forms every tile's Poisson partial again.  Either way the
+ * values are those of a full, storing render, bit for bit. */
 int cel_render_field(cel_images *img, cel_sources *src, int flags, double *ll_band, double *ll_total);
 /* work counters of the last cel_render_field: n_srcpix = sum of box areas (source-pixel
  * evaluations), n_gauss = sum of K*area, n_tile_entries = length of the tile lists */
@@ -452,7 +472,10 @@ int cel_debug_binomial(cel_ctx *ctx, int64_t n, double p, uint64_t seed, int64_t
  *   xtilde[s*B+b] = sum_pixels nelec * F_s / lambda     (celeste_em.py:85)
  *   mass[s*B+b]   = sum_pixels unit stamp of s in band b (celeste_em.py:89, before the min(1, .))
  *   noise[b]      = sum_pixels nelec * eps / lambda      (celeste_em.py:62, before the / size)
- * Renders lambda for `src` first.  Host outputs; any of them may be NULL. */
+ * Renders lambda for `src` first.  Host outputs; any of them may be NULL.
+ * On a MASKED image set (a NaN in nelec, cel_images_set_nelec) xtilde and noise run over the unmasked pixels, and
+ *   mass[s*B+b] = sum of the unit stamp over the UNMASKED pixels of the box
+ * -- the denominator the M-step needs: the light of s that the image could have recorded (0 for a box masked everywhere). */
 int cel_estep_stats(cel_images *img, cel_sources *src, double *xtilde, double *mass, double *noise);
 
 /* ---- gradient of the field log-likelihood ------------------------------------------------------ */
@@ -474,7 +497,9 @@ int cel_estep_stats(cel_images *img, cel_sources *src, double *xtilde, double *m
  * shipping defaults the render's T = 24 moves every r(p) = nelec / lambda - 1 by at most n e^-24 nelec / lambda as well: every
  * entry then stays within 1e-7 of the largest |entry| of its column of the gradient with nothing dropped (T = 0).
  * CEL_ERR_INVALID without cel_images_set_nelec and on an image set with a row window (cel_images_set_window): partitioned
- * (strip / windowed) gradients are not provided. */
+ * (strip / windowed) gradients are not provided.
+ * On a MASKED image set (a NaN in nelec, cel_images_set_nelec) r(p) = nelec / lambda - 1 at the unmasked pixels and 0 at the
+ * masked ones; ll_total is cel_render_field's masked value, bit for bit. */
 int cel_loglik_grad(cel_images *img, cel_sources *src, double *ll_total, double *g_radec, double *g_counts, double *g_shape,
                     int mem);
 
