@@ -118,26 +118,63 @@ __device__ inline void rec_group_hw(const CompTab &T, const double *__restrict__
 // phases of one recurrence, the middle one with NB + NS components per lane, the outer ones with NB.  A component is still
 // added on every row of its own range: what is left out lies below the drop level by the range's construction.  One segment
 // only (the caller checks gb - ga <= L).  Slots of a half: big p0 + half * NB + i, small p0 + 2 NB + half * NS + i.
+//
+// Two rows per step (round 7).  The one-row form g' = g r, r' = r q, s += g costs three operations per component and row.  With
+// R(y) = r(y) r(y+1) carried next to r, and the component's constants q2 = q^2 and Q = q^4, a trip over rows y and y + 1 is
+//     s0 += g;   s1 = fma(g, r, s1);   g *= R;   r *= q2;   R *= Q              (g(y+2) = g(y) R(y), R(y+2) = R(y) q^4)
+// five operations per component for two rows: g r is only ever needed inside row y + 1's sum, where the FMA takes it.  Per
+// lane and trip, N components: 5 N - 1 fp64 instructions (the first term of s1 is a plain multiply) against 6 N - 2.
+//
+// Pinned.  Written as C++ the trip gets the right 5 N - 1 instructions and, from the register allocator, up to eleven v_mov_b64
+// of the loop-carried values on top (a copy issues like any other VALU instruction: 40 per trip at N = 6 against the one-row
+// form's 35).  So each statement below is ONE instruction whose destination is tied to its first source (v_mul_f64 d, d, a;
+// v_fmac_f64 d, a, b): nothing is left to rotate, and the trip is 5 N - 1 fp64 instructions and one address add.  The statements
+// are volatile, which keeps them in the order written: component by component, a term of each sum and then the component's three
+// state multiplies, so that an instruction of a sum's chain stands four or five instructions behind the one whose result it reads
+// -- a dependent fp64 instruction issued right behind its predecessor waits for the result, and the SIMD's other wave fills only
+// some of such gaps: with the two chains alternating and the 3 N multiplies behind them (two instructions between dependents) the
+// kernel measured 0.5 % slower -- and a multiply that overwrites g or r comes after the sums have read it.
+//
+// Range.  seg_len keeps |E| <= REC_EMAX on every row of a segment for every lane whose value matters on any of its rows, so on
+// such a lane log r = E(y+1) - E(y) and log R = E(y+2) - E(y) lie within +-REC_EMAX wherever rows y .. y + 2 belong to the
+// walk: r and R are finite and normal there, and no product is taken in a wider range than the one-row form's.  A lane that
+// matters nowhere on the segment may ask for more: its r is clamped to e^+-REC_EMAX as before, and R -- r (r q), in this
+// order, since r r alone can overflow where R is finite -- to REC_RMAX = 2^981 ~ e^REC_EMAX.  A ratio clamped from above is
+// SMALLER than the true one, so what such a lane adds stays at or below its true value (below the drop level), and 0 * R is
+// 0, never 0 * inf; one clamped from below multiplies a g <= A by e^-REC_EMAX at most.  q2 and Q are <= 1: r and R only shrink from their seeds, g = A e^E <= A on every row, the rows one trip past the end
+// included (computed, never added), so nothing overflows later either.  Q = e^-4qc would underflow above qc ~ 177; a walk has
+// L >= 4, which seg_len grants only below qc ~ 79 (Q >= e^-316, normal) -- sharper pairs take the direct evaluation (L < 4).
+#define REC_RMAX 0x1p+981
+__device__ __forceinline__ void pin_add(double &d, double a, double b) { asm volatile("v_add_f64 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); }
+__device__ __forceinline__ void pin_mul(double &d, double a, double b) { asm volatile("v_mul_f64 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); }
+__device__ __forceinline__ void pin_acc(double &d, double a) { asm volatile("v_add_f64 %0, %0, %1" : "+v"(d) : "v"(a)); }
+__device__ __forceinline__ void pin_fmac(double &d, double a, double b) { asm volatile("v_fmac_f64 %0, %1, %2" : "+v"(d) : "v"(a), "v"(b)); }
+__device__ __forceinline__ void pin_scale(double &d, double a) { asm volatile("v_mul_f64 %0, %0, %1" : "+v"(d) : "v"(a)); }
+
+// rows [row, rend) of the first N components; -> a last, odd row was added and the state still stands ON it (a caller that
+// goes on with another phase advances it by one row: rec_group_nested)
 template <int N, int NT>
-__device__ __forceinline__ void rec_walk_n(double (&g)[NT], double (&r)[NT], const double (&q)[NT], int row, int rend, bool advance,
-                                           double *__restrict__ acc_col) {
+__device__ __forceinline__ bool rec_walk_n(double (&g)[NT], double (&r)[NT], double (&R)[NT], const double (&q2)[NT],
+                                           const double (&Q)[NT], int row, int rend, double *__restrict__ acc_col) {
+    static_assert(N >= 2, "the sums' chains start from two components");
     for (; row + 1 < rend; row += 2) {
-#pragma clang fp contract(off)
-        double s0 = g[0], s1, g1[N], r1[N];
+        double s0, s1;
+        pin_add(s0, g[0], g[1]);
+        pin_mul(s1, g[0], r[0]);
+        pin_scale(g[0], R[0]);
+        pin_scale(r[0], q2[0]);
+        pin_scale(R[0], Q[0]);
+        pin_fmac(s1, g[1], r[1]);
+        pin_scale(g[1], R[1]);
+        pin_scale(r[1], q2[1]);
+        pin_scale(R[1], Q[1]);
 #pragma unroll
-        for (int i = 1; i < N; i++) s0 += g[i];
-#pragma unroll
-        for (int i = 0; i < N; i++) {
-            g1[i] = g[i] * r[i];
-            r1[i] = r[i] * q[i];
-        }
-        s1 = g1[0];
-#pragma unroll
-        for (int i = 1; i < N; i++) s1 += g1[i];
-#pragma unroll
-        for (int i = 0; i < N; i++) {
-            g[i] = g1[i] * r1[i];
-            r[i] = r1[i] * q[i];
+        for (int i = 2; i < N; i++) {
+            pin_acc(s0, g[i]);
+            pin_fmac(s1, g[i], r[i]);
+            pin_scale(g[i], R[i]);
+            pin_scale(r[i], q2[i]);
+            pin_scale(R[i], Q[i]);
         }
         lds_add(&acc_col[row * HW_TW], s0);
         lds_add(&acc_col[(row + 1) * HW_TW], s1);
@@ -148,21 +185,16 @@ __device__ __forceinline__ void rec_walk_n(double (&g)[NT], double (&r)[NT], con
 #pragma unroll
         for (int i = 1; i < N; i++) s0 += g[i];
         lds_add(&acc_col[row * HW_TW], s0);
-        if (advance) {                       // the next phase goes on from the row behind this one
-#pragma unroll
-            for (int i = 0; i < N; i++) {
-                g[i] = g[i] * r[i];
-                r[i] = r[i] * q[i];
-            }
-        }
+        return true;
     }
+    return false;
 }
 
 template <int NB, int NS>
 __device__ inline void rec_group_nested(const CompTab &T, const double *__restrict__ et, int kb, int ks, double x, int Y0,
                                         int ga, int gb, int sa, int sb, bool on, double *__restrict__ acc_col) {
     constexpr int NT = NB + NS;
-    double g[NT], r[NT], q[NT];
+    double g[NT], r[NT], R[NT], q2[NT], Q[NT];
     const double aon = on ? 1.0 : 0.0;
     auto seed = [&](int i, int k, double y0) {
         double dx = x - T.mx[k], dy = y0 - T.my[k];
@@ -170,17 +202,34 @@ __device__ inline void rec_group_nested(const CompTab &T, const double *__restri
         double hx = qb * dx + qc * dy;
         double e = -0.5 * (T.qa[k] * dx * dx + (qb * dx + hx) * dy);
         double er = fmin(fmax(-(hx + 0.5 * qc), -REC_EMAX * EXP_SCALE), REC_EMAX * EXP_SCALE);
+        const double q = T.eq[k];
         g[i] = (T.A[k] * aon) * exp_tab64(e, et);
         r[i] = exp_tab64(er, et);
-        q[i] = T.eq[k];
+        R[i] = fmin(r[i] * (r[i] * q), REC_RMAX);
+        q2[i] = q * q;
+        Q[i] = q2[i] * q2[i];
+    };
+    // a phase that ended on an odd row leaves the state on that row: one row on, q read again from the table (once per phase: the
+    // trips do not carry it)
+    auto step = [&](int i, int k) {
+#pragma clang fp contract(off)
+        g[i] = g[i] * r[i];
+        r[i] = r[i] * T.eq[k];
+        R[i] = R[i] * q2[i];
     };
 #pragma unroll
     for (int i = 0; i < NB; i++) seed(i, kb + i, (double)(Y0 + ga));
-    rec_walk_n<NB, NT>(g, r, q, ga, sa, true, acc_col);
+    if (rec_walk_n<NB, NT>(g, r, R, q2, Q, ga, sa, acc_col)) {
+#pragma unroll
+        for (int i = 0; i < NB; i++) step(i, kb + i);
+    }
 #pragma unroll
     for (int i = 0; i < NS; i++) seed(NB + i, ks + i, (double)(Y0 + sa));
-    rec_walk_n<NT, NT>(g, r, q, sa, sb, true, acc_col);
-    rec_walk_n<NB, NT>(g, r, q, sb, gb, false, acc_col);
+    if (rec_walk_n<NT, NT>(g, r, R, q2, Q, sa, sb, acc_col) && sb < gb) {
+#pragma unroll
+        for (int i = 0; i < NB; i++) step(i, kb + i);
+    }
+    rec_walk_n<NB, NT>(g, r, R, q2, Q, sb, gb, acc_col);
 }
 
 // components per half in the pair's first (larger) set when a half holds gA: 3 of 5 or 6, 2 of 4; fewer than 4: no second set
