@@ -118,7 +118,7 @@ def gamma_by_stream(a, seed, ids):
 class GibbsField(object):
     """One field's images on the device plus what the sweep needs to know about them."""
 
-    def __init__(self, iset, band_index, calib, kappa, npix, a_0=5, b_0=.005, trace_iset=None):
+    def __init__(self, iset, band_index, calib, kappa, npix, a_0=5, b_0=.005, trace_iset=None, npix_observed=None):
         self.iset = iset
         # a strip-partitioned chain (dist.StripDeal): `iset` holds this rank's window (strip + halo), `trace_iset` its strip
         # alone -- what this rank adds to the field's log-likelihood; npix stays the whole frame's
@@ -127,6 +127,9 @@ class GibbsField(object):
         self.calib = np.asarray(calib, dtype=np.float64)
         self.kappa = np.asarray(kappa, dtype=np.float64)
         self.npix = float(npix)
+        # a masked image set: the pixels of every band that WERE observed (ImageSet.npix_observed() for a whole-frame set) -- what
+        # the sky level's Gamma conditional counts in place of npix
+        self.npix_observed = None if npix_observed is None else np.asarray(npix_observed, dtype=np.float64).reshape(iset.B)
         self.a_0, self.b_0 = a_0, b_0                                  # Gamma prior of the sky level (models.py:119-121)
         self.epsilon = np.array(iset.eps, copy=True)
         self.sset = None
@@ -212,10 +215,34 @@ class ModelGibbs(object):
     BANDS = ['u', 'g', 'r', 'i', 'z']
 
     def __init__(self, fields, typ, u, fluxes, shape, seed=0, flux_a_0=5., flux_b_0=.005, slice_args=None, engine="auto",
-                 deal=None, shape_args=None, shape_logprior=None, phi_period=180., shape_mass="reference", conditional="reference"):
+                 deal=None, shape_args=None, shape_logprior=None, phi_period=180., shape_mass="reference", conditional="reference",
+                 mask="refuse"):
         self.fields = list(fields)
-        for f in self.fields:       # the sweep on masked data is not built (photon split, flux masses, sky step): refuse it up front
-            f.iset._refuse_masked("ModelGibbs")
+        # mask="refuse": masked data is refused up front.  mask="honour": the sweep on masked images (NaN counts) -- no photons at
+        # a masked pixel (CEL_OPT_HONOUR_MASK around the split), the flux step's masses over the unmasked pixels, a sky step that
+        # counts unmasked pixels.  Under conditional="exact" only: the reference's location conditional charges a source
+        # counts * sum(psf weights) wherever it sits, but on masked data the exact term is counts * (the unit stamp summed over
+        # the OBSERVED pixels of the proposal's box), which moves with the proposal -- a star one PSF sigma from a masked column
+        # changes its observed mass by ~0.01 per 0.1 px, ~30 nats across one posterior width at 3 000 photons.  The exact
+        # conditional charges counts * stamp_mass(proposal), and stamp_mass returns the observed mass on such a set.
+        if mask not in ("refuse", "honour"):
+            raise ValueError("mask must be 'refuse' or 'honour'")
+        self.mask = mask
+        if mask == "honour":
+            if conditional != "exact":
+                raise ValueError("mask='honour' needs conditional='exact': the reference's location conditional charges "
+                                 "counts * sum(psf weights) wherever the source sits, but beside a mask the term is counts * (the "
+                                 "stamp's mass over the OBSERVED pixels of the proposal's box), which moves with the proposal")
+            if engine == "device":
+                raise ValueError("mask='honour' runs on the host slice engine: the device slice sampler does not charge the "
+                                 "observed mass per round (cel_slice_* refuse a masked set)")
+            for f in self.fields:
+                if int(f.iset.masked.sum()) and getattr(f, "npix_observed", None) is None:
+                    raise ValueError("mask='honour': a field with masked pixels needs GibbsField(npix_observed=) "
+                                     "(ImageSet.npix_observed() for a whole frame)")
+        else:
+            for f in self.fields:   # refused up front, before any device call
+                f.iset._refuse_masked("ModelGibbs")
         self.typ = np.ascontiguousarray(typ, dtype=np.int32)
         self.S = self.typ.shape[0]
         self.u = np.array(u, dtype=np.float64).reshape(self.S, 2)
@@ -321,13 +348,22 @@ class ModelGibbs(object):
         for img_dict in img_dicts:
             bands = [b for b in cls.BANDS if b in img_dict]
             imgs = [img_dict[b] for b in bands]
-            if any(getattr(im, "n_masked", 0) for im in imgs):
+            honour = kw.get("mask", "refuse") == "honour"
+            if kw.get("mask", "refuse") not in ("refuse", "honour"):
+                raise ValueError("mask must be 'refuse' or 'honour'")
+            if honour and kw.get("conditional", "reference") != "exact":
+                raise ValueError("mask='honour' needs conditional='exact' (the reference's location conditional does not charge "
+                                 "the observed mass of the proposal's box)")
+            if honour and kw.get("engine", "auto") == "device":
+                raise ValueError("mask='honour' runs on the host slice engine")
+            if not honour and any(getattr(im, "n_masked", 0) for im in imgs):
                 from ._lib import MaskedImagesError
                 raise MaskedImagesError("ModelGibbs: the images hold masked pixels (FitsImage(mask_invvar=True)) and the Gibbs "
                                         "sweep does not honour a mask")
             iset = _celeste._image_set(tuple(imgs))
             f = GibbsField(iset, [cls.BANDS.index(b) for b in bands], [im.calib for im in imgs],
-                           [im.kappa for im in imgs], imgs[0].nelec.size)
+                           [im.kappa for im in imgs], imgs[0].nelec.size,
+                           npix_observed=[im.nelec.size - getattr(im, "n_masked", 0) for im in imgs] if honour else None)
             f.images = imgs
             fields.append(f)
         S = len(params)
@@ -340,6 +376,26 @@ class ModelGibbs(object):
 
     def step_seed(self, step, k=0):
         return step_seed(self.seed, step, self.sweeps, k)
+
+    def _honour_mask(self):
+        """mask="honour": CEL_OPT_HONOUR_MASK set on every field's context around the device calls that honour a mask (photon split,
+        stamp masses), and restored behind them -- as CEL_OPT_SPLIT_FULL_BOX is set around the exact split.  Otherwise nothing."""
+        import contextlib
+        from . import _lib
+
+        @contextlib.contextmanager
+        def cm():
+            was = []
+            try:
+                if self.mask == "honour":
+                    for ctx in {id(f.iset.ctx): f.iset.ctx for f in self.fields}.values():
+                        was.append((ctx, ctx.get_option(_lib.CEL_OPT_HONOUR_MASK)))
+                        ctx.set_option(_lib.CEL_OPT_HONOUR_MASK, 1)
+                yield
+            finally:
+                for ctx, v in was:
+                    ctx.set_option(_lib.CEL_OPT_HONOUR_MASK, v)
+        return cm()
 
     def counts(self, f, fluxes=None, idx=None):
         """flux in nanomaggies -> expected photons in every image of field f  (sources.py:120-129)"""
@@ -375,6 +431,10 @@ class ModelGibbs(object):
         return self.noise_sums
 
     def _split_photons(self):
+        with self._honour_mask():       # (a masked set: no photons, no sky and no draws at a masked pixel)
+            self._split_photons_now()
+
+    def _split_photons_now(self):
         """the photon split of every field at the chain's current state (celeste_sample_sources.pyx:61-156): sample patches on the
         device, photons per (source, image), the sky photons per image"""
         self.noise_sums = []
@@ -413,7 +473,7 @@ class ModelGibbs(object):
         (models.py:155-160)"""
         for f, noise in zip(self.fields, self.noise_sums):
             a_n = f.a_0 + noise
-            b_n = f.b_0 + f.npix
+            b_n = f.b_0 + (f.npix if getattr(f, "npix_observed", None) is None else f.npix_observed)
             f.epsilon = self.rng.gamma(a_n, 1. / b_n)
             for b in range(f.iset.B):
                 f.iset.set_epsilon(b, f.epsilon[b])
@@ -492,10 +552,11 @@ class ModelGibbs(object):
                 psf_sums[:, f.band_index[b]] += mass[:, b] * (f.kappa[b] / f.calib[b])
 
         psf_sums = np.zeros((self.S, 5))
-        for f in self.fields[:-1]:
-            add_mass(psf_sums, f, f.iset.stamp_mass(field_sources(f)))
-        last = self.fields[-1]
-        last.iset.stamp_mass_begin(field_sources(last))
+        with self._honour_mask():       # (a masked set: the masses over the unmasked pixels, and no short cut from the split)
+            for f in self.fields[:-1]:
+                add_mass(psf_sums, f, f.iset.stamp_mass(field_sources(f)))
+            last = self.fields[-1]
+            last.iset.stamp_mass_begin(field_sources(last))
         try:
             # Gamma(a_n, 1 / b_n) = standard Gamma(a_n) * (1 / b_n); every (source, band) draws from its own stream -- on the
             # device, queued behind the mass kernel (cel_gamma_streams: gamma_by_stream's sampler, streams and decisions, ~10 us;
@@ -506,7 +567,8 @@ class ModelGibbs(object):
             else:
                 g = last.iset.ctx.gamma_streams(a_n.ravel(), self.step_seed("flux")).reshape(self.S, 5)
         finally:
-            m_last = last.iset.stamp_mass_end()     # whatever the draw does, the pending call is collected
+            with self._honour_mask():
+                m_last = last.iset.stamp_mass_end()     # whatever the draw does, the pending call is collected
         add_mass(psf_sums, last, m_last)
         new = g * (1. / (self.flux_b_0 + psf_sums))
         self.fluxes = np.where(self.active[:, None], new, self.fluxes)       # rows of other ranks' sources: merged at the sweep's end
@@ -540,7 +602,8 @@ class ModelGibbs(object):
         wsum = getattr(f, "_wsum", None)
         if wsum is None:                                               # (the PSF weights of an image set do not change)
             wsum = f._wsum = np.array([f.iset.band(b)[3:6].sum() for b in range(f.iset.B)])
-        mass = f.iset.stamp_mass(f.prop)
+        with self._honour_mask():       # (a masked set: the proposal's mass over the OBSERVED pixels of its box)
+            mass = f.iset.stamp_mass(f.prop)
         out = -(pc * (mass - wsum[None, :]) * f.has_patch[sel]).sum(axis=1)
         rects = getattr(f, "photon_rects", None)
         if rects is not None:

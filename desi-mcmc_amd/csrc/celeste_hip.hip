@@ -177,6 +177,7 @@ struct cel_ctx {
     int live = 0;               // image sets and source sets of this context that have not been destroyed (cel_ctx_destroy refuses)
     int split_full = 0;         // CEL_OPT_SPLIT_FULL_BOX
     int slice_fuse = SLICE_FUSE_DEFAULT;   // CEL_OPT_SLICE_FUSE
+    int honour_mask = 0;        // CEL_OPT_HONOUR_MASK
     int incremental = (getenv("CEL_INCREMENTAL") && atoi(getenv("CEL_INCREMENTAL")) == 0) ? 0 : 1;       // CEL_OPT_INCREMENTAL
     int tile_parts = (getenv("CEL_TILE_PARTS") && (atoi(getenv("CEL_TILE_PARTS")) == 1 || atoi(getenv("CEL_TILE_PARTS")) == 2 || atoi(getenv("CEL_TILE_PARTS")) == 4))
                          ? atoi(getenv("CEL_TILE_PARTS")) : 0;       // CEL_OPT_TILE_PARTS (the env var: the initial value, for A/B runs)
@@ -598,6 +599,10 @@ int cel_ctx_set_option(cel_ctx *c, int key, double v) {
         if (!(v >= 0.0 && v <= 1e9) || v != floor(v)) return fail(CEL_ERR_INVALID, "CEL_OPT_SLICE_FUSE must be 0, 1 or a block count");
         c->slice_fuse = (int)v;
         return CEL_OK;
+    case CEL_OPT_HONOUR_MASK:
+        if (v != 0.0 && v != 1.0) return fail(CEL_ERR_INVALID, "CEL_OPT_HONOUR_MASK must be 0 or 1");
+        c->honour_mask = (int)v;
+        return CEL_OK;
     case CEL_OPT_TILE_PARTS:
         if (v != 0.0 && v != 1.0 && v != 2.0 && v != 4.0) return fail(CEL_ERR_INVALID, "CEL_OPT_TILE_PARTS must be 0 (by the frame's size), 1, 2 or 4");
         c->tile_parts = (int)v;
@@ -658,6 +663,7 @@ int cel_ctx_get_option(cel_ctx *c, int key, double *v) {
     case CEL_OPT_INCREMENTAL: *v = c->incremental; return CEL_OK;
     case CEL_OPT_SPLIT_FULL_BOX: *v = c->split_full; return CEL_OK;
     case CEL_OPT_SLICE_FUSE: *v = c->slice_fuse; return CEL_OK;
+    case CEL_OPT_HONOUR_MASK: *v = c->honour_mask; return CEL_OK;
     case CEL_OPT_PROFILE: *v = (double)c->profile; return CEL_OK;
     case CEL_OPT_TILE_ORDER: *v = (double)c->tile_order; return CEL_OK;
     case CEL_OPT_TILE_ROWS: *v = c->tile_rows; return CEL_OK;
@@ -797,6 +803,13 @@ static int refuse_masked(const cel_images *im, const char *who) {
     for (int b = 0; b < im->B; b++) n += im->masked[b];
     return fail(CEL_ERR_INVALID, "%s: the image set holds %lld masked pixels (NaN counts, cel_images_set_nelec) and this call does not honour a mask",
                 who, (long long)n);
+}
+
+// ... and the calls of the Gibbs sweep that have been taught (photon split, stamp masses, flux step) do so unless the context asks
+// for the mask to be honoured (CEL_OPT_HONOUR_MASK); honours_mask: this call takes its masked path
+static inline bool honours_mask(const cel_images *im) { return im->any_masked && im->ctx->honour_mask != 0; }
+static int refuse_masked_unless_honoured(const cel_images *im, const char *who) {
+    return im->ctx->honour_mask ? CEL_OK : refuse_masked(im, who);
 }
 
 int cel_images_set_epsilon(cel_images *im, int band, double eps) {
@@ -1776,7 +1789,7 @@ int cel_patch_loglik(cel_images *im, cel_sources *src, const int32_t *boxes, con
 // other.  Removed again.)
 int cel_stamp_mass_ready(cel_images *im, cel_sources *src, int *ready) {
     if (!im || !src || !ready) return fail(CEL_ERR_INVALID, "cel_stamp_mass_ready: null argument");
-    *ready = (src->ctx == im->ctx && src->B == im->B && im->ctx->mass_reuse_of() && src->gen != 0 && im->massfx_gen == src->gen &&
+    *ready = (src->ctx == im->ctx && src->B == im->B && !honours_mask(im) && im->ctx->mass_reuse_of() && src->gen != 0 && im->massfx_gen == src->gen &&
               src->S * im->B <= im->d_massfx.cap) ? 1 : 0;
     return CEL_OK;
 }
@@ -1792,7 +1805,10 @@ int cel_stamp_mass_begin(cel_images *im, cel_sources *src) {
     im->mass_todo_S = -1;
     if (S == 0) { im->mass_pending = 0; return CEL_OK; }
     int rc = CEL_OK;
-    const bool from_split = c->mass_reuse_of() && src->gen != 0 && im->massfx_gen == src->gen && S * B <= im->d_massfx.cap;
+    // a masked set whose mask is honoured (CEL_OPT_HONOUR_MASK): the unit stamp summed over the UNMASKED pixels of the box -- the
+    // split's short cut, which sums every pixel it walks, does not apply (and the masked split leaves it alone)
+    const bool observed = honours_mask(im);
+    const bool from_split = !observed && c->mass_reuse_of() && src->gen != 0 && im->massfx_gen == src->gen && S * B <= im->d_massfx.cap;
     if (!from_split || im->recs_gen != src->gen) rc = run_prep(im, src);
     if (rc) return rc;
     double *d_out = nullptr;
@@ -1811,6 +1827,9 @@ int cel_stamp_mass_begin(cel_images *im, cel_sources *src) {
         HIP_TRY(hipMemcpyAsync(&c->mail->mass_todo, d_ntodo, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         im->mass_todo_S = S;
         im->mass_gen = src->gen; im->mass_todo_ptr = im->d_mass_todo;
+    } else if (observed) {
+        hipLaunchKernelGGL(k_stamp_mass_masked, dim3((unsigned)(S * B)), dim3(64), 0, c->stream, im->d_bands, B, im->H, im->W, S,
+                           im->d_recs, (const double *)im->d_nelec, c->tail_T, d_out, (const int *)nullptr);
     } else {
         hipLaunchKernelGGL((k_patch_ll_hw<3, double>), dim3((unsigned)(S * B)), dim3(64), 0, c->stream, im->d_bands, B, S, im->d_recs,
                            (const int *)nullptr, (const int4 *)nullptr, (const int64_t *)nullptr, (const double *)nullptr,
@@ -1869,7 +1888,7 @@ int cel_flux_conditionals(cel_images *im, cel_sources *src, uint64_t seed, doubl
                           const double *calib, const double *kappa, double *flux_new, int32_t *active) {
     if (!im || !src || !band_letter || !calib || !kappa || !flux_new || !active) return fail(CEL_ERR_INVALID, "cel_flux_conditionals: null argument");
     if (src->B != im->B || src->ctx != im->ctx) return fail(CEL_ERR_INVALID, "sources do not match images");
-    { int rm = refuse_masked(im, "cel_flux_conditionals"); if (rm) return rm; }
+    { int rm = refuse_masked_unless_honoured(im, "cel_flux_conditionals"); if (rm) return rm; }
     if (im->samp_S <= 0 || im->samp_S != src->S || !im->ssum_valid)
         return fail(CEL_ERR_INVALID, "cel_flux_conditionals needs a resident photon split of these %lld sources (have %lld)",
                     (long long)src->S, (long long)im->samp_S);
@@ -2412,7 +2431,7 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
     const bool resident = (offsets == nullptr);
     if (!resident && !samp) return fail(CEL_ERR_INVALID, "cel_photon_split: offsets given without an output buffer");
     if (!im->have_nelec) return fail(CEL_ERR_INVALID, "cel_photon_split needs cel_images_set_nelec first");
-    { int rm = refuse_masked(im, "cel_photon_split"); if (rm) return rm; }
+    { int rm = refuse_masked_unless_honoured(im, "cel_photon_split"); if (rm) return rm; }
     if (im->TW * im->TH != 2048) return fail(CEL_ERR_INVALID, "cel_photon_split needs 2048-pixel render tiles");
     cel_ctx *c = im->ctx;
     if (src->ctx != im->ctx || src->B != im->B) return fail(CEL_ERR_INVALID, "sources do not match images");
@@ -2422,6 +2441,8 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
     // with the split's strict boxes (the model image of cel_images_get_lambda is left alone).
     // Direct form: a plain render (its kernel accumulates the totals itself).
     const bool hw = (c->variant != 0) && (im->TW == HW_TW);
+    // a masked set under CEL_OPT_HONOUR_MASK: the masked twins (no photons, no sky, no draws at a masked pixel), no mass short cut
+    const bool masked = honours_mask(im);
     bool use_massfx = false;
     const double *full_rate = nullptr;
     int rc;
@@ -2438,7 +2459,7 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
             else rc = render_impl(im, src, 0, nullptr, nullptr, im->d_rate);
         } else if (c->split_reuse && current) {
             const int64_t nm = src->S * im->B;
-            if (resident && c->mass_reuse_of() && nm > 0) {
+            if (resident && c->mass_reuse_of() && nm > 0 && !masked) {
                 // both kernels of this path also sum every unit stamp they evaluate: together the stamps' masses (cel_stamp_mass)
                 if (nm > im->d_massfx.cap) {     // the two grow together; d_massfx, named last, holds the pair's capacity
                     const int64_t cap = nm + nm / 4 + 64;
@@ -2545,7 +2566,12 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
         a.debug = c->debug;
         if (hw && (rc = scratch_get(c, SCR_VALUES, sizeof(double) * 2 * (size_t)T, (void **)&a.partials))) return rc;
         int pi = prof_begin(c, CEL_K_SPLIT);
-        if (hw && resident) {
+        if (masked) {          // (a set with a NaN never takes the 16-bit photons-left plane: nelec_u16 is false)
+            if (hw && resident) hipLaunchKernelGGL(k_photon_split_hw_masked<int>, dim3(2 * T), dim3(64), 0, c->stream, a);
+            else if (hw) hipLaunchKernelGGL(k_photon_split_hw_masked<double>, dim3(2 * T), dim3(64), 0, c->stream, a);
+            else if (resident) hipLaunchKernelGGL(k_photon_split_masked<int>, dim3(T), dim3(64), 0, c->stream, a);
+            else hipLaunchKernelGGL(k_photon_split_masked<double>, dim3(T), dim3(64), 0, c->stream, a);
+        } else if (hw && resident) {
             if (im->nelec_u16) hipLaunchKernelGGL((k_photon_split_hw<int, unsigned short>), dim3(2 * T), dim3(64), 0, c->stream, a);
             else hipLaunchKernelGGL((k_photon_split_hw<int, int>), dim3(2 * T), dim3(64), 0, c->stream, a);
         } else if (hw) {

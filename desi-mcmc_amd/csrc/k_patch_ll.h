@@ -381,6 +381,73 @@ k_patch_ll_hw(const BandDev *__restrict__ bands, int B, int64_t P, const SrcRec 
 #undef PLL_PUT
 }
 
+// ---- the OBSERVED stamp mass (CEL_OPT_HONOUR_MASK on a masked image set) -------------------------------------------
+// The unit stamp of a source summed over the UNMASKED pixels of its own box (a NaN count marks a pixel that was not observed): what
+// cel_stamp_mass returns on such a set -- the rate of the source's photons per unit of expected counts, which the flux step and the
+// exact location and shape conditionals charge (cel_estep_stats reports the same quantity as `mass`).  MODE 3 above cannot form it:
+// it sums inside hw_walk<true> and never sees a pixel.  Here every 32 x 64 chunk of the box is walked into the LDS tile as MODES 1/2
+// walk it (the same table, drop rule and components as MODE 3), the chunk's counts are loaded eight rows at a time once the walk's
+// registers are free (addresses clamped into the chunk, nothing predicated), and a lane adds its rows in order where the count is
+// not NaN; then the wave's sum.  The order is fixed: the same bits on every run.  One wave per job; job_order: a list of
+// (source, band) jobs s * B + b (as MODE 3's leftovers), or nullptr = every job in index order.  The records are those of whichever
+// catalogue was prepared last: a batch of proposals is such a catalogue.  A box masked everywhere gives exactly 0, a source
+// without a record (type < 0) likewise.  LDS: MODE 2's (the 16 KB tile + the component table: eight blocks per CU).
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+k_stamp_mass_masked(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, const SrcRec *__restrict__ recs,
+                    const double *__restrict__ nelec, double Tdrop, double *__restrict__ out /* S*B */,
+                    const int *__restrict__ job_order) {
+    __shared__ double acc[HW_TH * HW_TW];
+    __shared__ CompTab T;
+    __shared__ double et[64];
+    const int lane = threadIdx.x;
+    const int half = lane >> 5, col = lane & 31;
+    const int64_t job = job_order ? (int64_t)job_order[blockIdx.x] : (int64_t)blockIdx.x;
+    const int b = (int)(job % B);
+    const int64_t s = job / B;
+    RecU rec = rec_unpack(rec_fetch(recs + (int64_t)b * S, (int)s, lane));
+    if (rec.type < 0 || rec.x1 <= rec.x0 || rec.y1 <= rec.y0) {      // no stamp
+        if (lane == 0) out[job] = 0.0;
+        return;
+    }
+    const BandDev *bd = bands + b;
+    rec.scale = 1.0;                                                 // the tile holds the unit stamp
+    et[lane] = exp2((double)lane * (1.0 / 64.0));
+    const LaneConst lc = lane_consts(lane, bd);
+    Comp cj;                                                         // the job's components: one per lane, for every chunk's table
+    if (lane < ((rec.type == 0) ? K_PSF : K_GAL)) cj = make_comp_lc(lc, rec);
+    const int dropmode = (Tdrop > 0.0) ? HW_DROP_SELF : HW_DROP_NONE;
+    const double *zn = nelec + (int64_t)b * H * W;
+    double m = 0.0;
+    for (int Y0 = rec.y0; Y0 < rec.y1; Y0 += HW_TH) {
+        const int rb = min(HW_TH, rec.y1 - Y0);
+        for (int X0 = rec.x0; X0 < rec.x1; X0 += HW_TW) {
+            const int xi = X0 + col;
+            const bool on = xi < rec.x1;
+#pragma unroll
+            for (int r = 0; r < HW_TH / 2; r++) acc[r * 64 + lane] = 0.0;
+            bool direct;
+            const int Kk = hw_build(T, lc, rec, lane, dropmode, Tdrop, 0.0, Y0, X0, min(rec.x1, X0 + HW_TW) - 1, 0, rb, direct, &cj);
+            hw_walk(T, et, Kk, (double)xi, Y0, 0, rb, on, direct, acc, lane);
+            __syncthreads();
+            // (the box lies inside the frame: 0 <= y0, y1 <= H, 0 <= x0, x1 <= W -- k_prep cuts it; the clamps keep every address in the chunk)
+            const int64_t zo = (int64_t)Y0 * W + min(xi, rec.x1 - 1);
+            for (int r0 = 0; r0 < HW_TH / 2 && 2 * r0 < rb; r0 += 8) {
+                double ne[8];
+#pragma unroll
+                for (int r = 0; r < 8; r++) ne[r] = zn[zo + (int64_t)min(2 * (r0 + r) + half, rb - 1) * W];
+#pragma unroll
+                for (int r = 0; r < 8; r++) {
+                    const bool mine = on && 2 * (r0 + r) + half < rb;
+                    m += (mine && ne[r] == ne[r]) ? acc[(r0 + r) * 64 + lane] : 0.0;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    m = wave_sum(m);
+    if (lane == 0) out[job] = m;
+}
+
 // A galaxy's 42 components are 3 x 14: covariance v_j W + P_k about the same centre for the 14 profile variances v_j of PSF
 // component k.  In the basis that diagonalises the pair (W, P_k) -- M_k with M^T W M = I, M^T P_k M = diag(l1, l2) -- every
 // one of the 14 quadratic forms is a1^2 / (v_j + l1) + a2^2 / (v_j + l2) with a = M_k^T (x - centre_k): the rotated

@@ -535,9 +535,12 @@ struct SplitArgs {
                                 // (source, half-tile) partials does not matter either; zeroed by the caller, or nullptr
 };
 
-template <typename TS>
-__global__ void __launch_bounds__(64)
-k_photon_split(SplitArgs a) {
+// MASKED (the twins k_photon_split_masked / k_photon_split_hw_masked below, CEL_OPT_HONOUR_MASK on a masked image set): a NaN count
+// marks a pixel that was not observed.  It holds no photons -- every patch value there is 0 --, adds nothing to the noise sum
+// whether or not a box covers it, and draws no random numbers; everything at observed pixels is untouched (the streams are keyed
+// by pixel and source).  Two selects outside the source loop: the split is that of the set with 0 counts at the masked pixels.
+template <typename TS, bool MASKED>
+__device__ __forceinline__ void photon_split_body(SplitArgs a) {
     __shared__ double rate[2048];     // remaining total rate of the pixel (sources not yet drawn + sky)
     __shared__ int left[2048];        // photons of the pixel not yet attributed
     __shared__ CompTab T;
@@ -567,7 +570,12 @@ k_photon_split(SplitArgs a) {
         const int y = Y0 + i * rstep + rsub;
         const bool in = (xi < a.W) && (y < a.H);
         rate[i * 64 + lane] = eps;
-        left[i * 64 + lane] = in ? photons_int(a.nelec[plane + (int64_t)y * a.W + xi]) : 0;
+        int n0 = 0;
+        if (in) {
+            const double ne = a.nelec[plane + (int64_t)y * a.W + xi];
+            n0 = (!MASKED || ne == ne) ? photons_int(ne) : 0;
+        }
+        left[i * 64 + lane] = n0;
     }
 
     for (int pass = 0; pass < 2; pass++) {
@@ -622,11 +630,21 @@ k_photon_split(SplitArgs a) {
         const int y = Y0 + i * rstep + rsub;
         if (y < a.noise_y0 || y >= a.noise_y1) continue;
         if ((covered >> i) & 1u) noise += (double)left[i * 64 + lane];
-        else if (xi < a.W && y < a.H) noise += a.nelec[plane + (int64_t)y * a.W + xi];
+        else if (xi < a.W && y < a.H) {
+            const double ne = a.nelec[plane + (int64_t)y * a.W + xi];
+            noise += (!MASKED || ne == ne) ? ne : 0.0;
+        }
     }
     noise = wave_sum(noise);
     if (lane == 0) a.partials[tile] = noise;
 }
+
+template <typename TS>
+__global__ void __launch_bounds__(64)
+k_photon_split(SplitArgs a) { photon_split_body<TS, false>(a); }
+template <typename TS>
+__global__ void __launch_bounds__(64)
+k_photon_split_masked(SplitArgs a) { photon_split_body<TS, true>(a); }
 
 // ---- the same split on the column recurrence ------------------------------------------------------
 // k_photon_split above evaluates every (source, pixel) twice with the direct evaluator (once for
@@ -643,9 +661,8 @@ k_photon_split(SplitArgs a) {
 #define SP_TH 32
 // TL: the type of the photons-left plane.  unsigned short (valid while every pixel of the image holds 0 ... 65 535 photons: the
 // host knows the image's range, k_nelec_range) takes the block from 25 312 to 23 264 B of LDS, 7 waves per CU instead of 6.
-template <typename TS, typename TL>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
-k_photon_split_hw(SplitArgs a) {
+template <typename TS, typename TL, bool MASKED>
+__device__ __forceinline__ void photon_split_hw_body(SplitArgs a) {
     __shared__ double one[SP_TH * HW_TW];
     __shared__ double rate[SP_TH * HW_TW];
     __shared__ TL left[SP_TH * HW_TW];
@@ -703,7 +720,8 @@ k_photon_split_hw(SplitArgs a) {
             const bool in = (xi < a.W) && (y < a.H);
             one[r * 64 + lane] = 0.0;
             rate[r * 64 + lane] = in ? rt[r] : eps;
-            left[r * 64 + lane] = (TL)(in ? photons_int(ne[r]) : 0);
+            // (MASKED: photons_int(NaN) is INT_MIN; a masked pixel has no photons to split)
+            left[r * 64 + lane] = (TL)((in && (!MASKED || ne[r] == ne[r])) ? photons_int(ne[r]) : 0);
         }
     }
     const int cnt = a.tile_cnt[tile];
@@ -945,7 +963,7 @@ k_photon_split_hw(SplitArgs a) {
         const int y = Y0 + 2 * r + half;
         const bool counted = (y >= a.noise_y0) && (y < a.noise_y1);
         const bool in = (xi < a.W) && (y < a.H);
-        const double v = ((covered >> r) & 1u) ? (double)left[r * 64 + lane] : (in ? raw[r] : 0.0);
+        const double v = ((covered >> r) & 1u) ? (double)left[r * 64 + lane] : ((in && (!MASKED || raw[r] == raw[r])) ? raw[r] : 0.0);
         noise += counted ? v : 0.0;
     }
 #ifdef CEL_ABLATE
@@ -954,3 +972,11 @@ k_photon_split_hw(SplitArgs a) {
     noise = wave_sum(noise);
     if (lane == 0) a.partials[2 * tile + sub] = noise;
 }
+
+template <typename TS, typename TL>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
+k_photon_split_hw(SplitArgs a) { photon_split_hw_body<TS, TL, false>(a); }
+// the masked twin: a set with a NaN never takes the 16-bit photons-left plane (k_nelec_range), so TL = int alone
+template <typename TS>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
+k_photon_split_hw_masked(SplitArgs a) { photon_split_hw_body<TS, int, true>(a); }

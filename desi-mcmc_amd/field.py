@@ -223,12 +223,21 @@ class ImageSet(object):
         L.check(L.lib().cel_images_mask_info(self._h, out.ctypes.data_as(L.c_int64_p)))
         return out
 
-    def _refuse_masked(self, who):
-        """the calls that do not honour a mask refuse a masked set before any device call (the library refuses them as well)"""
+    def _refuse_masked(self, who, honoured=False):
+        """the calls that do not honour a mask refuse a masked set before any device call (the library refuses them as well).
+        honoured=True: a call that honours the mask when its context says so (CEL_OPT_HONOUR_MASK: photon split, stamp masses,
+        flux step) -- refused only while the option is off"""
+        if honoured and self.ctx.get_option(L.CEL_OPT_HONOUR_MASK):
+            return
         n = int(self.masked.sum())
         if n:
             raise L.MaskedImagesError("%s: the image set holds %d masked pixels (NaN counts) and this call does not honour a mask"
                                       % (who, n))
+
+    def npix_observed(self):
+        """unmasked pixels per band of a whole-frame set, H W - masked -> float64[B]: what the sky step's Gamma conditional
+        counts (GibbsField(npix_observed=))"""
+        return float(self.H * self.W) - self.masked.astype(np.float64)
 
     def set_nelec_device(self, ptr):
         L.check(L.lib().cel_images_set_nelec(self._h, C.c_void_p(ptr), L.CEL_DEVICE))
@@ -337,7 +346,7 @@ class ImageSet(object):
     def photon_split(self, sources, seed):
         """Gibbs photon split (celeste_sample_sources.pyx:61-156) for every band.
         -> (patches[b][s] 2-D arrays or None, boxes[B,S,4], noise_sum[B])"""
-        self._refuse_masked("photon_split")
+        self._refuse_masked("photon_split", honoured=True)
         S = sources.S
         boxes, status = self.source_boxes(sources)
         area = np.where(status > 0, (boxes[..., 1] - boxes[..., 0]).astype(np.int64) * (boxes[..., 3] - boxes[..., 2]), 0)
@@ -364,7 +373,7 @@ class ImageSet(object):
     def photon_split_resident(self, sources, seed):
         """The photon split with the sample patches kept in device memory as int32 (1.6 GB at 10 000
         sources x 5 bands x 2048^2 never leave the GPU).  -> noise_sum[B]"""
-        self._refuse_masked("photon_split_resident")
+        self._refuse_masked("photon_split_resident", honoured=True)
         noise = np.zeros(self.B)
         L.check(L.lib().cel_photon_split(self._h, sources._h, C.c_uint64(int(seed) & (2 ** 64 - 1)), None, None,
                                          L.CEL_DEVICE, L.dptr(noise)))
@@ -476,7 +485,8 @@ class ImageSet(object):
         return rects
 
     def stamp_mass(self, sources):
-        """sum of every source's unit stamp over its own box -> (S, B)  (sources.py:336-339)"""
+        """sum of every source's unit stamp over its own box -> (S, B)  (sources.py:336-339).  On a masked set under
+        CEL_OPT_HONOUR_MASK: over the UNMASKED pixels of the box (estep_stats' mass); this, stamp_mass_begin / _end alike"""
         out = np.zeros((sources.S, self.B))
         self._mass_pending = False              # (a call queued earlier and never collected is dropped)
         L.check(L.lib().cel_stamp_mass(self._h, sources._h, L.dptr(out)))

@@ -94,6 +94,18 @@ enum {
                                 the block that finishes a chain's last job of the round consumes the chain's log-likelihoods, names
                                 its next point and writes that point's records; 1: every round.  The chains are the same bit for
                                 bit either way.  Measured in round 6: no gain at any N, hence off */
+    CEL_OPT_HONOUR_MASK = 17, /* 0 (default): the calls of the Gibbs sweep refuse a MASKED image set (NaN counts, cel_images_set_nelec)
+                                 as before.  1: on a masked set cel_photon_split (resident and caller-buffer forms, both kernels)
+                                 gives a masked pixel no photons -- every patch value there is 0, it adds nothing to the noise
+                                 sum whether or not a box covers it, and it draws no random numbers (the twins k_photon_split_hw_masked
+                                 / k_photon_split_masked; everything at observed pixels is the split of the set with 0 counts at the
+                                 masked pixels, bit for bit); cel_stamp_mass / _begin / _end return the unit stamp summed over the
+                                 UNMASKED pixels of the source's box (k_stamp_mass_masked: cel_estep_stats' `mass`), the stamp-mass
+                                 short cut of CEL_OPT_SPLIT_REUSE = 2 is not taken and cel_stamp_mass_ready answers 0; and
+                                 cel_flux_conditionals runs on those sums and masses (a source masked in every band draws from its
+                                 prior).  On a set without a NaN the option changes nothing: the same kernels, launches and bits.
+                                 cel_slice_locations, cel_slice_sample and the isolated forms of cel_patch_loglik[_multi] refuse a
+                                 masked set whatever this option says */
     CEL_OPT_TILE_PARTS = 13, /* how many one-wave blocks share a render tile of the general 32 x 64 kernel.  0 (default) = by
                                the frame's size: 4 for at most 512 tiles, 2 for at most 3 072, else 1 -- a frame of few tiles
                                (one rank's row strip of a field cut 8 ways, a 51 x 51 real field) finishes when its heaviest
