@@ -91,10 +91,31 @@ class ReplayStream(object):
         return self.pos == self.vals.size
 
 
+def _new_direction_record():
+    return dict(doublings=0, out_rounds=0, capped=False, shrinks=0, accept_calls=0, end_pairs=0, rejections=0, max_halvings=0,
+                outside=0, pairs_one_outside=0, pairs_both_outside=0)
+
+
 def scalar_slicesample(init_x, logprob, stream, chain, sigma=1.0, step_out=True, max_steps_out=1000, compwise=True,
-                       numdir=2, doubling_step=True):
-    """slicesample.py:114-228, one chain, uniforms taken from stream `chain` in the reference's order"""
+                       numdir=2, doubling_step=True, trace=None):
+    """slicesample.py:114-228, one chain, uniforms taken from stream `chain` in the reference's order
+
+    trace: None, or a dict that receives trace["directions"], one record per direction sliced, in order:
+        doublings           times the interval was doubled (:150-157)
+        out_rounds          times the doubling loop's condition was evaluated (doublings + 1 when stepping out by doubling)
+        capped              the loop ended at max_steps_out with an interval end still above the level
+        shrinks             points drawn inside the interval (:172)
+        accept_calls        calls of `acceptable` (:119-131)
+        end_pairs           halvings of `acceptable` that had to look at both interval ends (`splits`)
+        rejections          calls of `acceptable` that returned False
+        max_halvings        most halvings any one call of `acceptable` made
+        outside             points at which logprob returned -inf (outside the prior's support)
+        pairs_one_outside / pairs_both_outside     pairs of interval ends (doubling loop, `acceptable`) with one / both there
+    What it returns and what it draws do not depend on `trace`.  With a trace both ends of a pair are evaluated even where
+    the reference's `or` / `and` stops at the first (the lock-step engines always score both); the second value is only counted."""
     one = np.array([chain])
+    if trace is not None:
+        trace["directions"] = []
 
     def rand():
         return stream.uniform(one)[0]
@@ -103,10 +124,30 @@ def scalar_slicesample(init_x, logprob, stream, chain, sigma=1.0, step_out=True,
         return stream.normal(one)[0]
 
     def direction_slice(direction, init_x):
+        if trace is not None:
+            rec = _new_direction_record()
+            trace["directions"].append(rec)
+
         def dir_logprob(z):
-            return logprob(direction * z + init_x)
+            v = logprob(direction * z + init_x)
+            if trace is not None and v == -np.inf:
+                rec["outside"] += 1
+            return v
+
+        def saw_pair(a, b, va=None, vb=None):
+            """trace only: the ends a, b of a pair the engines score together; va / vb: a value the caller has already"""
+            va = logprob(direction * a + init_x) if va is None else va
+            vb = logprob(direction * b + init_x) if vb is None else vb
+            n = int(va == -np.inf) + int(vb == -np.inf)
+            if n == 1:
+                rec["pairs_one_outside"] += 1
+            elif n == 2:
+                rec["pairs_both_outside"] += 1
 
         def acceptable(z, llh_s, L, U):
+            halvings = 0
+            if trace is not None:
+                rec["accept_calls"] += 1
             while (U - L) > 1.1 * sigma:
                 middle = 0.5 * (L + U)
                 splits = (middle > 0 and z >= middle) or (middle <= 0 and z < middle)
@@ -114,7 +155,15 @@ def scalar_slicesample(init_x, logprob, stream, chain, sigma=1.0, step_out=True,
                     U = middle
                 else:
                     L = middle
+                if trace is not None:
+                    halvings += 1
+                    rec["max_halvings"] = max(rec["max_halvings"], halvings)
+                    if splits:
+                        rec["end_pairs"] += 1
+                        saw_pair(L, U)
                 if splits and llh_s >= dir_logprob(U) and llh_s >= dir_logprob(L):
+                    if trace is not None:
+                        rec["rejections"] += 1
                     return False
             return True
         upper = sigma * rand()
@@ -123,7 +172,17 @@ def scalar_slicesample(init_x, logprob, stream, chain, sigma=1.0, step_out=True,
         l_steps_out = u_steps_out = 0
         if step_out:
             if doubling_step:
-                while (dir_logprob(lower) > llh_s or dir_logprob(upper) > llh_s) and (l_steps_out + u_steps_out) < max_steps_out:
+                while True:
+                    if trace is not None:
+                        rec["out_rounds"] += 1
+                        saw_pair(lower, upper)
+                    above = dir_logprob(lower) > llh_s or dir_logprob(upper) > llh_s
+                    if not (above and (l_steps_out + u_steps_out) < max_steps_out):
+                        if trace is not None:
+                            rec["capped"] = bool(above)
+                        break
+                    if trace is not None:
+                        rec["doublings"] += 1
                     if rand() < 0.5:
                         l_steps_out += 1
                         lower -= (upper - lower)
@@ -141,6 +200,8 @@ def scalar_slicesample(init_x, logprob, stream, chain, sigma=1.0, step_out=True,
         while True:
             new_z = (upper - lower) * rand() + lower
             new_llh = dir_logprob(new_z)
+            if trace is not None:
+                rec["shrinks"] += 1
             if new_llh > llh_s and acceptable(new_z, llh_s, start_lower, start_upper):
                 break
             elif new_z < 0:
