@@ -20,6 +20,8 @@ CEL_OPT_TILE_TIMING, CEL_OPT_TILE_LAYOUT, CEL_OPT_DEBUG, CEL_OPT_PHOTON_LISTS, C
 CEL_OPT_TAIL_LOG_SOURCE, CEL_OPT_TILE_PARTS, CEL_OPT_INCREMENTAL, CEL_OPT_SPLIT_FULL_BOX, CEL_OPT_SLICE_FUSE = 12, 13, 14, 15, 16
 #: 1 = on a masked image set the photon split, the stamp masses and the flux step honour the mask (0, the default: they refuse it)
 CEL_OPT_HONOUR_MASK = 17
+#: what cel_slice_sample scores: 0 the reference's conditional (default), 1 the exact one (ImageSet.slice_sample(conditional=))
+CEL_OPT_SLICE_CONDITIONAL = 18
 #: CEL_OPT_TAIL_LOG presets.  32 (the default): a skipped component is below eps * e^-32 on its tile, model pixels
 #: agree with the reference to ~1e-13, which is what the parity tests assert (1e-10).  20: the documented fast
 #: preset for callers that need only north_star's 1e-6 -- a skipped component is below eps * 2e-9, the sum of

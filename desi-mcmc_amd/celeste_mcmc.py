@@ -282,7 +282,8 @@ class ModelGibbs(object):
         # row and column out); the location AND the shape step charge counts * (the proposal's stamp mass on ITS box); and a
         # proposal whose box does not cover every photon of the source has probability zero (the reference scores the fixed
         # data patch whatever the proposal's box, sources.py:134-183).  Calibrated at 192 replicates and pi P = pi on a sigma
-        # grid (tests/test_calibration.py, DESIGN Q20).  Host engine; a change of the integer box needs the ring between the two
+        # grid (tests/test_calibration.py, DESIGN Q20).  Either slice engine (the device's: cel_slice_sample under
+        # CEL_OPT_SLICE_CONDITIONAL, one field of whole unmasked frames); a change of the integer box needs the ring between the two
         # boxes free of the source's photons, so big galaxies mix more slowly across box sizes than under the reference's rules.
         if conditional not in ("reference", "exact"):
             raise ValueError("conditional must be 'reference' or 'exact'")
@@ -661,7 +662,8 @@ class ModelGibbs(object):
             dirs = None if a.get("compwise", True) else ChainStreams(seed, np.arange(self.S)).directions(int(a.get("numdir", 2)), 4)
             ids = np.where(mine & (self.typ == 1), np.arange(self.S), -1).astype(np.int32)
             new, _, st = f.iset.slice_sample(sset, 1, a.get("sigma", 1.0), seed, dirs=dirs, step_out=a.get("step_out", True),
-                                             max_steps_out=a.get("max_steps_out", 1000), phi_max=self.phi_period, chain_ids=ids)
+                                             max_steps_out=a.get("max_steps_out", 1000), phi_max=self.phi_period, chain_ids=ids,
+                                             conditional=self.conditional)
             new[:, 2] = np.where(ids >= 0, (new[:, 2] + self.phi_period) % self.phi_period, new[:, 2])
             self.shape = new
             f._uploaded = None                                 # (the device holds the unwrapped angles)
@@ -686,19 +688,55 @@ class ModelGibbs(object):
 
     def _shape_engine_on_device(self):
         """the device runs the shape step when there is one field, the log-prior is the built-in one and the options are
-        those of slice_sample_skew's family: no stepping out or doubling, component-wise or random directions"""
+        those of slice_sample_skew's family: no stepping out or doubling, component-wise or random directions -- under either
+        conditional (the exact one: CEL_OPT_SLICE_CONDITIONAL; an unmasked set, no strip deal).  shape_mass="exact" under the
+        reference's conditional is a diagnostic setting of the host engine."""
         a = self.shape_args
         ok = (len(self.fields) == 1 and self._default_shape_prior and (not a.get("step_out", True) or a.get("doubling_step", True))
               and set(a) <= {"step_out", "doubling_step", "compwise", "numdir", "sigma", "max_steps_out"}
-              and a.get("accept", "reference") == "reference" and self.shape_mass == "reference" and self.conditional == "reference")
+              and a.get("accept", "reference") == "reference"
+              and (self._exact_on_device() if self.conditional == "exact" else self.shape_mass == "reference"))
         if self.engine == "device" and not ok:
             raise ValueError("the device shape sampler runs one field, the built-in log-prior, stepping out by doubling or none")
         return ok and self.engine != "host"
 
+    def _exact_on_device(self):
+        """what the exact conditional needs of the chain to run on the device (cel_slice_sample under
+        CEL_OPT_SLICE_CONDITIONAL): whole, unmasked frames"""
+        return self.mask != "honour" and not (self.deal is not None and getattr(self.deal, "kind", "") == "strips")
+
     def _device_engine_applies(self):
         a = self.slice_args
+        if self.conditional == "exact":
+            # the general sampler scores the exact conditional (cel_slice_locations does not): the options it runs
+            return (len(self.fields) == 1 and self._exact_on_device()
+                    and (not a.get("step_out", True) or a.get("doubling_step", True))
+                    and set(a) <= {"step_out", "doubling_step", "compwise", "numdir", "sigma", "max_steps_out"})
         return (len(self.fields) == 1 and not a.get("step_out", True) and a.get("compwise", True)
-                and set(a) <= {"step_out", "compwise", "sigma"} and self.conditional == "reference")
+                and set(a) <= {"step_out", "compwise", "sigma"})
+
+    def _resample_locations_exact_on_device(self, t0):
+        """the location step of the exact sweep on the device: cel_slice_sample(param 0) under CEL_OPT_SLICE_CONDITIONAL = 1.
+        The directions are drawn here from each chain's normal stream, exactly as resample_shapes draws them."""
+        import time
+        from .util.infer.slicesample import ChainStreams
+        f = self.fields[0]
+        sset = self._sources(f)
+        a = self.slice_args
+        seed = self.step_seed("location")
+        dirs = None if a.get("compwise", True) else ChainStreams(seed, np.arange(self.S)).directions(int(a.get("numdir", 2)), 2)
+        mine = self.active if self.deal is None else (self.active & self.deal.mask)
+        ids = np.where(mine, np.arange(self.S), -1).astype(np.int32)
+        new_u, _, st = f.iset.slice_sample(sset, 0, a.get("sigma", 1.0), seed, dirs=dirs, step_out=a.get("step_out", True),
+                                           max_steps_out=a.get("max_steps_out", 1000), chain_ids=ids, conditional="exact")
+        self.u = new_u
+        if getattr(f, "_uploaded", None) is not None:      # the device's catalogue moved with the chains: it IS the new state
+            f._uploaded = (f._uploaded[0], new_u.copy(), f._uploaded[2], f._uploaded[3])
+        self.timing["rounds"] += st["rounds"]
+        self.timing["evals"] += st["evals"]
+        self.timing["loc_launches"] = self.timing.get("loc_launches", 0) + st["launches"]
+        self.timing["location"] += time.perf_counter() - t0
+        return self.u
 
     def resample_locations(self):
         import time
@@ -707,7 +745,12 @@ class ModelGibbs(object):
         use_device = self.engine == "device" or (self.engine == "auto" and self._device_engine_applies())
         if use_device:
             if not self._device_engine_applies():
+                if self.conditional == "exact":
+                    raise ValueError("the device slice sampler scores the exact conditional on one field of whole, unmasked frames, "
+                                     "stepping out by doubling or not at all")
                 raise ValueError("the device slice sampler runs one field with step_out=False, compwise=True")
+            if self.conditional == "exact":
+                return self._resample_locations_exact_on_device(t0)
             f = self.fields[0]
             sset = self._sources(f)                        # the catalogue with the fluxes just drawn (other ranks' rows are
             # stale until the merge: a chain reads only its own source's counts)

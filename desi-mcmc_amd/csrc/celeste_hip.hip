@@ -178,6 +178,7 @@ struct cel_ctx {
     int split_full = 0;         // CEL_OPT_SPLIT_FULL_BOX
     int slice_fuse = SLICE_FUSE_DEFAULT;   // CEL_OPT_SLICE_FUSE
     int honour_mask = 0;        // CEL_OPT_HONOUR_MASK
+    int slice_conditional = 0;  // CEL_OPT_SLICE_CONDITIONAL
     int incremental = (getenv("CEL_INCREMENTAL") && atoi(getenv("CEL_INCREMENTAL")) == 0) ? 0 : 1;       // CEL_OPT_INCREMENTAL
     int tile_parts = (getenv("CEL_TILE_PARTS") && (atoi(getenv("CEL_TILE_PARTS")) == 1 || atoi(getenv("CEL_TILE_PARTS")) == 2 || atoi(getenv("CEL_TILE_PARTS")) == 4))
                          ? atoi(getenv("CEL_TILE_PARTS")) : 0;       // CEL_OPT_TILE_PARTS (the env var: the initial value, for A/B runs)
@@ -603,6 +604,11 @@ int cel_ctx_set_option(cel_ctx *c, int key, double v) {
         if (v != 0.0 && v != 1.0) return fail(CEL_ERR_INVALID, "CEL_OPT_HONOUR_MASK must be 0 or 1");
         c->honour_mask = (int)v;
         return CEL_OK;
+    case CEL_OPT_SLICE_CONDITIONAL:
+        static_assert(CEL_OPT_SLICE_CONDITIONAL == 18, "the key is 18 in every binding");
+        if (v != 0.0 && v != 1.0) return fail(CEL_ERR_INVALID, "CEL_OPT_SLICE_CONDITIONAL must be 0 (the reference's conditional) or 1 (the exact one)");
+        c->slice_conditional = (int)v;
+        return CEL_OK;
     case CEL_OPT_TILE_PARTS:
         if (v != 0.0 && v != 1.0 && v != 2.0 && v != 4.0) return fail(CEL_ERR_INVALID, "CEL_OPT_TILE_PARTS must be 0 (by the frame's size), 1, 2 or 4");
         c->tile_parts = (int)v;
@@ -664,6 +670,7 @@ int cel_ctx_get_option(cel_ctx *c, int key, double *v) {
     case CEL_OPT_SPLIT_FULL_BOX: *v = c->split_full; return CEL_OK;
     case CEL_OPT_SLICE_FUSE: *v = c->slice_fuse; return CEL_OK;
     case CEL_OPT_HONOUR_MASK: *v = c->honour_mask; return CEL_OK;
+    case CEL_OPT_SLICE_CONDITIONAL: *v = c->slice_conditional; return CEL_OK;
     case CEL_OPT_PROFILE: *v = (double)c->profile; return CEL_OK;
     case CEL_OPT_TILE_ORDER: *v = (double)c->tile_order; return CEL_OK;
     case CEL_OPT_TILE_ROWS: *v = c->tile_rows; return CEL_OK;
@@ -2261,6 +2268,12 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
                      double *x_out, double *llh_out, int64_t *stats) {
     if (!im || !src) return fail(CEL_ERR_INVALID, "cel_slice_sample: null argument");
     { int rm = refuse_masked(im, "cel_slice_sample"); if (rm) return rm; }
+    // CEL_OPT_SLICE_CONDITIONAL = 1: the exact conditional (k_slice_gen.h) -- the proposal's stamp mass on its own box and the
+    // cover test per round
+    const bool exact = im->ctx->slice_conditional == 1;
+    if (exact && (im->win_y0 != 0 || im->full_H != im->H))
+        return fail(CEL_ERR_INVALID, "cel_slice_sample: the exact conditional (CEL_OPT_SLICE_CONDITIONAL) is not supported on an image set "
+                                     "with a row window (cel_images_set_window): its cover test is not window-relative");
     if (src->B != im->B || src->ctx != im->ctx) return fail(CEL_ERR_INVALID, "sources do not match images");
     if (im->samp_S <= 0 || im->samp_S != src->S)
         return fail(CEL_ERR_INVALID, "cel_slice_sample needs a resident photon split of these %lld sources (have %lld)",
@@ -2280,8 +2293,8 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
     // one allocation, carved (Carver: once for the size, once for the pointers)
     SliceGen g;
     SliceState rs;
-    double *d_dirs, *d_ll;
-    int *d_owner, *d_ids, *d_list, *d_list_nz, *d_flags;
+    double *d_dirs, *d_ll, *d_mass = nullptr, *d_exact = nullptr;
+    int *d_owner, *d_ids, *d_list, *d_list_nz, *d_flags, *d_list_mass = nullptr;
     auto carve = [&](char *base) {
         Carver k{base};
         const size_t n = (size_t)S;
@@ -2314,6 +2327,11 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
         d_list = k.take<int>(2 * n * B * PLL_PARTS);          // the running chains' blocks (k_sg_live_jobs): dense, at the photons
         d_list_nz = k.take<int>(2 * n * B * PLL_PARTS);
         d_flags = k.take<int>(8, 16);
+        if (exact) {
+            d_mass = k.take<double>(2 * n * B);               // the proposals' stamp masses, per (slot, band)
+            d_exact = k.take<double>(2 * n);                  // the exact conditional's term per slot (k_sg_exact_terms)
+            d_list_mass = k.take<int>(2 * n * B);             // the running chains' mass jobs (k_sg_mass_jobs)
+        }
         return k.off;
     };
     const size_t need = carve(nullptr);
@@ -2352,14 +2370,19 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
     const int64_t DEAL_ALL_BELOW = 8192;          // (chain, slot, band) jobs: fewer than the GPU has wave slots for -- deal every job
     int64_t live = S;                             // chains running at the last readback
     // the first batch's block lists (every later one is built behind the batch before it); their counts come back now
-    int64_t n_dense = P * B, n_nz = 0;
-    if (c->variant != 0) {
+    int64_t n_dense = P * B, n_nz = 0, n_mass = 0;
+    const int nflags = exact ? 7 : 6;             // flag 6: the mass kernel's job count
+    if (c->variant != 0)
         hipLaunchKernelGGL(k_sg_live_jobs, dim3((unsigned)((S * B + 255) / 256)), dim3(256), 0, st, g, S, B,
                            (const int *)(use_nz ? im->d_nzmode : nullptr), (const int *)im->d_nnz, (const int4 *)im->d_snz, 0,
                            d_list, d_flags + 4, d_list_nz, d_flags + 5);
-        HIP_TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * 6, hipMemcpyDeviceToHost, st));
+    if (exact)
+        hipLaunchKernelGGL(k_sg_mass_jobs, dim3((unsigned)((S * B + 255) / 256)), dim3(256), 0, st, g, S, B, d_list_mass, d_flags + 6);
+    if (c->variant != 0 || exact) {
+        HIP_TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * nflags, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        n_dense = h_flags[4]; n_nz = h_flags[5];
+        if (c->variant != 0) { n_dense = h_flags[4]; n_nz = h_flags[5]; }
+        if (exact) n_mass = h_flags[6];
     }
     for (;;) {
         const int nb = (int)std::min<int64_t>(BATCH, (int64_t)max_rounds - queued);
@@ -2367,7 +2390,11 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
             hipLaunchKernelGGL(k_sg_propose, dim3(g256), dim3(256), 0, st, g, rs, S, param ? prop->d_shape : prop->d_radec, d_owner, d_flags,
                                queued == 0 ? 1 : 0);
             prop->gen = prop->full_gen = ++g_source_gen;
-            if ((rc = run_prep(im, prop, d_owner, 1))) return rc;      // the patch limits are fixed: no boxes
+            // the patch limits are fixed: no boxes -- but the exact conditional needs the proposals' own (cover test, mass)
+            if ((rc = run_prep(im, prop, d_owner, exact ? 0 : 1))) return rc;
+            if (exact)
+                hipLaunchKernelGGL(k_sg_cover, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, P, B, d_owner, g.pri,
+                                   (const int4 *)im->d_boxes, (const int *)im->d_status, (const int4 *)im->d_snz);
             if (c->variant == 0) {
                 int pi = prof_slot(c, CEL_K_PATCH_LL);
                 LAUNCH_EV(k_patch_ll<int>, dim3((unsigned)(P * B)), dim3(256), st, EV0(c, pi), EV1(c, pi), im->d_bands, B, P, im->d_recs,
@@ -2375,7 +2402,21 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
             } else {
                 launch_resident_ll(c, im, P, d_owner, d_ll, use_nz, {n_dense, d_list, nullptr}, {n_nz, d_list_nz, nullptr}, nullptr);
             }
-            hipLaunchKernelGGL(k_sg_consume, dim3(g256), dim3(256), 0, st, g, rs, S, B, ostr, (const double *)d_ll, d_flags);
+            if (exact) {
+                // the mass kernel proper, cel_stamp_mass_begin's plain branch, on the running chains' jobs (a slot that is not
+                // scored retires by its owner; a launch of 2 S B blocks that find nothing to do costs 0.15 ms, see there)
+                if (n_mass > 0)
+                    hipLaunchKernelGGL((k_patch_ll_hw<3, double>), dim3((unsigned)n_mass), dim3(64), 0, st, im->d_bands, B, P, im->d_recs,
+                                       (const int *)d_owner, (const int4 *)nullptr, (const int64_t *)nullptr, (const double *)nullptr,
+                                       (const double *)nullptr, im->H, im->W, (const int4 *)nullptr, c->tail_T, d_mass,
+                                       (const int *)d_list_mass);
+                hipLaunchKernelGGL(k_sg_exact_terms, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, P, B, (const int *)d_owner,
+                                   (const BandDev *)im->d_bands, (const double *)prop->d_counts, (const double *)d_mass,
+                                   (const int64_t *)im->d_soff, d_exact);
+                hipLaunchKernelGGL(k_sg_consume_exact, dim3(g256), dim3(256), 0, st, g, rs, S, B, ostr, (const double *)d_ll, d_flags,
+                                   (const double *)d_exact);
+            } else
+                hipLaunchKernelGGL(k_sg_consume, dim3(g256), dim3(256), 0, st, g, rs, S, B, ostr, (const double *)d_ll, d_flags);
             queued++;
         }
         if (c->variant != 0) {          // the next batch's blocks: the chains still running now
@@ -2384,11 +2425,16 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
                                (const int *)(use_nz ? im->d_nzmode : nullptr), (const int *)im->d_nnz, (const int4 *)im->d_snz,
                                (live * 2 * B <= DEAL_ALL_BELOW) ? 1 : 0, d_list, d_flags + 4, d_list_nz, d_flags + 5);
         }
-        HIP_TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * 6, hipMemcpyDeviceToHost, st));
+        if (exact) {
+            HIP_TRY(hipMemsetAsync(d_flags + 6, 0, sizeof(int), st));
+            hipLaunchKernelGGL(k_sg_mass_jobs, dim3((unsigned)((S * B + 255) / 256)), dim3(256), 0, st, g, S, B, d_list_mass, d_flags + 6);
+        }
+        HIP_TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * nflags, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));
         const int running = h_flags[0], err = h_flags[1];
         if (c->variant != 0) { n_dense = h_flags[4]; n_nz = h_flags[5]; }
+        if (exact) n_mass = h_flags[6];
         live = running;
         if (err & 1) return fail(CEL_ERR_INVALID, "Slice sampler got a NaN");
         if (err & 2) return fail(CEL_ERR_INVALID, "Slice sampler shrank to zero!");

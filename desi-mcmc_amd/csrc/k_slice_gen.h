@@ -154,9 +154,11 @@ __device__ inline void sg_accept_advance(const SliceGen &g, int64_t s, bool firs
     }
 }
 
-// consume the round's log-likelihoods: ll_pb holds PLL_PARTS slots per (proposal slot, band), added in order
-__global__ void __launch_bounds__(256)
-k_sg_consume(SliceGen g, SliceState rs, int64_t S, int B, int nparts, const double *__restrict__ ll_pb, int *__restrict__ flags) {
+// consume the round's log-likelihoods: ll_pb holds PLL_PARTS slots per (proposal slot, band), added in order.  exact: the
+// exact conditional's term per proposal slot (k_sg_exact_terms), or nullptr -- the reference's conditional; the two kernels
+// below pass a constant, so that the reference's k_sg_consume is compiled without the term
+__device__ __forceinline__ void sg_consume(const SliceGen &g, const SliceState &rs, int64_t S, int B, int nparts,
+                                           const double *__restrict__ ll_pb, int *__restrict__ flags, const double *__restrict__ exact) {
 #pragma clang fp contract(off)
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool active = false;
@@ -176,6 +178,7 @@ k_sg_consume(SliceGen g, SliceState rs, int64_t S, int B, int nparts, const doub
                         for (int k = 1; k < nparts; k++) x += p[k];
                         acc += x;
                     }
+                    if (exact) acc += exact[2 * s + q];             // ll = patch sum; ll += exact; out = prior + ll
                     v[q] = lp + acc;
                 } else {
                     v[q] = -INFINITY;
@@ -246,6 +249,84 @@ k_sg_consume(SliceGen g, SliceState rs, int64_t S, int B, int nparts, const doub
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(flags, __popcll(m));
     for (int o = 32; o > 0; o >>= 1) scored += __shfl_xor(scored, o);
     if ((threadIdx.x & 63) == 0 && scored) atomicAdd(flags + 2, scored);          // evaluations so far
+}
+
+__global__ void __launch_bounds__(256)
+k_sg_consume(SliceGen g, SliceState rs, int64_t S, int B, int nparts, const double *__restrict__ ll_pb, int *__restrict__ flags) {
+    sg_consume(g, rs, S, B, nparts, ll_pb, flags, nullptr);
+}
+
+// ---- the exact conditional (CEL_OPT_SLICE_CONDITIONAL = 1; ModelGibbs._exact_terms on the device) -----------------------------
+// A proposal is scored as  prior + (patch log-likelihood + e),  e = -sum_b (counts_b * (mass_b - wsum_b)) * has_patch_b  with
+// mass_b the proposal's unit stamp summed over ITS OWN box (k_patch_ll_hw<3>), and has probability zero where its box does not
+// cover every photon of the source (DESIGN Q20).  A round: k_sg_propose, k_prep WITH boxes, k_sg_cover, the likelihoods, the
+// masses, k_sg_exact_terms, k_sg_consume_exact.
+__global__ void __launch_bounds__(256)
+k_sg_consume_exact(SliceGen g, SliceState rs, int64_t S, int B, int nparts, const double *__restrict__ ll_pb, int *__restrict__ flags,
+                   const double *__restrict__ exact /* 2S */) {
+    sg_consume(g, rs, S, B, nparts, ll_pb, flags, exact);
+}
+
+// the cover test: in every band where the source holds a photon the proposal has a stamp (status > 0) and its box contains
+// the source's photon rectangle (the resident split's k_patch_nzbox rectangles: what cel_samples_photon_rects returns).  A
+// proposal that fails is never rendered -- the rule the prior's -inf follows: its slot retires (owner -1: its likelihood and
+// mass jobs return at their first instructions) and k_sg_consume reads -inf from pri, counting the point all the same.
+__global__ void __launch_bounds__(256)
+k_sg_cover(int64_t P /* 2S proposal slots */, int B, int *__restrict__ owner, double *__restrict__ pri,
+           const int4 *__restrict__ boxes /* [B][P], as k_prep has just written them */, const int *__restrict__ status /* [B][P] */,
+           const int4 *__restrict__ nzbox /* [S][B] */) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    const int s = owner[p];
+    if (s < 0) return;
+    bool covered = true;
+    for (int b = 0; b < B; b++) {
+        const int4 r = nzbox[(int64_t)s * B + b];
+        if (!(r.y > r.x && r.w > r.z)) continue;                    // no photon of the source in this band
+        const int4 q = boxes[(int64_t)b * P + p];
+        covered = covered && status[(int64_t)b * P + p] > 0 && q.z <= r.z && q.w >= r.w && q.x <= r.x && q.y >= r.y;
+    }
+    if (!covered) {
+        pri[p] = -INFINITY;
+        owner[p] = -1;
+    }
+}
+
+// the mass kernel's jobs of the next rounds: both slots x every band of every running chain (k_sg_live_jobs' twin: built at the
+// end of a batch, the count rides back with the batch's flags).  A slot that is not scored retires in the kernel by its owner.
+// Without stepping out a chain never needs its second slot (SG_OUT_DOUBLE is not entered, and the interval the shrink steps
+// start from is sigma wide, never > 1.1 sigma: no SG_ACCEPT): the list holds the first slots only, half the blocks.
+__global__ void __launch_bounds__(256)
+k_sg_mass_jobs(SliceGen g, int64_t S, int B, int *__restrict__ list, int *__restrict__ count) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;        // (chain, band)
+    const int64_t s = (i < S * B) ? i / B : 0;
+    const int b = (int)(i - s * B);
+    const bool alive = i < S * B && g.phase[s] != SG_FINAL;
+    const int per = g.step_out ? 2 : 1;
+    const int at = wave_reserve(count, alive ? per : 0);                     // one atomic per wave
+    if (!alive) return;
+    list[at] = (int)((2 * s) * B + b);
+    if (per > 1) list[at + 1] = (int)((2 * s + 1) * B + b);
+}
+
+// e per scored proposal slot, in the host's order (ModelGibbs._exact_terms: -(pc * (mass - wsum) * has_patch).sum(axis=1))
+__global__ void __launch_bounds__(256)
+k_sg_exact_terms(int64_t P, int B, const int *__restrict__ owner, const BandDev *__restrict__ bands,
+                 const double *__restrict__ pcounts /* [P][B] */, const double *__restrict__ mass /* [P][B] */,
+                 const int64_t *__restrict__ soff /* [S * B + 1]: the sample patches' offsets */, double *__restrict__ e /* P */) {
+#pragma clang fp contract(off)
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    const int s = owner[p];
+    if (s < 0) return;
+    double acc = 0.0;
+    for (int b = 0; b < B; b++) {
+        const double wsum = bands[b].w[0] + bands[b].w[1] + bands[b].w[2];
+        const int64_t ob = (int64_t)s * B + b;
+        const double has_patch = soff[ob + 1] > soff[ob] ? 1.0 : 0.0;
+        acc += (pcounts[p * B + b] * (mass[p * B + b] - wsum)) * has_patch;
+    }
+    e[p] = -acc;
 }
 
 // the proposal set of a call: two slots per chain, everything but the sampled parameter copied from the catalogue

@@ -417,11 +417,15 @@ class ImageSet(object):
         return radec, llh, dict(rounds=int(stats[0]), evals=int(stats[1]), algorithmic_bytes=int(stats[2]), launches=int(stats[3]))
 
     def slice_sample(self, sources, param, sigma, seed, dirs=None, step_out=True, max_steps_out=1000, phi_max=180.,
-                     chain_ids=None, max_rounds=20000):
+                     chain_ids=None, max_rounds=20000, conditional="reference"):
         """slicesample with random directions / stepping out by doubling for every source's location (param 0) or every
         galaxy's shape (param 1) on the device (cel_slice_sample).  dirs (S, numdir, D) unit directions or None =
         component-wise.  The sampled parameter is updated in place on the device.
+        conditional="exact": the exact conditional of ModelGibbs(conditional="exact") -- the proposal's stamp mass on its own
+        box, -inf where its box does not cover the source's photons (CEL_OPT_SLICE_CONDITIONAL, set around the call).
         -> (x[S,D], llh[S], dict(rounds, evals))"""
+        if conditional not in ("reference", "exact"):
+            raise ValueError("conditional must be 'reference' or 'exact'")
         S = sources.S
         D = 4 if param else 2
         x, llh = np.zeros((S, D)), np.zeros(S)
@@ -437,7 +441,9 @@ class ImageSet(object):
             if dirs.ndim != 3 or dirs.shape[0] != S or dirs.shape[2] != D:
                 raise ValueError("dirs must be (S, numdir, %d)" % D)
             numdir = dirs.shape[1]
+        was = self.ctx.get_option(L.CEL_OPT_SLICE_CONDITIONAL)
         try:
+            self.ctx.set_option(L.CEL_OPT_SLICE_CONDITIONAL, 1 if conditional == "exact" else 0)
             L.check(L.lib().cel_slice_sample(self._h, sources._h, int(param), None if ids is None else ids.ctypes.data_as(L.c_int32_p),
                                              None if dirs is None else L.dptr(dirs), int(numdir), 1 if step_out else 0,
                                              int(max_steps_out), float(sigma), float(phi_max), C.c_uint64(int(seed) & (2 ** 64 - 1)),
@@ -446,6 +452,8 @@ class ImageSet(object):
             if "Slice sampler" in str(e):
                 raise Exception(str(e))
             raise
+        finally:
+            self.ctx.set_option(L.CEL_OPT_SLICE_CONDITIONAL, was)
         return x, llh, dict(rounds=int(stats[0]), evals=int(stats[1]), launches=int(stats[3]))
 
     def sample_sums(self):

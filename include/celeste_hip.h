@@ -106,6 +106,19 @@ enum {
                                  prior).  On a set without a NaN the option changes nothing: the same kernels, launches and bits.
                                  cel_slice_locations, cel_slice_sample and the isolated forms of cel_patch_loglik[_multi] refuse a
                                  masked set whatever this option says */
+    /* exact conditional: */ CEL_OPT_SLICE_CONDITIONAL = 18, /* what cel_slice_sample scores.  0 (default): the reference's conditional, as before: the same
+                                 kernels, launches and bits.  1: the EXACT conditional of ModelGibbs(conditional="exact") (DESIGN Q20):
+                                 a proposal of a chain with expected photons c_b scores  prior + (sum_b mode-0 likelihood + e),
+                                 e = -sum_b (c_b * (mass_b - sum of the band's PSF weights)) * [the source has a sample patch in b],
+                                 mass_b = the proposal's unit stamp summed over its OWN box (cel_stamp_mass's kernel), and -inf -- never
+                                 rendered, counted in `evals` -- where in a band that holds a photon of the source the proposal has no
+                                 stamp or its box does not contain the source's photon rectangle (cel_samples_photon_rects).  Per round
+                                 the proposals' records are written WITH their boxes, then k_sg_cover, the likelihoods, the masses,
+                                 k_sg_exact_terms; no further host synchronisation.  It applies to cel_slice_sample ALONE:
+                                 cel_slice_locations does not read it and keeps its code, launches and bits -- the location step under
+                                 the exact conditional is cel_slice_sample(param 0, dirs = NULL, step_out = 0).  Under 1 a masked set is
+                                 refused as under 0, and so is an image set with a row window (cel_images_set_window: the cover test
+                                 is not window-relative).  Any other value: CEL_ERR_INVALID */
     CEL_OPT_TILE_PARTS = 13, /* how many one-wave blocks share a render tile of the general 32 x 64 kernel.  0 (default) = by
                                the frame's size: 4 for at most 512 tiles, 2 for at most 3 072, else 1 -- a frame of few tiles
                                (one rank's row strip of a field cut 8 ways, a 51 x 51 real field) finishes when its heaviest
@@ -438,7 +451,8 @@ int cel_slice_locations(cel_images *img, cel_sources *src, const int32_t *chain_
  *              <= 0: no prior.  (Any other prior: the host engine.)
  *   chain_ids  as cel_slice_locations; a star is left alone under param 1
  *   x_out      S*D (host, may be NULL): the new states; they also REPLACE src's on the device.  llh_out, stats: as
- *              cel_slice_locations (stats[2] = 0) */
+ *              cel_slice_locations (stats[2] = 0)
+ * CEL_OPT_SLICE_CONDITIONAL = 1: the exact conditional in place of the reference's (see the option). */
 int cel_slice_sample(cel_images *img, cel_sources *src, int param, const int32_t *chain_ids, const double *dirs, int numdir,
                      int step_out, int max_steps_out, double sigma, double phi_max, uint64_t seed, int max_rounds,
                      double *x_out, double *llh_out, int64_t *stats);
