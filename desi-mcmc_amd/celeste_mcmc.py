@@ -18,7 +18,8 @@ from .sources import SamplePatch
 _M64 = (1 << 64) - 1
 # one tag per randomised step of a sweep: no two steps share a stream key for any seed (with seed = 0 the plain
 # `seed * prime + sweep` forms all collapsed to `sweep`, and a source's location, shape and flux draws were one sequence)
-STEP_TAGS = dict(split=0x53504C4954000001, flux=0x464C555800000002, location=0x4C4F434154000003, shape=0x5348415045000004)
+STEP_TAGS = dict(split=0x53504C4954000001, flux=0x464C555800000002, location=0x4C4F434154000003, shape=0x5348415045000004,
+                 type=0x5459504500000005)
 
 
 def _mix64(z):
@@ -30,7 +31,7 @@ def _mix64(z):
 
 
 def step_seed(seed, step, sweep, k=0):
-    """the stream seed of one step (`split`, `flux`, `location`, `shape`) of sweep number `sweep` (of field k): a hash of
+    """the stream seed of one step (`split`, `flux`, `location`, `shape`, `type`) of sweep number `sweep` (of field k): a hash of
     all of them, so that the Gibbs blocks draw from unrelated streams whatever the chain's seed is"""
     return _mix64((_mix64(_mix64(int(seed) & _M64) ^ STEP_TAGS[step]) + int(sweep)) & _M64 ^ (int(k) * 0xD6E8FEB86659FD93 & _M64))
 
@@ -216,8 +217,11 @@ class ModelGibbs(object):
 
     def __init__(self, fields, typ, u, fluxes, shape, seed=0, flux_a_0=5., flux_b_0=.005, slice_args=None, engine="auto",
                  deal=None, shape_args=None, shape_logprior=None, phi_period=180., shape_mass="reference", conditional="reference",
-                 mask="refuse"):
+                 mask="refuse", type_log_odds=0.0):
         self.fields = list(fields)
+        # the type step's log prior odds, galaxy : star (resample_types; sweep(types=True))
+        self.type_log_odds = float(type_log_odds)
+        self.type_engine = None                 # "host" / "device": the type step's engine where it is not `engine`'s (tools/type_move_cost.py)
         # mask="refuse": masked data is refused up front.  mask="honour": the sweep on masked images (NaN counts) -- no photons at
         # a masked pixel (CEL_OPT_HONOUR_MASK around the split), the flux step's masses over the unmasked pixels, a sky step that
         # counts unmasked pixels.  Under conditional="exact" only: the reference's location conditional charges a source
@@ -303,7 +307,8 @@ class ModelGibbs(object):
             raise ValueError("engine must be auto, device or host")
         self.engine = engine
         self.sweeps = 0
-        self.timing = dict(split=0.0, flux=0.0, location=0.0, rounds=0, evals=0, shape=0.0, shape_rounds=0, shape_evals=0)
+        self.timing = dict(split=0.0, flux=0.0, location=0.0, rounds=0, evals=0, shape=0.0, shape_rounds=0, shape_evals=0,
+                           type=0.0, type_evals=0, type_accepted=0)
         # ONE chain over several GPUs: `deal` (dist.SourceDeal) names the sources this rank
         # updates.  Every rank runs the same photon split (counter-based draws: the replicas are bitwise equal) and
         # the same host draws (same seed), updates the fluxes and locations of ITS sources only, and the ranks
@@ -577,13 +582,15 @@ class ModelGibbs(object):
         return self.fluxes
 
     # -- Source.resample_location: sources.py:308-319, all sources in lock-step ------------------------
-    def location_loglik(self, idx, U):
-        """Source.location_likelihood (sources.py:185-186) of chain idx[i] at U[i], summed over fields"""
+    def location_loglik(self, idx, U, typ=None, shape=None):
+        """Source.location_likelihood (sources.py:185-186) of chain idx[i] at U[i], summed over fields.  typ / shape: the
+        proposals' own types and shapes where they are not the chains' (the type step's two slots per chain)"""
         from . import field as _field
         idx = np.asarray(idx, dtype=np.int64)
         P = idx.shape[0]
         ll = np.zeros(P)
-        typ, shape = self.typ[idx], self.shape[idx]
+        typ = self.typ[idx] if typ is None else np.ascontiguousarray(typ, dtype=np.int32)
+        shape = self.shape[idx] if shape is None else np.asarray(shape, dtype=np.float64).reshape(P, 4)
         owner = idx.astype(np.int32)
         for f in self.fields:
             if f.prop is None or f.prop.capacity < P:
@@ -782,35 +789,150 @@ class ModelGibbs(object):
         self.timing["location"] += time.perf_counter() - t0
         return self.u
 
-    def sweep(self, shapes=False):
+    # -- Source.resample_type: sources.py:247-306, all sources at once ---------------------------------------------
+    def sample_shape_prior(self, seed, ids):
+        """one draw per chain from the normalised form of galaxy_shape_prior_constrained, from ChainStreams(seed, ids): theta,
+        rho ~ U(0, 1), phi ~ U(0, phi_period), sigma = 1 / sqrt(z^2 / 2 - log u) with z the stream's normal and u its uniform
+        -- z^2 / 2 ~ Gamma(1/2, 1) and -log u ~ Gamma(1, 1), so 1 / sigma^2 ~ Gamma(3/2, 1), whose density in sigma is
+        proportional to sigma^-4 exp(-1 / sigma^2): the prior's.  -> (len(ids), 4)"""
+        from .util.infer.slicesample import ChainStreams
+        cs = ChainStreams(seed, ids)
+        every = np.arange(len(ids))
+        theta, rho = cs.uniform(every), cs.uniform(every)
+        phi = cs.uniform(every) * self.phi_period
+        z, u = cs.normal(every), cs.uniform(every)
+        sigma = 1.0 / np.sqrt(z * z / 2.0 - np.log(u))
+        return np.stack([theta, sigma, phi, rho], axis=1)
+
+    def _type_engine_on_device(self):
+        """the device runs the type step (cel_slice_sample, param 2) where the exact slice engine applies: one field, and
+        under conditional="exact" whole, unmasked frames"""
+        ok = len(self.fields) == 1 and self.mask != "honour" and (self.conditional != "exact" or self._exact_on_device())
+        engine = self.type_engine or self.engine
+        if engine == "device" and not ok:
+            raise ValueError("the device type move runs one field of whole, unmasked frames")
+        return ok and engine != "host"
+
+    def resample_types(self, proposal=None):
+        """Source.resample_type (sources.py:247-306) for every source at once: one Metropolis-Hastings star <-> galaxy proposal
+        per source against the current photon split.  Given the split a source's conditional involves no other source, so the
+        move of all sources at once is exact.  A star is offered a galaxy shape, a galaxy the star at its location with its
+        expected counts;  log alpha = (score(proposal) - score(current)) + h,  the scores those of the location and shape
+        steps' conditional, accepted iff log u < log alpha with u the first uniform of the chain's stream of
+        step_seed("type").
+        proposal: None -- a star's shape is drawn from the normalised shape prior (sample_shape_prior, the streams of
+        step_seed("type", 1): not the accept test's), so proposal and prior cancel and h = +type_log_odds for star -> galaxy,
+        -type_log_odds for the reverse; or a callable(model) -> (shapes[S, 4], h[S]) with h everything of the log acceptance
+        ratio that is not the likelihood (prior odds, proposal densities, Jacobian).  A custom shape prior needs one."""
+        import time
+        from .util.infer.slicesample import ChainStreams
+        if proposal is None and not self._default_shape_prior:
+            raise ValueError("resample_types: a custom shape prior (shape_logprior=) needs a custom proposal= "
+                             "(a callable returning (shapes[S, 4], h[S])): the default proposal draws from the built-in prior")
+        on_device = self._type_engine_on_device()
+        t0 = time.perf_counter()
+        ids_all = np.arange(self.S)
+        if proposal is None:
+            shapes = self.sample_shape_prior(self.step_seed("type", 1), ids_all)
+            h = np.where(self.typ == 0, self.type_log_odds, -self.type_log_odds).astype(np.float64)
+        else:
+            shapes, h = proposal(self)
+            shapes = np.array(shapes, dtype=np.float64).reshape(self.S, 4)
+            h = np.array(h, dtype=np.float64).reshape(self.S)
+        seed = self.step_seed("type")
+        mine = self.active if self.deal is None else (self.active & self.deal.mask)
+        runs = mine & ((self.typ == 0) | (self.typ == 1))
+        if not np.all(np.isfinite(h[runs])):
+            raise ValueError("resample_types: h is not finite for a chain that moves")
+        h = np.where(runs, h, 0.0)
+        if on_device:
+            f = self.fields[0]
+            sset = self._sources(f)
+            ids = np.where(runs, ids_all, -1).astype(np.int32)
+            typ, shape, _, st = f.iset.type_move(sset, shapes, h, seed, chain_ids=ids, conditional=self.conditional)
+            self.typ, self.shape = typ, shape
+            if getattr(f, "_uploaded", None) is not None:      # the device's catalogue moved with the chains: it IS the new state
+                f._uploaded = (typ.copy(), f._uploaded[1], f._uploaded[2], shape.copy())
+            evals, accepted = st["evals"], st["accepted"]
+        else:
+            act = np.nonzero(runs)[0]
+            evals = accepted = 0
+            if act.size:
+                n = act.size
+                to_gal = self.typ[act] == 0
+                p_shape = np.where(to_gal[:, None], shapes[act], self.shape[act])
+                inside = ~to_gal | ((p_shape[:, 0] > 0.) & (p_shape[:, 0] < 1.) & (p_shape[:, 1] > 0.) &
+                                    (p_shape[:, 3] > 0.) & (p_shape[:, 3] < 1.))
+                # two slots per chain: the current row, the flipped row; a shape outside the support is never rendered
+                slot_idx = np.concatenate([act, act[inside]])
+                slot_typ = np.concatenate([self.typ[act], 1 - self.typ[act][inside]])
+                slot_shape = np.concatenate([self.shape[act], p_shape[inside]], axis=0)
+                v = self.location_loglik(slot_idx, self.u[slot_idx], typ=slot_typ, shape=slot_shape)
+                v0 = v[:n]
+                v1 = np.full(n, -np.inf)
+                v1[inside] = v[n:]
+                if not np.all(v0 > -np.inf):
+                    raise ValueError("resample_types: a state outside its own conditional (its current row scores -inf)")
+                with np.errstate(invalid="ignore"):
+                    la = (v1 - v0) + h[act]
+                    log_u = np.log(ChainStreams(seed, act).uniform(np.arange(n)))
+                    acc = log_u < la
+                won = act[acc]
+                self.typ = self.typ.copy()
+                self.typ[won] = 1 - self.typ[won]
+                self.shape[won] = p_shape[acc]
+                evals, accepted = 2 * n, int(acc.sum())
+        self.timing["type_evals"] += evals
+        self.timing["type_accepted"] += accepted
+        self.timing["type"] += time.perf_counter() - t0
+        return self.typ
+
+    def _check_types(self, types):
+        if types and not self._default_shape_prior:
+            raise ValueError("sweep(types=True) draws a star's galaxy shape from the built-in shape prior: with a custom shape prior "
+                             "(shape_logprior=) call resample_types(proposal=) with a custom proposal instead")
+        if types and self.deal is not None and getattr(self.deal, "kind", "") == "strips":
+            raise ValueError("sweep(types=True) runs on whole frames (a replicated deal or one rank): a source that changes its "
+                             "type changes its box, and a strip's window was cut for the boxes it was dealt")
+
+    def sweep(self, shapes=False, types=False):
         """CelesteBase.resample_model: every field's photons, then every source (fluxes, location) -- and, with
         shapes=True, the galaxies' shapes as sample_galaxy_params does (celeste_mcmc.py:166-243;
-        Source.resample_shape is a stub in the reference, sources.py:321-325, so it is off by default)"""
+        Source.resample_shape is a stub in the reference, sources.py:321-325, so it is off by default); with types=True the
+        star <-> galaxy move last (resample_types)"""
+        self._check_types(types)
         solo = self.deal is not None and getattr(self.deal, "solo", False) and self.deal.world > 1
         if solo:        # one rank of an N-rank chain played alone (bench.py --as-rank): the other ranks' rows keep their values
-            before = (self.u.copy(), self.fluxes.copy(), self.shape.copy())
+            before = (self.u.copy(), self.fluxes.copy(), self.shape.copy(), self.typ.copy())
         self.resample_photons()
         self.resample_fluxes()
         self.resample_locations()
         if shapes:
             self.resample_shapes()
-        self.merge_ranks()
+        if types:
+            self.resample_types()
+        self.merge_ranks(types=types)
         if solo:
             other = ~self.deal.mask
             self.u[other], self.fluxes[other], self.shape[other] = before[0][other], before[1][other], before[2][other]
+            if types:
+                self.typ[other] = before[3][other]
         self.sweeps += 1
 
-    def sweep_reversed(self, shapes=False):
+    def sweep_reversed(self, shapes=False, types=False):
         """The sweep's blocks in REVERSE order -- (shapes,) locations, fluxes, sky levels, photons -- on the augmented state (sources, sky
-        levels, the current photon split): the time reversal of sweep().  Every block is reversible with respect to its
+        levels, the current photon split): the time reversal of sweep() (types=True: the type move first).  Every block is reversible with respect to its
         conditional (Gibbs draws; slice updates whose axis order is shuffled per call), so a chain run backwards from a state
         is a chain run with this.  It needs a photon split of the current state to start from (_split_photons()).  Used by the
         calibration test (tests/test_calibration.py) to put the true parameters at a random position of a stationary chain;
         a single rank."""
         if self.deal is not None and self.deal.world > 1:
             raise ValueError("sweep_reversed runs a single-rank chain")
+        self._check_types(types)
         if not self.noise_sums:
             raise ValueError("sweep_reversed needs a photon split of the current state: call _split_photons() first")
+        if types:
+            self.resample_types()
         if shapes:
             self.resample_shapes()
         self.resample_locations()
@@ -819,15 +941,19 @@ class ModelGibbs(object):
         self._split_photons()
         self.sweeps += 1
 
-    def merge_ranks(self):
-        """one chain over several GPUs: every rank's new fluxes and locations to every rank (one all-gather)"""
+    def merge_ranks(self, types=False):
+        """one chain over several GPUs: every rank's new fluxes and locations to every rank (one all-gather); types=True: the
+        types too, as one more column of it (an int32 is exact in a double)"""
         if self.deal is None or self.deal.world == 1:
             return
         import time
         t0 = time.perf_counter()
-        both = self.deal.merge(np.concatenate([self.u, self.fluxes, self.shape], axis=1))
+        cols = [self.u, self.fluxes, self.shape] + ([self.typ[:, None].astype(np.float64)] if types else [])
+        both = self.deal.merge(np.concatenate(cols, axis=1))
         self.u, self.fluxes, self.shape = (np.ascontiguousarray(both[:, :2]), np.ascontiguousarray(both[:, 2:7]),
-                                           np.ascontiguousarray(both[:, 7:]))
+                                           np.ascontiguousarray(both[:, 7:11]))
+        if types:
+            self.typ = np.ascontiguousarray(both[:, 11]).astype(np.int32)
         self.timing["merge"] = self.timing.get("merge", 0.0) + time.perf_counter() - t0
 
     def log_likelihood(self):

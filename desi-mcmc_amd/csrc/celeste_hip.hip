@@ -94,6 +94,7 @@ static int fail(int code, const char *fmt, ...) {
 #include "k_misc.h"
 #include "k_patch_ll.h"
 #include "k_slice_gen.h"
+#include "k_type_move.h"
 #include "k_estep.h"
 #include "k_grad.h"
 #include "k_split.h"
@@ -2262,6 +2263,153 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
     return CEL_OK;
 }
 
+// The star <-> galaxy move (k_type_move.h): cel_slice_sample's param 2, after its refusals.  One Metropolis-Hastings proposal
+// per chain against the resident split, both slots of every running chain scored in one round of the slice samplers' launches.
+static int slice_type_move(cel_images *im, cel_sources *src, const int32_t *chain_ids, const double *dirs, int numdir,
+                           uint64_t seed, double *x_out, double *llh_out, int64_t *stats) {
+    if (!dirs || numdir != 1)
+        return fail(CEL_ERR_INVALID, "cel_slice_sample: the type move (param 2) needs dirs = S rows of (theta, sigma, phi, rho, h) and numdir = 1");
+    cel_ctx *c = im->ctx;
+    const int B = im->B;
+    const int64_t S = src->S;
+    for (int64_t s = 0; s < S; s++)
+        if (!(chain_ids && chain_ids[s] < 0) && !std::isfinite(dirs[5 * s + 4]))
+            return fail(CEL_ERR_INVALID, "cel_slice_sample: the type move's h of chain %lld is not finite", (long long)s);
+    const bool exact = c->slice_conditional == 1;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const int ostr = (c->variant != 0) ? PLL_PARTS : 1;
+    const bool lists = c->variant != 0;
+    // one allocation, carved (Carver: once for the size, once for the pointers)
+    TypeMove tm;
+    double *d_dirs, *d_ll, *d_out, *d_mass = nullptr, *d_exact = nullptr;
+    int *d_owner, *d_ids, *d_list, *d_list_nz, *d_flags, *d_flag, *d_list_mass = nullptr;
+    auto carve = [&](char *base) {
+        Carver k{base};
+        const size_t n = (size_t)S;
+        tm.log_u = k.take<double>(n);
+        tm.h = k.take<double>(n);
+        tm.pri = k.take<double>(2 * n);
+        d_dirs = k.take<double>(5 * n);
+        d_ll = k.take<double>(2 * n * B * ostr);
+        if (exact) {
+            d_mass = k.take<double>(2 * n * B);               // the slots' stamp masses, per (slot, band)
+            d_exact = k.take<double>(2 * n);                  // the exact conditional's term per slot (k_sg_exact_terms)
+        }
+        d_out = k.take<double>(6 * n);                        // the new type and shape per chain, then log alpha per chain
+        d_flag = k.take<int>(n);                              // right behind d_out: one readback takes both
+        tm.run = k.take<int>(n);
+        d_owner = k.take<int>(2 * n);
+        d_ids = k.take<int>(n);
+        d_list = k.take<int>(lists ? 2 * n * B * PLL_PARTS : 0);
+        d_list_nz = k.take<int>(lists ? 2 * n * B * PLL_PARTS : 0);
+        if (exact) d_list_mass = k.take<int>(2 * n * B);
+        d_flags = k.take<int>(8, 16);                         // [1] error bits, [4] / [5] dense / photon-list blocks, [6] mass jobs
+        return k.off;
+    };
+    const size_t need = carve(nullptr);
+    HIP_TRY(im->d_sgen.grow(need, need + need / 4, st));
+    carve(im->d_sgen);
+    if (!im->sgen_prop || im->sgen_prop->cap < 2 * S) {
+        im->sgen_prop.reset();
+        cel_sources *np = nullptr;
+        int rc0 = cel_sources_create(c, 2 * S + S / 2 + 16, B, &np);
+        if (rc0) return rc0;
+        im->sgen_prop.reset(np);
+    }
+    cel_sources *prop = im->sgen_prop.get();
+    const int64_t P = 2 * S;
+    if (S == 0) {
+        if (stats) { stats[0] = 1; stats[1] = 0; stats[2] = 0; stats[3] = 0; }
+        return CEL_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(d_dirs, dirs, sizeof(double) * 5 * S, hipMemcpyHostToDevice, st));
+    if (chain_ids) HIP_TRY(hipMemcpyAsync(d_ids, chain_ids, sizeof(int) * S, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));                        // pageable sources must stay valid
+    HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(int) * 8, st));
+    const unsigned g256 = (unsigned)((S + 255) / 256), p256 = (unsigned)((P + 255) / 256), j256 = (unsigned)((S * B + 255) / 256);
+    hipLaunchKernelGGL(k_tm_fill, dim3(p256), dim3(256), 0, st, tm, S, B, (const int *)src->d_type, (const double *)src->d_radec,
+                       (const double *)src->d_counts, (const double *)src->d_shape, (const double *)d_dirs,
+                       chain_ids ? (const int *)d_ids : (const int *)nullptr, (const int64_t *)im->d_soff, (unsigned long long)seed,
+                       prop->d_type, prop->d_radec, prop->d_counts, prop->d_shape, d_owner);
+    prop->S = P;
+    prop->n_gal = -1;
+    prop->gen = prop->full_gen = ++g_source_gen;
+    const bool use_nz = im->nz_valid && c->variant != 0;
+    int64_t n_dense = P * B, n_nz = 0, n_mass = 0;
+    int *h_flags = c->mail->sh.slice_flags;
+    if (lists || exact) {
+        int64_t live = S;
+        if (chain_ids) { live = 0; for (int64_t s = 0; s < S; s++) live += chain_ids[s] >= 0; }
+        hipLaunchKernelGGL(k_tm_jobs, dim3(j256), dim3(256), 0, st, tm, S, B, (const int *)(use_nz ? im->d_nzmode : nullptr),
+                           (const int *)im->d_nnz, (const int4 *)im->d_snz, (live * 2 * B <= 8192) ? 1 : 0,
+                           lists ? d_list : (int *)nullptr, d_flags + 4, d_list_nz, d_flags + 5, d_list_mass, d_flags + 6);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * 7, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (lists) { n_dense = h_flags[4]; n_nz = h_flags[5]; }
+        if (exact) n_mass = h_flags[6];
+    }
+    // the slots' records, with their own boxes under the exact conditional (cover test, mass); otherwise the patch limits are fixed
+    int rc = run_prep(im, prop, d_owner, exact ? 0 : 1);
+    if (rc) return rc;
+    if (exact)
+        hipLaunchKernelGGL(k_sg_cover, dim3(p256), dim3(256), 0, st, P, B, d_owner, tm.pri, (const int4 *)im->d_boxes,
+                           (const int *)im->d_status, (const int4 *)im->d_snz);
+    int64_t launches = 0;
+    if (c->variant == 0) {
+        int pi = prof_slot(c, CEL_K_PATCH_LL);
+        LAUNCH_EV(k_patch_ll<int>, dim3((unsigned)(P * B)), dim3(256), st, EV0(c, pi), EV1(c, pi), im->d_bands, B, P, im->d_recs,
+                  (const int *)d_owner, im->d_sbox, im->d_soff, (const int *)im->d_samp, im->d_nelec, im->H, im->W, 0, d_ll);
+        launches = 1;
+    } else {
+        launch_resident_ll(c, im, P, d_owner, d_ll, use_nz, {n_dense, d_list, nullptr}, {n_nz, d_list_nz, nullptr}, nullptr);
+        launches = (n_dense > 0) + (n_nz > 0);
+    }
+    if (exact) {
+        if (n_mass > 0)
+            hipLaunchKernelGGL((k_patch_ll_hw<3, double>), dim3((unsigned)n_mass), dim3(64), 0, st, im->d_bands, B, P, im->d_recs,
+                               (const int *)d_owner, (const int4 *)nullptr, (const int64_t *)nullptr, (const double *)nullptr,
+                               (const double *)nullptr, im->H, im->W, (const int4 *)nullptr, c->tail_T, d_mass,
+                               (const int *)d_list_mass);
+        hipLaunchKernelGGL(k_sg_exact_terms, dim3(p256), dim3(256), 0, st, P, B, (const int *)d_owner,
+                           (const BandDev *)im->d_bands, (const double *)prop->d_counts, (const double *)d_mass,
+                           (const int64_t *)im->d_soff, d_exact);
+    }
+    hipLaunchKernelGGL(k_tm_decide, dim3(g256), dim3(256), 0, st, tm, S, B, ostr, (const double *)d_ll, (const double *)d_exact,
+                       (const double *)prop->d_shape, (int *)src->d_type, (double *)src->d_shape, d_out, d_flag, d_flags + 1);
+    HIP_TRY(hipGetLastError());
+    // the catalogue on the device has new rows: a new generation
+    src->gen = src->full_gen = ++g_source_gen;
+    src->row_gen.clear();
+    src->n_gal = -1;
+    src->h_type.clear();
+    // one readback: the rows, log alpha and the flags lie one behind the other (the flags behind 6 S doubles)
+    static_assert(sizeof(double) == 2 * sizeof(int), "the readback's layout");
+    std::vector<double> back((size_t)(6 * S + (S + 1) / 2));
+    const size_t back_bytes = sizeof(double) * 6 * S + sizeof(int) * S;
+    HIP_TRY(hipMemcpyAsync(back.data(), d_out, back_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int *hf = reinterpret_cast<const int *>(back.data() + 6 * S);
+    int64_t running = 0, accepted = 0, n_gal = 0;
+    src->h_type.resize((size_t)S);
+    for (int64_t s = 0; s < S; s++) {
+        const int32_t t = (int32_t)back[(size_t)(5 * s)];
+        src->h_type[(size_t)s] = t;
+        n_gal += t != 0;
+        running += hf[s] >= 0;
+        accepted += hf[s] == 1;
+    }
+    src->n_gal = n_gal;
+    if (x_out) memcpy(x_out, back.data(), sizeof(double) * 5 * S);
+    if (llh_out) memcpy(llh_out, back.data() + 5 * S, sizeof(double) * S);
+    if (stats) { stats[0] = 1; stats[1] = 2 * running; stats[2] = accepted; stats[3] = launches; }
+    if (h_flags[1] & 1)
+        return fail(CEL_ERR_INVALID, "cel_slice_sample: the type move found a state outside its own conditional (its current row scores -inf)");
+    return CEL_OK;
+}
+
 // The general slice sampler (k_slice_gen.h): random directions, stepping out by doubling, D = 2 or 4.
 int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t *chain_ids, const double *dirs, int numdir,
                      int step_out, int max_steps_out, double sigma, double phi_max, uint64_t seed, int max_rounds,
@@ -2278,8 +2426,9 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
     if (im->samp_S <= 0 || im->samp_S != src->S)
         return fail(CEL_ERR_INVALID, "cel_slice_sample needs a resident photon split of these %lld sources (have %lld)",
                     (long long)src->S, (long long)im->samp_S);
-    if (param != 0 && param != 1) return fail(CEL_ERR_INVALID, "cel_slice_sample: param must be 0 (location) or 1 (shape)");
+    if (param != 0 && param != 1 && param != 2) return fail(CEL_ERR_INVALID, "cel_slice_sample: param must be 0 (location), 1 (shape) or 2 (type)");
     if (!(sigma > 0.0) || max_rounds < 1 || max_steps_out < 0) return fail(CEL_ERR_INVALID, "cel_slice_sample: sigma and max_rounds must be positive");
+    if (param == 2) return slice_type_move(im, src, chain_ids, dirs, numdir, seed, x_out, llh_out, stats);
     const int D = param ? 4 : 2;
     const int compwise = dirs ? 0 : 1;
     const int ndir = compwise ? D : numdir;

@@ -43,6 +43,9 @@ k_patch_ll(const BandDev *__restrict__ bands, int B, int64_t P, const SrcRec *__
     const int64_t p = job / B;
     const BandDev *bd = bands + b;
     const SrcRec *rp = recs + (int64_t)b * P + p;
+    // a proposal that is not scored (owner -1: a retired slice chain, an unused second slot, a slot the prior or the cover test
+    // refused) has no patch set: the block retires before it forms an index from it.  Nothing reads such a job's output.
+    if (owner && owner[p] < 0) return;
     const int64_t ob = (int64_t)(owner ? owner[p] : 0) * B + b;
     const int4 bx = pbox[ob];
     const int nx = bx.y - bx.x, ny = bx.w - bx.z;

@@ -456,6 +456,39 @@ class ImageSet(object):
             self.ctx.set_option(L.CEL_OPT_SLICE_CONDITIONAL, was)
         return x, llh, dict(rounds=int(stats[0]), evals=int(stats[1]), launches=int(stats[3]))
 
+    def type_move(self, sources, shapes, h, seed, chain_ids=None, conditional="reference"):
+        """Source.resample_type (sources.py:247-306) for every source at once, on the device (cel_slice_sample, param 2): one
+        Metropolis-Hastings star <-> galaxy proposal per chain against the resident split.  shapes (S, 4): the galaxy shape
+        proposed for a chain that is a star now; h (S,): the caller's term of the log acceptance ratio (prior odds, proposal
+        densities, Jacobian).  Accepted rows replace the sources' type and shape on the device.
+        -> (typ[S] int32, shape[S,4], log_alpha[S], dict(evals, accepted, launches))"""
+        if conditional not in ("reference", "exact"):
+            raise ValueError("conditional must be 'reference' or 'exact'")
+        S = sources.S
+        if shapes is None or h is None:
+            raise ValueError("type_move needs the proposed shapes (S, 4) and h (S,)")
+        shapes, h = L.f64(shapes), L.f64(h)
+        if shapes.shape != (S, 4) or h.shape != (S,):
+            raise ValueError("shapes must be (S, 4) and h (S,)")
+        dirs = np.ascontiguousarray(np.concatenate([shapes, h[:, None]], axis=1))
+        ids = None
+        if chain_ids is not None:
+            ids = np.ascontiguousarray(chain_ids, dtype=np.int32)
+            if ids.shape != (S,):
+                raise ValueError("chain_ids must have one entry per source")
+        x, la = np.zeros((S, 5)), np.zeros(S)
+        stats = np.zeros(4, dtype=np.int64)
+        was = self.ctx.get_option(L.CEL_OPT_SLICE_CONDITIONAL)
+        try:
+            self.ctx.set_option(L.CEL_OPT_SLICE_CONDITIONAL, 1 if conditional == "exact" else 0)
+            L.check(L.lib().cel_slice_sample(self._h, sources._h, 2, None if ids is None else ids.ctypes.data_as(L.c_int32_p),
+                                             L.dptr(dirs), 1, 0, 0, 1.0, 0.0, C.c_uint64(int(seed) & (2 ** 64 - 1)), 1,
+                                             L.dptr(x), L.dptr(la), stats.ctypes.data_as(L.c_int64_p)))
+        finally:
+            self.ctx.set_option(L.CEL_OPT_SLICE_CONDITIONAL, was)
+        return (x[:, 0].astype(np.int32), np.ascontiguousarray(x[:, 1:]), la,
+                dict(evals=int(stats[1]), accepted=int(stats[2]), launches=int(stats[3])))
+
     def sample_sums(self):
         """photons attributed to every (source, band) by the resident split -> (S, B)"""
         S, tot = C.c_int64(0), C.c_int64(0)

@@ -452,7 +452,32 @@ int cel_slice_locations(cel_images *img, cel_sources *src, const int32_t *chain_
  *   chain_ids  as cel_slice_locations; a star is left alone under param 1
  *   x_out      S*D (host, may be NULL): the new states; they also REPLACE src's on the device.  llh_out, stats: as
  *              cel_slice_locations (stats[2] = 0)
- * CEL_OPT_SLICE_CONDITIONAL = 1: the exact conditional in place of the reference's (see the option). */
+ * CEL_OPT_SLICE_CONDITIONAL = 1: the exact conditional in place of the reference's (see the option).
+ *
+ * param 2: the star <-> galaxy move (Source.resample_type, CelestePy/sources.py:247-306) for every source at once: ONE
+ * Metropolis-Hastings proposal per chain against the resident split -- given the photon split a source's conditional involves
+ * no other source, so all sources move in one call, exactly.  A chain's current row and the row with the type flipped are
+ * scored as params 0 and 1 score a slot (the bands' mode-0 values added in band order from 0.0, plus the exact conditional's
+ * term and cover test under CEL_OPT_SLICE_CONDITIONAL = 1);  log alpha = (score(proposal) - score(current)) + h,  accepted
+ * iff log(u) < log alpha with u the FIRST uniform of the chain's SplitMix64 stream keyed by (seed, chain id).  The arguments
+ * are re-read:
+ *   dirs       S*5 (host, required; numdir must be 1): per chain (theta, sigma, phi, rho, h).  The shape is the galaxy proposed
+ *              for a chain that is a star now (ignored for a galaxy: its proposal is the star at the same location with the
+ *              same expected counts); a shape outside theta in (0,1), sigma > 0, rho in (0,1) is never rendered and is
+ *              rejected, and counts as an evaluation.  h is the caller's term of the log acceptance ratio of the move the chain
+ *              would make -- prior odds, proposal densities, Jacobian: everything that is not the likelihood (the reference's
+ *              proposal_fun seam).  It must be finite for every chain with chain_ids[s] >= 0 (CEL_ERR_INVALID otherwise,
+ *              before any launch)
+ *   chain_ids  as above; a source without a sample patch in any band and a source of type 2 are left alone too: their rows
+ *              stay bit for bit
+ *   step_out, max_steps_out, phi_max, max_rounds: not read; sigma: not read, but must be > 0
+ *   x_out      S*5 (host, may be NULL): the new type as a double, then the new shape.  An accepted row REPLACES src's type and
+ *              shape on the device (a galaxy turned star keeps its shape row's bits); locations and counts are untouched
+ *   llh_out    S (host, may be NULL): log alpha, NaN for a chain left alone
+ *   stats      {1, scored slots (two per running chain), accepted moves, likelihood launches}
+ * A proposal the cover test refuses scores -inf and is rejected.  A running chain whose CURRENT row scores -inf (it cannot
+ * after a full-box split) stays where it is and the call returns CEL_ERR_INVALID behind the other chains' moves.  The same
+ * refusals as params 0 and 1: a masked set, no resident split of these sources, under the exact conditional a row window. */
 int cel_slice_sample(cel_images *img, cel_sources *src, int param, const int32_t *chain_ids, const double *dirs, int numdir,
                      int step_out, int max_steps_out, double sigma, double phi_max, uint64_t seed, int max_rounds,
                      double *x_out, double *llh_out, int64_t *stats);
