@@ -252,7 +252,8 @@ struct cel_images {
     bool bin_two_level = false;   // a super-tile once held more than BIN_CH candidates: coarse lists in global memory from then on
     int64_t mass_pending = -1;       // doubles waiting in d_mass between cel_stamp_mass_begin and _end (-1: none)
     int64_t mass_todo_S = -1;        // >= 0: that _begin took the short cut on a catalogue of so many sources; _end finishes its leftovers
-    uint64_t mass_gen = 0;           // ... of the catalogue of this generation, with the to-do list at mass_todo_ptr: what _end checks
+    uint64_t mass_gen = 0;           // _begin summed the catalogue of this generation (short cut: with the to-do list at mass_todo_ptr): what _end checks
+    uint64_t split_epoch = 0, mass_epoch = 0;   // photon splits of this set so far, and how many there were at _begin
     const int *mass_todo_ptr = nullptr; //  before it launches on the leftovers (a call in between may have re-run k_prep for another
                                      //     catalogue or re-allocated the split's buffers; points into d_mass_todo: not owned)
     double *d_mass = nullptr;        // (points into a scratch slot of the context: not owned)
@@ -769,6 +770,11 @@ int cel_images_set_nelec(cel_images *im, const double *nelec, int mem) {
     if (rc != CEL_OK) return rc;
     im->have_nelec = true;
     im->partials_gen = 0;                 // the tiles' Poisson partials were formed against the old pixels (the incremental render keeps none of them)
+    // ... and the resident photon split was drawn from them: new pixels drop it (cel_samples_info reports S = 0, and every call that
+    // needs the split refuses until the next resident cel_photon_split) with the stamp sums that split left for cel_stamp_mass
+    im->samp_S = 0; im->samp_total = 0;
+    im->ssum_valid = im->hsum_valid = im->nz_valid = false;
+    im->massfx_gen = 0;
     // the image's range: 0 ... 65 535 everywhere lets the photon split keep its photons-left plane in 16 bits (k_split.h)
     im->nelec_u16 = false;
     // ... and the NaN counts per band: the mask (a block's count stays below 2^53: exact in a double)
@@ -1654,12 +1660,13 @@ int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owne
     if (!resident && (!boxes || !offsets)) return fail(CEL_ERR_INVALID, "cel_patch_loglik: null boxes / offsets");
     if (resident && mode > 1) return fail(CEL_ERR_INVALID, "the resident form scores mode 0 or 1");
     const int nplanes = (mode == 4) ? 2 : 1;               // mode 4: data plane, then background plane
+    // (a masked set is refused as such before the missing split is named: cel_images_set_nelec drops the split it masks)
+    if (mode == 1) { int rm = refuse_masked(im, "cel_patch_loglik (isolated form)"); if (rm) return rm; }
     if (resident && (im->samp_S <= 0 || NB != im->samp_S))
         return fail(CEL_ERR_INVALID, "resident form needs a resident photon split of NB = %lld sources (have %lld)",
                     (long long)NB, (long long)im->samp_S);
     if (NB < 1 || (NB > 1 && !owner)) return fail(CEL_ERR_INVALID, "cel_patch_loglik: NB patch sets need an owner array");
     if (resident && mode == 1 && !im->have_nelec) return fail(CEL_ERR_INVALID, "the isolated form needs cel_images_set_nelec");
-    if (mode == 1) { int rm = refuse_masked(im, "cel_patch_loglik (isolated form)"); if (rm) return rm; }
     cel_ctx *c = im->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const int B = im->B;
@@ -1834,7 +1841,7 @@ int cel_stamp_mass_begin(cel_images *im, cel_sources *src) {
         // without very faint sources; a launch of S B blocks that find nothing to do cost 0.15 ms of the flux step)
         HIP_TRY(hipMemcpyAsync(&c->mail->mass_todo, d_ntodo, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         im->mass_todo_S = S;
-        im->mass_gen = src->gen; im->mass_todo_ptr = im->d_mass_todo;
+        im->mass_todo_ptr = im->d_mass_todo;
     } else if (observed) {
         hipLaunchKernelGGL(k_stamp_mass_masked, dim3((unsigned)(S * B)), dim3(64), 0, c->stream, im->d_bands, B, im->H, im->W, S,
                            im->d_recs, (const double *)im->d_nelec, c->tail_T, d_out, (const int *)nullptr);
@@ -1845,6 +1852,7 @@ int cel_stamp_mass_begin(cel_images *im, cel_sources *src) {
     }
     prof_end(c, pi);
     HIP_TRY(hipGetLastError());
+    im->mass_gen = src->gen; im->mass_epoch = im->split_epoch;
     im->mass_pending = S * B;
     im->d_mass = d_out;
     return CEL_OK;
@@ -1862,6 +1870,10 @@ static int mass_finish(cel_images *im, int64_t *n_out) {
     im->mass_todo_S = -1;
     *n_out = n;
     if (n == 0) return CEL_OK;
+    // A device sampler, a render or a stamp call of another catalogue (or generation) in between re-ran k_prep, and a photon
+    // split takes the scratch slot the values wait in: the header allows neither, and what waits is not handed out
+    if (im->recs_gen != im->mass_gen || im->split_epoch != im->mass_epoch)
+        return fail(CEL_ERR_INVALID, "cel_stamp_mass_end: the source records or the photon split were rebuilt since cel_stamp_mass_begin");
     if (S_todo >= 0) {                  // the short cut's leftovers (cel_stamp_mass_begin)
         HIP_TRY(hipStreamSynchronize(c->stream));
         const int ntodo = c->mail->mass_todo;
@@ -2636,6 +2648,7 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
     // with the split's strict boxes (the model image of cel_images_get_lambda is left alone).
     // Direct form: a plain render (its kernel accumulates the totals itself).
     const bool hw = (c->variant != 0) && (im->TW == HW_TW);
+    im->split_epoch++;                          // (masses waiting for cel_stamp_mass_end share a scratch slot with this call's partial sums)
     // a masked set under CEL_OPT_HONOUR_MASK: the masked twins (no photons, no sky, no draws at a masked pixel), no mass short cut
     const bool masked = honours_mask(im);
     bool use_massfx = false;

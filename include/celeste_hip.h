@@ -164,7 +164,8 @@ enum {
                                two kernels also add up every unit stamp they evaluate, so that a cel_stamp_mass[_begin] of the
                                same catalogue right after the split reads the masses off those sums instead of evaluating
                                every stamp again (1.7 ms at configs[4]); galaxies fainter than a sixteenth of a sky pixel (counts <
-                               eps / 16; stars: eps / 1024) still go through the mass kernel.  The sums carry the split's drop rule:
+                               eps / 16; stars: eps / 1024) still go through the mass kernel, and so does a stamp over the frame's
+                               edge that leaves less than that ON the frame (counts * mass).  The sums carry the split's drop rule:
                                masses agree with the mass kernel's to 1e-11 eps / counts at most for a galaxy, 1.5e-13 eps / counts for
                                a star (measured; 1e-14 for a bright source): 1.6e-10 at the thresholds.  0 = totals always rendered from scratch, masses
                                always by the mass kernel */
@@ -245,7 +246,12 @@ int cel_images_destroy(cel_images *img);
  * there); the calls that have not been taught about a mask -- cel_photon_split, the isolated forms of cel_patch_loglik[_multi]
  * and, for want of a split, cel_flux_conditionals and cel_slice_* -- refuse a masked set with CEL_ERR_INVALID before they
  * launch anything.  Everything that does not read nelec (stamps, boxes, masses, the mode 4 planes, which carry their own NaN
- * mask) is unchanged, and a set without a NaN takes exactly the code it took before there was a mask. */
+ * mask) is unchanged, and a set without a NaN takes exactly the code it took before there was a mask.
+ * THE RESIDENT SPLIT.  New pixels drop the resident photon split, which was drawn from the old ones: after this call
+ * cel_samples_info reports S = 0, cel_stamp_mass_ready answers 0, and cel_flux_conditionals, cel_slice_locations, cel_slice_sample,
+ * the resident forms of cel_patch_loglik_multi, cel_samples_fetch and cel_samples_photon_rects fail with CEL_ERR_INVALID, naming
+ * the missing split, until the next resident cel_photon_split (on a masked set the masked refusal above comes first).  Pixels
+ * written in place through cel_images_device_ptrs are the caller's business, as that call says. */
 int cel_images_set_nelec(cel_images *img, const double *nelec, int mem);
 /* masked[b] = the number of NaN (masked) pixels of band b that the last cel_images_set_nelec found (0 before the first) */
 int cel_images_mask_info(cel_images *img, int64_t *masked /* B */);
@@ -402,7 +408,8 @@ int cel_stamp_mass_ready(cel_images *img, cel_sources *src, int *ready);
  * can draw its Gamma variates while the device sums the stamps (the flux step of a Gibbs sweep) without a second thread.
  * Between the two, calls that touch neither the catalogue, the source records nor the photon split may run on this context
  * (cel_gamma_streams, cel_samples_fetch, cel_images_set_epsilon: what ModelGibbs does there); _end fails with
- * CEL_ERR_INVALID when the source records or the photon split were rebuilt in between. */
+ * CEL_ERR_INVALID when the source records or the photon split were rebuilt in between -- by a device sampler, by a render or a
+ * stamp call of another catalogue or generation, by any cel_photon_split -- whether or not _begin took the split's short cut. */
 int cel_stamp_mass_begin(cel_images *img, cel_sources *src);
 int cel_stamp_mass_end(cel_images *img, double *mass);
 /* Source.resample_fluxes (CelestePy/sources.py:321-349) for every source of a catalogue whose resident photon split is on the
