@@ -54,6 +54,7 @@
 
 #include "../../include/celeste_hip.h"
 #include "host_buf.h"
+#include "field_state.h"
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -116,7 +117,7 @@ struct Prof {
 };
 
 // The context's scratch slots (scratch_get), by purpose.  A slot's contents are dead when the call that took it returns --
-// except SCR_VALUES after cel_stamp_mass_begin: the masses WAIT there (im->d_mass) for cel_stamp_mass_end, and none of the calls
+// except SCR_VALUES after cel_stamp_mass_begin: the masses WAIT there (im->mass.values) for cel_stamp_mass_end, and none of the calls
 // the header allows in between (cel_gamma_streams, cel_samples_fetch, cel_images_set_epsilon) takes that slot.
 enum ScratchSlot {
     SCR_PLL_BOXES,    // cel_patch_loglik_multi: the caller's boxes, their photon rectangles, the owners
@@ -216,7 +217,9 @@ struct SourcesDeleter {
     void operator()(cel_sources *s) const { cel_sources_destroy(s); }
 };
 
-struct cel_images {
+// (FieldState, field_state.h: whose records, lists, model image and photon split the buffers below hold -- im->rec, im->lists,
+// im->model, im->split, im->mass -- and the events that are the only writers of those stamps)
+struct cel_images : FieldState {
     cel_ctx *ctx = nullptr;
     int B = 0, H = 0, W = 0;   // H = rows held on the device (the window height)
     int full_H = 0, win_y0 = 0;  // the window is rows [win_y0, win_y0 + H) of a full_H-row frame
@@ -234,35 +237,19 @@ struct cel_images {
     DevBuf<int4> d_boxes;
     DevBuf<int> d_kind;
     DevBuf<int> d_status;          // per (band, source): 1 has a stamp, 0 empty box, -1 overlap-test miss
-    // which sources the records on the device belong to (cel_sources::gen, unique per cel_sources_set),
-    // and the host copy of their boxes / status that cel_stamp_boxes / cel_source_boxes hand out:
+    // the host copy of the boxes / status that cel_stamp_boxes / cel_source_boxes hand out (rec.hbox_gen):
     // a stamp call (boxes, then stamps) runs k_prep and the D2H once, not twice
-    uint64_t recs_gen = 0, hbox_gen = 0;
-    // which sources the model image in d_lambda (full boxes, the current sky levels) and the tile lists belong to: what lets
-    // the photon split take its totals from that image (k_border.h); 0 = not valid
-    uint64_t lambda_gen = 0, lists_gen = 0;
-    DevBuf<unsigned long long> d_massfx;      // the split's integer stamp-mass sums (k_split.h, k_border.h), per (source, band)
-    uint64_t massfx_gen = 0;                  // ... hold the masses of the catalogue of this generation (0: of none)
+    DevBuf<unsigned long long> d_massfx;      // the split's integer stamp-mass sums (k_split.h, k_border.h), per (source, band): split.massfx_gen
     DevBuf<int> d_mass_todo;                  // (source, band) jobs the mass kernel proper still has to do + their count behind them
     std::vector<int4> h_boxes;
     std::vector<int> h_status;
     DevBuf<int> d_tile_cnt, d_tile_nstar, d_tile_work, d_order;
     DevBuf<int> d_tile_cost;      // measured duration of every tile in the last render (the next render's launch order)
-    int64_t cost_S = -1;          // number of sources that render had (-1: nothing measured yet)
     bool bin_two_level = false;   // a super-tile once held more than BIN_CH candidates: coarse lists in global memory from then on
-    int64_t mass_pending = -1;       // doubles waiting in d_mass between cel_stamp_mass_begin and _end (-1: none)
-    int64_t mass_todo_S = -1;        // >= 0: that _begin took the short cut on a catalogue of so many sources; _end finishes its leftovers
-    uint64_t mass_gen = 0;           // _begin summed the catalogue of this generation (short cut: with the to-do list at mass_todo_ptr): what _end checks
-    uint64_t split_epoch = 0, mass_epoch = 0;   // photon splits of this set so far, and how many there were at _begin
-    const int *mass_todo_ptr = nullptr; //  before it launches on the leftovers (a call in between may have re-run k_prep for another
-                                     //     catalogue or re-allocated the split's buffers; points into d_mass_todo: not owned)
-    double *d_mass = nullptr;        // (points into a scratch slot of the context: not owned)
     DevBuf<long long> d_btot;        // per-1024-entries totals of the patch / list layout scans
-    bool nelec_u16 = false;          // every observed pixel in 0 ... 65 535: the split's 16-bit photons-left plane
     int64_t masked[MAX_BANDS] = {0}; // NaN (masked) pixels per band that the last cel_images_set_nelec found (cel_images_mask_info)
     bool any_masked = false;         // ... at least one: a MASKED set (k_mask.h, the masked twins of the gradient and E-step kernels)
     bool star_one_segment = false;   // every band passes star_setup's test: k_render_stars may take star tiles
-    int64_t order_S = -1;         // d_order already holds the heaviest-first order of those costs (sorted behind that render's readback)
     hipEvent_t ev_step = nullptr; // marks a step's readback copy: the host waits for it, not for the sort queued behind it
     DevBuf<int64_t> d_tile_off;
     unsigned long long *d_cursor = nullptr;   // fine cursor, fine overflow, coarse cursor, coarse overflow (inside d_llband)
@@ -274,17 +261,13 @@ struct cel_images {
     DevBuf<unsigned long long> d_timing;      // CEL_OPT_TILE_TIMING diagnostic stamps, 3 per tile
     // device-resident sample patches of the last resident photon split (source-major, index s*B+b)
     DevBuf<int> d_samp;         // the resident photon split's sample patches: int32 photon counts, source-major
-    bool ssum_valid = false;
     // host copies of the last resident split's sums and patch offsets (pinned), made INSIDE cel_photon_split before its last
     // wait: cel_samples_fetch hands them over without touching the stream, on which the photon lists are still being compacted
     // (grown together; h_ssum is named last, so its capacity is the pair's)
     PinnedBuf<double> h_ssum;
     PinnedBuf<int64_t> h_soff;
-    bool hsum_valid = false;
     DevBuf<NzEntry> d_nzlist;   // photon lists of the resident split (k_nz_layout / k_nz_compact): per patch the pixels that hold a photon
-    bool nz_valid = false;
     DevBuf<double> d_rate;      // per-pixel total rates of the photon split (strict boxes), B*H*W, on first use
-    bool rate_in_lambda = false;    // the last split read its totals from the model image itself (CEL_OPT_SPLIT_FULL_BOX with a current image)
     // the resident split's patch layout, grown together (cel_photon_split: grow_group); d_sbox is named last, so its capacity is the group's
     DevBuf<int4> d_sbox;
     DevBuf<int4> d_snz;         // nonzero rectangles of the resident sample patches (k_patch_nzbox)
@@ -292,23 +275,15 @@ struct cel_images {
     DevBuf<double> d_ssum;      // photons per (source, band) of the resident split, summed by the split kernel itself
     DevBuf<int> d_nnz, d_nzmode;   // ... and its photon lists' per-patch counts, modes and offsets
     DevBuf<int64_t> d_nzoff;
-    int64_t samp_S = 0, samp_total = 0;
     DevBuf<double> d_stats;
     // device-resident slice sampler (cel_slice_locations): chain state, proposal set, per-round outputs
     DevBuf<char> d_slice;
     std::unique_ptr<cel_sources, SourcesDeleter> slice_prop;
     DevBuf<char> d_sgen;        // the general slice sampler's state (cel_slice_sample)
     std::unique_ptr<cel_sources, SourcesDeleter> sgen_prop;
-    int64_t last_S = 0;
     double last_entries = 0;
     bool counted = false;            // in ctx->live
-    bool nelec_shared = false;       // cel_images_device_ptrs handed the observed pixels' device pointer out
-    uint64_t partials_gen = 0;       // the per-tile Poisson partials in d_partials are those of this catalogue generation's render (0: not)
-    uint64_t lambda_uid = 0;         // the catalogue OBJECT whose generation lambda_gen is (the incremental render compares row stamps of the same object only)
-    double lambda_T = -1.0;          // ... and the drop threshold that image was rendered at
-    int lambda_parts = 0;            // ... with so many blocks per tile
     DevBuf<int> d_dirty;             // per tile: touched by a changed source's box (the incremental render)
-    int64_t last_dirty = -1;         // tiles the last render rendered incrementally (-1: it rendered every tile)
     // the one-launch path of a small star field (k_small_stars.h): per-block partials + per-band arrival counters
     MappedBuf<double> h_small;
     double *d_small = nullptr;       // the device address of h_small (not owned)
@@ -319,21 +294,14 @@ struct cel_images {
     bool small_off = false;       // a part once held more stars than the kernel stages: the general path from then on
 };
 
-static std::atomic<uint64_t> g_source_gen{0};
-
-struct cel_sources {
+// (SourceStamps, field_state.h: gen, uid, full_gen, row_gen, n_gal, h_type and the three functions that write them)
+struct cel_sources : SourceStamps {
     cel_ctx *ctx = nullptr;
     bool counted = false;          // in ctx->live
     int64_t cap = 0, S = 0;
     int B = 0;
-    uint64_t gen = 0;              // changes with every cel_sources_set (process-wide counter)
-    uint64_t uid = 0;              // which catalogue object this is (process-wide, never reused: a generation alone does not say whose it is)
-    uint64_t full_gen = 0;         // ... the generation of the last change of the WHOLE catalogue (cel_sources_set, a sampler's update)
-    std::vector<uint64_t> row_gen; // per row: the generation of its last change by cel_sources_set_rows (empty: none since full_gen)
-    int64_t n_gal = -1;            // entries that are not stars (type != 0); -1 = unknown (types set from device memory)
     DevBuf<int> d_type;
     DevBuf<double> d_radec, d_counts, d_shape;
-    std::vector<int32_t> h_type;   // the types as last set from host memory (cel_sources_set_rows keeps n_gal exact with them)
 };
 
 // The launch order of the tiles matters only when there are more tiles than the chip runs at once (2048 waves of the
@@ -769,14 +737,10 @@ int cel_images_set_nelec(cel_images *im, const double *nelec, int mem) {
     int rc = copy_in(im->d_nelec, nelec, sizeof(double) * (size_t)im->B * im->H * im->W, mem, im->ctx->stream);
     if (rc != CEL_OK) return rc;
     im->have_nelec = true;
-    im->partials_gen = 0;                 // the tiles' Poisson partials were formed against the old pixels (the incremental render keeps none of them)
-    // ... and the resident photon split was drawn from them: new pixels drop it (cel_samples_info reports S = 0, and every call that
-    // needs the split refuses until the next resident cel_photon_split) with the stamp sums that split left for cel_stamp_mass
-    im->samp_S = 0; im->samp_total = 0;
-    im->ssum_valid = im->hsum_valid = im->nz_valid = false;
-    im->massfx_gen = 0;
+    // new pixels drop the resident photon split (cel_samples_info reports S = 0, and every call that needs the split refuses
+    // until the next resident cel_photon_split) with the stamp sums that split left for cel_stamp_mass
+    im->new_pixels();
     // the image's range: 0 ... 65 535 everywhere lets the photon split keep its photons-left plane in 16 bits (k_split.h)
-    im->nelec_u16 = false;
     // ... and the NaN counts per band: the mask (a block's count stays below 2^53: exact in a double)
     im->any_masked = false;
     {
@@ -799,7 +763,7 @@ int cel_images_set_nelec(cel_images *im, const double *nelec, int mem) {
             bad += im->masked[b];
         }
         im->any_masked = bad != 0;
-        im->nelec_u16 = (bad == 0) && (lo >= 0.0) && (hi <= 65535.0);
+        im->pixel_range((bad == 0) && (lo >= 0.0) && (hi <= 65535.0));
     }
     return CEL_OK;
 }
@@ -830,8 +794,7 @@ int cel_images_set_epsilon(cel_images *im, int band, double eps) {
     if (!im || band < 0 || band >= im->B) return fail(CEL_ERR_INVALID, "cel_images_set_epsilon: bad band");
     HIP_TRY(hipSetDevice(im->ctx->device));
     im->hb[band].eps = eps;
-    im->lambda_gen = 0;                   // the model image on the device was rendered with the old sky level
-    im->partials_gen = 0;                 // ... and the tiles' Poisson partials against it
+    im->new_sky_level();
     // stream-ordered, no host synchronisation (Gibbs calls this per band per sweep)
     hipLaunchKernelGGL(k_set_eps, dim3(1), dim3(1), 0, im->ctx->stream, im->d_bands, band, eps);
     HIP_TRY(hipGetLastError());
@@ -844,9 +807,7 @@ int cel_images_set_window(cel_images *im, int y0, int full_H) {
         return fail(CEL_ERR_INVALID, "window rows [%d, %d) do not fit a %d-row frame", y0, y0 + im->H, full_H);
     im->win_y0 = y0;
     im->full_H = full_H;
-    im->recs_gen = im->hbox_gen = 0;      // boxes are cut to the window
-    im->lambda_gen = im->lists_gen = 0;
-    im->massfx_gen = 0;
+    im->new_window();
     return CEL_OK;
 }
 
@@ -873,7 +834,7 @@ int cel_images_get_lambda(cel_images *im, double *out, int mem) {
 int cel_images_device_ptrs(cel_images *im, void **nelec, void **lambda) {
     if (!im) return fail(CEL_ERR_INVALID, "null images");
     if (nelec) {        // the caller may write it, at any time: no assumption about its range any more, no Poisson partials kept
-        *nelec = im->d_nelec; im->nelec_u16 = false; im->nelec_shared = true; im->partials_gen = 0;
+        *nelec = im->d_nelec; im->pixels_handed_out();
     }
     if (lambda) *lambda = im->d_lambda;
     return CEL_OK;
@@ -912,7 +873,7 @@ int cel_sources_create(cel_ctx *c, int64_t capacity, int B, cel_sources **out) {
     std::unique_ptr<cel_sources> s(new (std::nothrow) cel_sources());   // (a failed creation frees what it allocated)
     if (!s) return fail(CEL_ERR_NOMEM, "out of host memory");
     s->ctx = c; s->cap = capacity; s->B = B;
-    s->uid = ++g_source_gen;
+    s->created();
     HIP_TRY(s->d_type.grow(capacity, capacity, c->stream));
     HIP_TRY(s->d_radec.grow(2 * capacity, 2 * capacity, c->stream));
     HIP_TRY(s->d_counts.grow(B * capacity, B * capacity, c->stream));
@@ -938,15 +899,8 @@ int cel_sources_set(cel_sources *s, int64_t S, const int32_t *type, const double
         if (mem != CEL_DEVICE) HIP_TRY(hipStreamSynchronize(st));   // pageable sources must stay valid: one sync for the four
     }
     s->S = S;
-    s->gen = s->full_gen = ++g_source_gen;
-    s->row_gen.clear();
-    s->n_gal = -1;
-    s->h_type.clear();
-    if (mem != CEL_DEVICE) {
-        s->n_gal = 0;
-        for (int64_t i = 0; i < S; i++) s->n_gal += (type[i] != 0);
-        s->h_type.assign(type, type + S);
-    }
+    s->all_rows_changed(true);
+    if (mem != CEL_DEVICE) s->types_known(type, S);
     return CEL_OK;
 }
 
@@ -1007,26 +961,14 @@ int cel_sources_set_rows(cel_sources *s, int64_t n, const int32_t *idx, const in
                        dd, dd + 2 * n, dd + (2 + B) * n, s->d_type, s->d_radec, s->d_counts, s->d_shape);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));          // the pageable staging vector goes out of scope
-    if ((int64_t)s->h_type.size() == s->S) {
-        for (int64_t i = 0; i < n; i++) {
-            s->n_gal += (type[i] != 0) - (s->h_type[idx[i]] != 0);
-            s->h_type[idx[i]] = type[i];
-        }
-    } else {
-        s->n_gal = -1;
-    }
-    s->gen = ++g_source_gen;
-    // which rows changed since when: a render whose image set still holds the model image of an earlier generation of THIS
-    // catalogue renders only the tiles these rows' boxes touch (render_impl: the incremental path)
-    if ((int64_t)s->row_gen.size() != s->S) s->row_gen.assign((size_t)s->S, 0);
-    for (int64_t i = 0; i < n; i++) s->row_gen[idx[i]] = s->gen;
+    s->rows_replaced(s->S, n, idx, type);        // (the row stamps: render_impl's incremental path)
     return CEL_OK;
 }
 
 // ---- prep + bin (shared by field and stamps) ------------------------------------------------
 static int ensure_recs(cel_images *im, int64_t n) {
     if (n <= im->d_recs.cap) return CEL_OK;
-    im->recs_gen = im->hbox_gen = 0;
+    im->records_regrown();
     const int64_t cap = n + n / 4 + 64;
     HIP_TRY(grow_group(im->ctx->stream, im->d_boxes, cap, im->d_kind, cap, im->d_status, cap, im->d_recs, cap));
     return CEL_OK;
@@ -1042,23 +984,21 @@ static int run_prep(cel_images *im, cel_sources *src, const int *d_live = nullpt
     int64_t n = src->S * im->B;
     int rc = ensure_recs(im, n > 0 ? n : 1);
     if (rc) return rc;
-    if (n == 0) { im->recs_gen = src->gen; im->last_S = 0; return CEL_OK; }
+    if (n == 0) { im->records_written(src->gen, 0); return CEL_OK; }
     int pi = prof_slot(c, CEL_K_PREP);
     LAUNCH_EV(k_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), c->stream, EV0(c, pi), EV1(c, pi), im->d_bands, im->B,
               im->full_H, im->W, im->win_y0, im->H, src->S, src->d_type, src->d_radec, src->d_counts, src->d_shape,
               rsq_galaxy(), im->d_recs, im->d_boxes, im->d_kind, im->d_status, im->d_cursor, d_live, nobox);
     HIP_TRY(hipGetLastError());
-    im->recs_gen = (d_live || nobox) ? 0 : src->gen;      // a partial table is nobody else's
-    im->last_S = src->S;
+    im->records_written((d_live || nobox) ? 0 : src->gen, src->S);      // a partial table is nobody else's
     return CEL_OK;
 }
 
 // host copies of the boxes and status of every (band, source) of `src` (20 B each, not the 128-B
 // records); reused until the sources or the window change
 static int host_boxes(cel_images *im, cel_sources *src) {
-    if (im->hbox_gen == src->gen && src->gen != 0 && im->recs_gen == src->gen) return CEL_OK;
-    int rc = CEL_OK;
-    if (im->recs_gen != src->gen || src->gen == 0) rc = run_prep(im, src);
+    if (im->rec.host_boxes_of(*src)) return CEL_OK;
+    int rc = im->rec.of(*src) ? CEL_OK : run_prep(im, src);
     if (rc) return rc;
     const int64_t n = src->S * im->B;
     im->h_boxes.resize((size_t)n);
@@ -1069,7 +1009,7 @@ static int host_boxes(cel_images *im, cel_sources *src) {
         HIP_TRY(hipMemcpyAsync(im->h_status.data(), im->d_status, sizeof(int) * n, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    im->hbox_gen = src->gen;
+    im->host_boxes_read(src->gen);
     return CEL_OK;
 }
 
@@ -1174,11 +1114,7 @@ static int render_small_stars(cel_images *im, cel_sources *src, int flags, bool 
         }
         im->llband_on_host = true;              // d_llband does not hold this render's sums (cel_images_loglik_device uploads them)
     }
-    im->recs_gen = src->gen;                    // the kernel wrote k_prep's records, boxes and status words
-    im->lists_gen = 0;                          // ... and no tile lists
-    if (!(flags & CEL_RENDER_NO_STORE)) im->lambda_gen = 0;
-    im->last_S = S;
-    im->cost_S = -1; im->order_S = -1;
+    im->small_star_render(src->gen, S, !(flags & CEL_RENDER_NO_STORE));
     im->last_entries = 0;
     *done = true;
     return CEL_OK;
@@ -1231,11 +1167,8 @@ static int plan_render(const cel_images *im, const cel_sources *src, int flags, 
     p.parts_used = (im->TW == HW_TW && !p.diag) ? p.parts : 1;
     if (p.stars_only) p.parts_used = 0;         // (the star-tile kernel adds a pixel's stars in another order: not the general kernel's bits)
     p.incremental = c->incremental && !lambda_out && !(flags & (CEL_RENDER_NO_STORE | CEL_RENDER_STRICT)) && im->TW == HW_TW &&
-                    c->variant != 0 && !p.diag && !p.stars_only && p.parts == 1 && S > 0 && S == im->last_S &&
-                    im->lambda_gen != 0 && im->lambda_uid == src->uid && im->lambda_T == c->render_T && im->lambda_parts == 1 && im->lambda_gen != src->gen &&
-                    im->lambda_gen >= src->full_gen &&
-                    im->lists_gen == im->lambda_gen && im->recs_gen == im->lambda_gen && (int64_t)src->row_gen.size() == S &&
-                    (!(flags & CEL_RENDER_LOGLIK) || p.masked_ll || (im->partials_gen == im->lambda_gen && !im->nelec_shared));
+                    c->variant != 0 && !p.diag && !p.stars_only && p.parts == 1 && S > 0 &&
+                    im->incremental_base(*src, S, c->render_T, (flags & CEL_RENDER_LOGLIK) && !p.masked_ll);
     // (masked: the dirty tiles' PIXELS are rendered incrementally, every tile's partial is formed again -- no partials are kept)
     p.tile_order = tile_order_of(c, im);
     // a small catalogue is binned by one wave per tile into per-tile segments of S entries (k_bin_direct)
@@ -1291,7 +1224,7 @@ static void launch_masked_ll(cel_ctx *c, cel_images *im, const RenderPlan &p) {
     LAUNCH_EV(k_reduce, dim3(im->B), dim3(256), c->stream, EV0(c, pi), EV1(c, pi), (const double *)im->d_partials, im->ntx * im->nty, im->d_llband.get(),
               im->ntx, p.own_ty0, p.own_ty1);
     im->llband_on_host = false;
-    im->partials_gen = 0;           // (nothing vouches for these partials between renders: a masked render forms every one again)
+    im->partials_overwritten();     // (nothing vouches for these partials between renders: a masked render forms every one again)
 }
 
 // the bands' sums in the mailbox, handed to the caller
@@ -1352,7 +1285,7 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
     };
     if (incr) {
         for (int64_t s = 0; s < S && incr; s++)
-            if (src->row_gen[(size_t)s] > im->lambda_gen) {
+            if (src->row_gen[(size_t)s] > im->model.lambda_gen) {
                 if (delta.n == DELTA_MAX) incr = false;
                 else delta.idx[delta.n++] = (int)s;
             }
@@ -1363,13 +1296,10 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         HIP_TRY(hipMemsetAsync(im->d_dirty, 0, sizeof(int) * (size_t)T, st));
         mark_dirty();   // the tiles the changed sources' OLD boxes touch (before k_prep rewrites the boxes) ...
     }
-    if (flags & CEL_RENDER_LOGLIK) im->partials_gen = 0;
-    im->lists_gen = 0;
-    if (!lambda_out && !(flags & CEL_RENDER_NO_STORE)) im->lambda_gen = 0;
+    im->render_begins((flags & CEL_RENDER_LOGLIK) != 0, !lambda_out && !(flags & CEL_RENDER_NO_STORE));
     rc = run_prep(im, src);
     if (rc) return rc;
     if (incr) mark_dirty();     // ... and the tiles their new boxes touch
-    im->last_dirty = -1;
     if (im->d_lists.cap == 0) {
         // first guess: every (band, source) touches ~6 tiles; grown on overflow below
         const int64_t n = (S * im->B) * 6 + 1024;
@@ -1392,7 +1322,7 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         int pi = prof_slot(c, CEL_K_BIN);
         // the order by the previous render's measured durations was sorted behind that render's readback
         // (below): nothing to do here then
-        const bool order_ready = (tile_order == 1 && im->order_S == S && im->cost_S == S);
+        const bool order_ready = tile_order == 1 && im->lists.order_ready(S);
         const hipEvent_t bin_ev1 = (tile_order && !order_ready) ? (hipEvent_t) nullptr : EV1(c, pi);
         // a small catalogue: one wave per tile (k_bin_direct).  Otherwise one binning kernel while no super-tile holds more
         // than BIN_CH candidates, the two-level form after that
@@ -1411,7 +1341,7 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
             // of the same source count (an MCMC chain changes little from one evaluation to the
             // next), by the binning pass's estimate otherwise.  The order never changes results.
             LAUNCH_EV(k_order, dim3(1), dim3(1024), st, (hipEvent_t) nullptr, EV1(c, pi),
-                      (const int *)((im->cost_S == S && tile_order == 1) ? im->d_tile_cost : im->d_tile_work), T, im->d_order);
+                      (const int *)((im->lists.costs_of(S) && tile_order == 1) ? im->d_tile_cost : im->d_tile_work), T, im->d_order);
         RenderArgs a;
         a.bands = im->d_bands; a.recs = im->d_recs; a.lists = im->d_lists; a.tile_cnt = im->d_tile_cnt;
         a.tile_nstar = im->d_tile_nstar;
@@ -1448,7 +1378,6 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         HIP_TRY(hipMemcpyAsync(c->mail.get(), im->d_llband, offsetof(Mailbox, sh) + sizeof(MailShared::bin_coarse),
                                hipMemcpyDeviceToHost, st));
         HIP_TRY(hipGetLastError());
-        im->last_S = S;
         // An MCMC chain renders the same number of sources again: sort this render's tile durations into
         // the next render's launch order NOW, behind the readback the host is waiting for, instead of
         // in front of the next render (13 us + a launch gap per step).  The host waits for the copy only.
@@ -1467,24 +1396,15 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         const bool coarse_ok = (coarse[1] & 0xffffffffull) == 0 && (int64_t)coarse[0] <= im->d_clist.cap;
         if (coarse_ok) im->last_entries = (double)fine[0];
         if (fine_ok && coarse_ok) {
-            im->cost_S = a.cost ? S : -1; im->order_S = post_order ? S : -1;
-            im->lists_gen = src->gen;
-            if (!lambda_out && !(flags & (CEL_RENDER_NO_STORE | CEL_RENDER_STRICT)) && im->TW == HW_TW && c->variant != 0) {
-                im->lambda_gen = src->gen;
-                im->lambda_uid = src->uid;
-                im->lambda_T = c->render_T;
-                // a render by the DIAG instantiation (tile timing, ablation bits) vouches for nothing: with an ablation bit set its
-                // pixels and partials are documented as wrong, and the incremental path would take them as a base
-                im->lambda_parts = diag ? 0 : plan.parts_used;
-                // (a render WITHOUT the log-likelihood vouches for no partials: those in the buffer may be of another sky
-                // level or drop threshold although the catalogue's generation is the same -- found by tools/dbg/incremental_stress.py)
-                im->partials_gen = ((flags & CEL_RENDER_LOGLIK) && !plan.masked_ll) ? src->gen : 0;
-            }
-            if (incr) im->last_dirty = -2;          // (counted on request: cel_debug_last_render)
+            // a render by the DIAG instantiation (tile timing, ablation bits) vouches for nothing (0 parts): with an ablation bit
+            // set its pixels and partials are documented as wrong, and the incremental path would take them as a base
+            // (last_dirty: counted on request, cel_debug_last_render)
+            im->render_succeeded(*src, S, a.cost != nullptr, post_order,
+                                 !lambda_out && !(flags & (CEL_RENDER_NO_STORE | CEL_RENDER_STRICT)) && im->TW == HW_TW && c->variant != 0,
+                                 c->render_T, diag ? 0 : plan.parts_used, (flags & CEL_RENDER_LOGLIK) && !plan.masked_ll, incr);
             break;
         }
-        im->cost_S = -1;
-        im->order_S = -1;
+        im->render_overflowed();
         // rerun with room (a truncated coarse list also truncates the fine counts)
         if (too_dense) { im->bin_two_level = true; continue; }
         const int64_t nc = (int64_t)coarse[0] + (int64_t)coarse[0] / 4 + 1024, nf = (int64_t)fine[0] + (int64_t)fine[0] / 4 + 1024;
@@ -1500,13 +1420,13 @@ int cel_debug_split_rates(cel_images *im, double *out) {
     if (!im || !out) return fail(CEL_ERR_INVALID, "cel_debug_split_rates: null argument");
     if (!im->d_rate) return fail(CEL_ERR_INVALID, "no totals image: cel_photon_split on the recurrence kernels has not run");
     HIP_TRY(hipSetDevice(im->ctx->device));
-    return copy_out(out, im->rate_in_lambda ? im->d_lambda : im->d_rate, sizeof(double) * (size_t)im->B * im->H * im->W, CEL_HOST, im->ctx->stream);
+    return copy_out(out, im->split.rate_in_lambda ? im->d_lambda : im->d_rate, sizeof(double) * (size_t)im->B * im->H * im->W, CEL_HOST, im->ctx->stream);
 }
 
 int cel_debug_last_render(cel_images *im, int64_t *dirty_tiles) {
     if (!im || !dirty_tiles) return fail(CEL_ERR_INVALID, "cel_debug_last_render: null argument");
     *dirty_tiles = -1;
-    if (im->last_dirty == -1 || !im->d_dirty) return CEL_OK;
+    if (im->model.last_dirty == -1 || !im->d_dirty) return CEL_OK;
     HIP_TRY(hipSetDevice(im->ctx->device));
     const int T = im->B * im->ntx * im->nty;
     std::vector<int> h((size_t)T);
@@ -1532,7 +1452,7 @@ int cel_field_stats(cel_images *im, double *n_srcpix, double *n_gauss, double *n
     if (!im) return fail(CEL_ERR_INVALID, "null images");
     cel_ctx *c = im->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    int64_t n = im->last_S * im->B;
+    int64_t n = im->rec.last_S * im->B;
     HIP_TRY(hipMemsetAsync(im->d_stats, 0, sizeof(double) * 2, c->stream));
     if (n > 0)
         hipLaunchKernelGGL(k_stats, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, im->d_recs, n, im->d_stats);
@@ -1662,9 +1582,9 @@ int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owne
     const int nplanes = (mode == 4) ? 2 : 1;               // mode 4: data plane, then background plane
     // (a masked set is refused as such before the missing split is named: cel_images_set_nelec drops the split it masks)
     if (mode == 1) { int rm = refuse_masked(im, "cel_patch_loglik (isolated form)"); if (rm) return rm; }
-    if (resident && (im->samp_S <= 0 || NB != im->samp_S))
+    if (resident && !im->split.resident_of(NB))
         return fail(CEL_ERR_INVALID, "resident form needs a resident photon split of NB = %lld sources (have %lld)",
-                    (long long)NB, (long long)im->samp_S);
+                    (long long)NB, (long long)im->split.samp_S);
     if (NB < 1 || (NB > 1 && !owner)) return fail(CEL_ERR_INVALID, "cel_patch_loglik: NB patch sets need an owner array");
     if (resident && mode == 1 && !im->have_nelec) return fail(CEL_ERR_INVALID, "the isolated form needs cel_images_set_nelec");
     cel_ctx *c = im->ctx;
@@ -1690,7 +1610,6 @@ int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owne
     if (!resident && offsets[nb] > 0 && !data) return fail(CEL_ERR_INVALID, "cel_patch_loglik: null data");
     int rc = run_prep(im, src);
     if (rc) return rc;
-    im->last_S = P;
     int4 *d_box = nullptr;
     int64_t *d_off = nullptr;
     int *d_owner = nullptr;
@@ -1698,7 +1617,7 @@ int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owne
     // a call with few proposals is a handful of one-wave jobs as long as their longest: each is dealt to PLL_PARTS blocks
     // (the values do not depend on it: the kernel sums its chunks in PLL_PARTS classes either way)
     // (with photon lists a job always owns PLL_PARTS slots: the kernel that scores at the photons writes its four class sums)
-    const bool nzl = resident && mode == 0 && c->variant != 0 && im->nz_valid;
+    const bool nzl = resident && mode == 0 && c->variant != 0 && im->split.nz_valid;
     const int nsplit = (c->variant != 0 && mode == 0 && P * B <= 8192) ? PLL_PARTS : 1;
     const int nparts = nzl ? PLL_PARTS : nsplit;
     std::vector<double> hout((size_t)(P * B * nparts));
@@ -1802,11 +1721,22 @@ int cel_patch_loglik(cel_images *im, cel_sources *src, const int32_t *boxes, con
 // chain's trace render came last: the split slowed down by 1.35 ms for the 1.7 ms taken off the flux step and the sweep was
 // 0.9 ms LONGER than with the two kernels one behind the other; two VALU- and LDS-bound kernels have nothing to give each
 // other.  Removed again.)
+// may the masses come from the split's own stamp sums (cel_stamp_mass_ready answers it, cel_stamp_mass_begin acts on it)
+static bool masses_from_split(const cel_images *im, const cel_sources *src) {
+    return !honours_mask(im) && im->ctx->mass_reuse_of() && im->split.sums_of(*src) && src->S * im->B <= im->d_massfx.cap;
+}
+
 int cel_stamp_mass_ready(cel_images *im, cel_sources *src, int *ready) {
     if (!im || !src || !ready) return fail(CEL_ERR_INVALID, "cel_stamp_mass_ready: null argument");
-    *ready = (src->ctx == im->ctx && src->B == im->B && !honours_mask(im) && im->ctx->mass_reuse_of() && src->gen != 0 && im->massfx_gen == src->gen &&
-              src->S * im->B <= im->d_massfx.cap) ? 1 : 0;
+    *ready = (src->ctx == im->ctx && src->B == im->B && masses_from_split(im, src)) ? 1 : 0;
     return CEL_OK;
+}
+
+// the device samplers and the flux step score against the resident split of exactly these sources
+static int need_resident_split(const cel_images *im, const cel_sources *src, const char *who, bool sums = false) {
+    if (im->split.resident_of(src->S) && (!sums || im->split.ssum_valid)) return CEL_OK;
+    return fail(CEL_ERR_INVALID, "%s needs a resident photon split of these %lld sources (have %lld)", who, (long long)src->S,
+                (long long)im->split.samp_S);
 }
 
 int cel_stamp_mass_begin(cel_images *im, cel_sources *src) {
@@ -1816,15 +1746,14 @@ int cel_stamp_mass_begin(cel_images *im, cel_sources *src) {
     HIP_TRY(hipSetDevice(c->device));
     const int B = im->B;
     const int64_t S = src->S;
-    im->mass_pending = -1;
-    im->mass_todo_S = -1;
-    if (S == 0) { im->mass_pending = 0; return CEL_OK; }
+    im->mass.cancel();
+    if (S == 0) { im->mass.begin(src->gen, im->split.split_epoch, 0, -1, nullptr, nullptr); return CEL_OK; }
     int rc = CEL_OK;
     // a masked set whose mask is honoured (CEL_OPT_HONOUR_MASK): the unit stamp summed over the UNMASKED pixels of the box -- the
     // split's short cut, which sums every pixel it walks, does not apply (and the masked split leaves it alone)
     const bool observed = honours_mask(im);
-    const bool from_split = !observed && c->mass_reuse_of() && src->gen != 0 && im->massfx_gen == src->gen && S * B <= im->d_massfx.cap;
-    if (!from_split || im->recs_gen != src->gen) rc = run_prep(im, src);
+    const bool from_split = masses_from_split(im, src);
+    if (!from_split || !im->rec.of(*src)) rc = run_prep(im, src);
     if (rc) return rc;
     double *d_out = nullptr;
     if ((rc = scratch_get(c, SCR_VALUES, sizeof(double) * S * B, (void **)&d_out))) return rc;
@@ -1840,8 +1769,6 @@ int cel_stamp_mass_begin(cel_images *im, cel_sources *src) {
         // (how many: read in cel_stamp_mass_end, which launches the mass kernel on exactly those -- none at all in a field
         // without very faint sources; a launch of S B blocks that find nothing to do cost 0.15 ms of the flux step)
         HIP_TRY(hipMemcpyAsync(&c->mail->mass_todo, d_ntodo, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        im->mass_todo_S = S;
-        im->mass_todo_ptr = im->d_mass_todo;
     } else if (observed) {
         hipLaunchKernelGGL(k_stamp_mass_masked, dim3((unsigned)(S * B)), dim3(64), 0, c->stream, im->d_bands, B, im->H, im->W, S,
                            im->d_recs, (const double *)im->d_nelec, c->tail_T, d_out, (const int *)nullptr);
@@ -1852,27 +1779,23 @@ int cel_stamp_mass_begin(cel_images *im, cel_sources *src) {
     }
     prof_end(c, pi);
     HIP_TRY(hipGetLastError());
-    im->mass_gen = src->gen; im->mass_epoch = im->split_epoch;
-    im->mass_pending = S * B;
-    im->d_mass = d_out;
+    im->mass.begin(src->gen, im->split.split_epoch, S * B, from_split ? S : -1, from_split ? im->d_mass_todo.get() : nullptr, d_out);
     return CEL_OK;
 }
 
-// the second half of cel_stamp_mass without the copy: the leftovers' kernel queued, im->d_mass complete in stream order; *n_out
+// the second half of cel_stamp_mass without the copy: the leftovers' kernel queued, im->mass.values complete in stream order; *n_out
 // = values (0: nothing pending was there to finish)
 static int mass_finish(cel_images *im, int64_t *n_out) {
-    if (im->mass_pending < 0) return fail(CEL_ERR_INVALID, "cel_stamp_mass_end without a cel_stamp_mass_begin");
+    if (im->mass.pending < 0) return fail(CEL_ERR_INVALID, "cel_stamp_mass_end without a cel_stamp_mass_begin");
     cel_ctx *c = im->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    const int64_t n = im->mass_pending;
-    im->mass_pending = -1;
-    const int64_t S_todo = im->mass_todo_S;
-    im->mass_todo_S = -1;
+    int64_t n = 0, S_todo = -1;
+    im->mass.take(&n, &S_todo);
     *n_out = n;
     if (n == 0) return CEL_OK;
     // A device sampler, a render or a stamp call of another catalogue (or generation) in between re-ran k_prep, and a photon
     // split takes the scratch slot the values wait in: the header allows neither, and what waits is not handed out
-    if (im->recs_gen != im->mass_gen || im->split_epoch != im->mass_epoch)
+    if (!im->mass.intact(im->rec, im->split))
         return fail(CEL_ERR_INVALID, "cel_stamp_mass_end: the source records or the photon split were rebuilt since cel_stamp_mass_begin");
     if (S_todo >= 0) {                  // the short cut's leftovers (cel_stamp_mass_begin)
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1881,11 +1804,11 @@ static int mass_finish(cel_images *im, int64_t *n_out) {
             // Calls that came between _begin and _end (the header lists what may: cel_gamma_streams, cel_samples_fetch,
             // cel_images_set_epsilon) leave the records and the to-do list alone.  Anything that re-ran k_prep for another
             // catalogue, or a photon split that re-allocated its buffers, is caught here instead of scoring stale records:
-            if (im->mass_todo_ptr != im->d_mass_todo || im->recs_gen != im->mass_gen)
+            if (im->mass.todo_ptr != im->d_mass_todo || !im->mass.intact(im->rec, im->split))
                 return fail(CEL_ERR_INVALID, "cel_stamp_mass_end: the source records or the photon split were rebuilt since cel_stamp_mass_begin");
             hipLaunchKernelGGL((k_patch_ll_hw<3, double>), dim3((unsigned)ntodo), dim3(64), 0, c->stream, im->d_bands, im->B, S_todo, im->d_recs,
                                (const int *)nullptr, (const int4 *)nullptr, (const int64_t *)nullptr, (const double *)nullptr,
-                               (const double *)nullptr, im->H, im->W, (const int4 *)nullptr, c->tail_T, im->d_mass,
+                               (const double *)nullptr, im->H, im->W, (const int4 *)nullptr, c->tail_T, im->mass.values,
                                (const int *)im->d_mass_todo);
             HIP_TRY(hipGetLastError());
         }
@@ -1898,7 +1821,7 @@ int cel_stamp_mass_end(cel_images *im, double *mass) {
     int64_t n = 0;
     int rc = mass_finish(im, &n);
     if (rc || n == 0) return rc;
-    return copy_out(mass, im->d_mass, sizeof(double) * n, CEL_HOST, im->ctx->stream);
+    return copy_out(mass, im->mass.values, sizeof(double) * n, CEL_HOST, im->ctx->stream);
 }
 
 // Source.resample_fluxes for the whole catalogue on the device (k_flux_step): the stamp masses (cel_stamp_mass's own path, short
@@ -1909,9 +1832,7 @@ int cel_flux_conditionals(cel_images *im, cel_sources *src, uint64_t seed, doubl
     if (!im || !src || !band_letter || !calib || !kappa || !flux_new || !active) return fail(CEL_ERR_INVALID, "cel_flux_conditionals: null argument");
     if (src->B != im->B || src->ctx != im->ctx) return fail(CEL_ERR_INVALID, "sources do not match images");
     { int rm = refuse_masked_unless_honoured(im, "cel_flux_conditionals"); if (rm) return rm; }
-    if (im->samp_S <= 0 || im->samp_S != src->S || !im->ssum_valid)
-        return fail(CEL_ERR_INVALID, "cel_flux_conditionals needs a resident photon split of these %lld sources (have %lld)",
-                    (long long)src->S, (long long)im->samp_S);
+    { int rs = need_resident_split(im, src, "cel_flux_conditionals", true); if (rs) return rs; }
     if (!(a0 > 0.0) || !(b0 > 0.0) || !(a0 < 1e300) || !(b0 < 1e300)) return fail(CEL_ERR_INVALID, "cel_flux_conditionals: a0 and b0 must be positive and finite");
     cel_ctx *c = im->ctx;
     const int B = im->B;
@@ -1949,12 +1870,10 @@ int cel_flux_conditionals(cel_images *im, cel_sources *src, uint64_t seed, doubl
     static_assert(offsetof(decltype(hc), ratio) == sizeof(int) * MAX_BANDS, "the upload is laid out as the block is carved");
     if (S > 0) {
         hipLaunchKernelGGL(k_flux_step, dim3((unsigned)((S * 5 + 255) / 256)), dim3(256), 0, c->stream, S, B, (const double *)im->d_ssum,
-                           (const double *)im->d_mass, (const int64_t *)im->d_soff, d_letter, d_ratio, d_ratio + MAX_BANDS, d_ratio + 2 * MAX_BANDS,
+                           (const double *)im->mass.values, (const int64_t *)im->d_soff, d_letter, d_ratio, d_ratio + MAX_BANDS, d_ratio + 2 * MAX_BANDS,
                            a0, b0, (unsigned long long)seed, src->d_counts, d_flux, d_act);
         HIP_TRY(hipGetLastError());
-        // the catalogue on the device has new counts: a new generation (no row stamps: everything may have changed)
-        src->gen = src->full_gen = ++g_source_gen;
-        src->row_gen.clear();
+        src->all_rows_changed(false);         // the catalogue on the device has new counts
         HIP_TRY(hipMemcpyAsync(flux_new, d_flux, sizeof(double) * 5 * S, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(active, d_act, sizeof(int) * S, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2018,9 +1937,7 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
     if (!im || !src) return fail(CEL_ERR_INVALID, "cel_slice_locations: null argument");
     { int rm = refuse_masked(im, "cel_slice_locations"); if (rm) return rm; }
     if (src->B != im->B || src->ctx != im->ctx) return fail(CEL_ERR_INVALID, "sources do not match images");
-    if (im->samp_S <= 0 || im->samp_S != src->S)
-        return fail(CEL_ERR_INVALID, "cel_slice_locations needs a resident photon split of these %lld sources (have %lld)",
-                    (long long)src->S, (long long)im->samp_S);
+    { int rs = need_resident_split(im, src, "cel_slice_locations"); if (rs) return rs; }
     if (!(sigma > 0.0) || max_rounds < 1) return fail(CEL_ERR_INVALID, "cel_slice_locations: sigma and max_rounds must be positive");
     cel_ctx *c = im->ctx;
     HIP_TRY(hipSetDevice(c->device));
@@ -2091,7 +2008,6 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
     HIP_TRY(hipMemcpyAsync(prop->d_counts, src->d_counts, sizeof(double) * B * S, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(prop->d_shape, src->d_shape, sizeof(double) * 4 * S, hipMemcpyDeviceToDevice, st));
     prop->S = S;
-    prop->n_gal = -1;
     if (chain_ids) {
         HIP_TRY(hipMemcpyAsync(d_ids, chain_ids, sizeof(int) * S, hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -2105,7 +2021,7 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
     // The blocks of a round.  With the recurrence kernels every (chain, band) job is one block, or PLL_PARTS blocks when it
     // is long (k_job_work), listed heaviest first; with photon lists a patch is scored either densely (k_patch_ll_hw<0>) or
     // at its photons (k_patch_ll_nz): two lists.  The photon rectangles, lists and routes are fixed for the call.
-    const bool use_nz = im->nz_valid && c->variant != 0;
+    const bool use_nz = im->split.nz_valid && c->variant != 0;
     int64_t n_dense = S * B, n_nz = 0;
     if (c->variant != 0) {
         const int nent = (int)(S * B * SLICE_SPLIT);
@@ -2196,7 +2112,7 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
             for (int k = 0; k < nb; k++) {
                 // the first round's points; every later round's were named by the step kernel of the round before
                 if (queued == 0) hipLaunchKernelGGL(k_slice_propose, dim3(g256), dim3(256), 0, st, ss, S, prop->d_radec, d_owner, d_flags);
-                prop->gen = prop->full_gen = ++g_source_gen;
+                prop->all_rows_changed(true);
                 // the first round's records; every later round's were written by the step kernel that named its points
                 if (queued == 0 && (rc = run_prep(im, prop, d_owner, 1))) return rc;      // the patch limits are fixed: no boxes
                 if (c->variant == 0) {
@@ -2251,8 +2167,7 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
     }
     // the new locations replace the catalogue's
     HIP_TRY(hipMemcpyAsync(src->d_radec, ss.x, sizeof(double) * 2 * S, hipMemcpyDeviceToDevice, st));
-    src->gen = src->full_gen = ++g_source_gen;
-    src->row_gen.clear();
+    src->all_rows_changed(false);
     if (radec_out) HIP_TRY(hipMemcpyAsync(radec_out, ss.x, sizeof(double) * 2 * S, hipMemcpyDeviceToHost, st));
     if (llh_out) HIP_TRY(hipMemcpyAsync(llh_out, ss.new_llh, sizeof(double) * S, hipMemcpyDeviceToHost, st));
     unsigned long long *d_bytes = reinterpret_cast<unsigned long long *>(((uintptr_t)(d_flags + 6) + 7) & ~(uintptr_t)7);
@@ -2345,9 +2260,8 @@ static int slice_type_move(cel_images *im, cel_sources *src, const int32_t *chai
                        chain_ids ? (const int *)d_ids : (const int *)nullptr, (const int64_t *)im->d_soff, (unsigned long long)seed,
                        prop->d_type, prop->d_radec, prop->d_counts, prop->d_shape, d_owner);
     prop->S = P;
-    prop->n_gal = -1;
-    prop->gen = prop->full_gen = ++g_source_gen;
-    const bool use_nz = im->nz_valid && c->variant != 0;
+    prop->all_rows_changed(true);
+    const bool use_nz = im->split.nz_valid && c->variant != 0;
     int64_t n_dense = P * B, n_nz = 0, n_mass = 0;
     int *h_flags = c->mail->sh.slice_flags;
     if (lists || exact) {
@@ -2391,11 +2305,7 @@ static int slice_type_move(cel_images *im, cel_sources *src, const int32_t *chai
     hipLaunchKernelGGL(k_tm_decide, dim3(g256), dim3(256), 0, st, tm, S, B, ostr, (const double *)d_ll, (const double *)d_exact,
                        (const double *)prop->d_shape, (int *)src->d_type, (double *)src->d_shape, d_out, d_flag, d_flags + 1);
     HIP_TRY(hipGetLastError());
-    // the catalogue on the device has new rows: a new generation
-    src->gen = src->full_gen = ++g_source_gen;
-    src->row_gen.clear();
-    src->n_gal = -1;
-    src->h_type.clear();
+    src->all_rows_changed(true);          // the catalogue on the device has new rows, types among them
     // one readback: the rows, log alpha and the flags lie one behind the other (the flags behind 6 S doubles)
     static_assert(sizeof(double) == 2 * sizeof(int), "the readback's layout");
     std::vector<double> back((size_t)(6 * S + (S + 1) / 2));
@@ -2404,16 +2314,14 @@ static int slice_type_move(cel_images *im, cel_sources *src, const int32_t *chai
     HIP_TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const int *hf = reinterpret_cast<const int *>(back.data() + 6 * S);
-    int64_t running = 0, accepted = 0, n_gal = 0;
-    src->h_type.resize((size_t)S);
+    int64_t running = 0, accepted = 0;
+    std::vector<int32_t> types((size_t)S);
     for (int64_t s = 0; s < S; s++) {
-        const int32_t t = (int32_t)back[(size_t)(5 * s)];
-        src->h_type[(size_t)s] = t;
-        n_gal += t != 0;
+        types[(size_t)s] = (int32_t)back[(size_t)(5 * s)];
         running += hf[s] >= 0;
         accepted += hf[s] == 1;
     }
-    src->n_gal = n_gal;
+    src->types_known(types.data(), S);
     if (x_out) memcpy(x_out, back.data(), sizeof(double) * 5 * S);
     if (llh_out) memcpy(llh_out, back.data() + 5 * S, sizeof(double) * S);
     if (stats) { stats[0] = 1; stats[1] = 2 * running; stats[2] = accepted; stats[3] = launches; }
@@ -2435,9 +2343,7 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
         return fail(CEL_ERR_INVALID, "cel_slice_sample: the exact conditional (CEL_OPT_SLICE_CONDITIONAL) is not supported on an image set "
                                      "with a row window (cel_images_set_window): its cover test is not window-relative");
     if (src->B != im->B || src->ctx != im->ctx) return fail(CEL_ERR_INVALID, "sources do not match images");
-    if (im->samp_S <= 0 || im->samp_S != src->S)
-        return fail(CEL_ERR_INVALID, "cel_slice_sample needs a resident photon split of these %lld sources (have %lld)",
-                    (long long)src->S, (long long)im->samp_S);
+    { int rs = need_resident_split(im, src, "cel_slice_sample"); if (rs) return rs; }
     if (param != 0 && param != 1 && param != 2) return fail(CEL_ERR_INVALID, "cel_slice_sample: param must be 0 (location), 1 (shape) or 2 (type)");
     if (!(sigma > 0.0) || max_rounds < 1 || max_steps_out < 0) return fail(CEL_ERR_INVALID, "cel_slice_sample: sigma and max_rounds must be positive");
     if (param == 2) return slice_type_move(im, src, chain_ids, dirs, numdir, seed, x_out, llh_out, stats);
@@ -2518,11 +2424,10 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
                        (const double *)src->d_radec, (const double *)src->d_counts, (const double *)src->d_shape,
                        prop->d_type, prop->d_radec, prop->d_counts, prop->d_shape);
     prop->S = 2 * S;
-    prop->n_gal = -1;
     hipLaunchKernelGGL(k_sg_init, dim3(g256), dim3(256), 0, st, g, rs, S, (const double *)(param ? src->d_shape : src->d_radec),
                        chain_ids ? (const int *)d_ids : (const int *)nullptr, (const int64_t *)im->d_soff, B, (const int *)src->d_type,
                        (unsigned long long)seed);
-    const bool use_nz = im->nz_valid && c->variant != 0;
+    const bool use_nz = im->split.nz_valid && c->variant != 0;
     int64_t rounds = 0, evals = 0, queued = 0;
     int *h_flags = c->mail->sh.slice_flags;
     int rc = CEL_OK;
@@ -2550,7 +2455,7 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
         for (int k = 0; k < nb; k++) {
             hipLaunchKernelGGL(k_sg_propose, dim3(g256), dim3(256), 0, st, g, rs, S, param ? prop->d_shape : prop->d_radec, d_owner, d_flags,
                                queued == 0 ? 1 : 0);
-            prop->gen = prop->full_gen = ++g_source_gen;
+            prop->all_rows_changed(true);
             // the patch limits are fixed: no boxes -- but the exact conditional needs the proposals' own (cover test, mass)
             if ((rc = run_prep(im, prop, d_owner, exact ? 0 : 1))) return rc;
             if (exact)
@@ -2606,7 +2511,7 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
     }
     // the new states replace the catalogue's
     HIP_TRY(hipMemcpyAsync(param ? src->d_shape : src->d_radec, g.x, sizeof(double) * D * S, hipMemcpyDeviceToDevice, st));
-    src->gen = src->full_gen = ++g_source_gen; src->row_gen.clear();
+    src->all_rows_changed(false);
     if (x_out) HIP_TRY(hipMemcpyAsync(x_out, g.x, sizeof(double) * D * S, hipMemcpyDeviceToHost, st));
     if (llh_out) HIP_TRY(hipMemcpyAsync(llh_out, g.new_llh, sizeof(double) * S, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -2648,18 +2553,16 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
     // with the split's strict boxes (the model image of cel_images_get_lambda is left alone).
     // Direct form: a plain render (its kernel accumulates the totals itself).
     const bool hw = (c->variant != 0) && (im->TW == HW_TW);
-    im->split_epoch++;                          // (masses waiting for cel_stamp_mass_end share a scratch slot with this call's partial sums)
+    im->split_begins(hw);
     // a masked set under CEL_OPT_HONOUR_MASK: the masked twins (no photons, no sky, no draws at a masked pixel), no mass short cut
     const bool masked = honours_mask(im);
     bool use_massfx = false;
     const double *full_rate = nullptr;
     int rc;
-    if (!hw) im->partials_gen = 0;              // (the direct form keeps its noise partials in the render's buffer)
     if (hw) {
         const int64_t npix = (int64_t)im->B * im->H * im->W;
         HIP_TRY(im->d_rate.grow(npix, npix, c->stream));
-        im->massfx_gen = 0;
-        const bool current = src->gen != 0 && im->lambda_gen == src->gen && im->lists_gen == src->gen && im->recs_gen == src->gen;
+        const bool current = im->model_current(*src);
         if (c->split_full) {
             // CEL_OPT_SPLIT_FULL_BOX: a source takes part on its WHOLE box, so the totals are the model image itself -- the one
             // on the device when it is these sources', a render into the totals image otherwise
@@ -2720,8 +2623,6 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
         HIP_TRY(im->d_samp.grow(total, total + total / 8 + 1024, c->stream));
         d_off = im->d_soff;
         d_samp = im->d_samp;
-        im->samp_S = S;
-        im->samp_total = total;
     } else {
         // the caller's layout against the sources' own boxes (cel_source_boxes): a patch too small for its box would be
         // written past its end
@@ -2745,10 +2646,9 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
     // resident + recurrence form: the kernel writes every interior pixel and reduces the photon
     // rectangles itself; otherwise zero the buffer and (resident) find the rectangles afterwards
     const bool fused_nz = resident && hw && n > 0;
-    if (resident) im->ssum_valid = fused_nz;
+    if (resident) im->split_laid_out(S, total, fused_nz);
     // photon lists: pixel coordinates are packed into 16 bits each
     const bool lists = fused_nz && im->W < 65536 && (im->win_y0 + im->H) < 65536 && c->nz_force != 2;
-    if (resident) im->nz_valid = false;
     if (fused_nz) HIP_TRY(hipMemsetAsync(im->d_ssum, 0, sizeof(double) * n, c->stream));
     if (lists) HIP_TRY(hipMemsetAsync(im->d_nnz, 0, sizeof(int) * n, c->stream));
     if (fused_nz)
@@ -2766,7 +2666,7 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
         a.noise_y0 = im->noise_y0; a.noise_y1 = im->noise_y1;
         a.rate_img = full_rate ? full_rate : im->d_rate; a.tail_T = c->tail_T; a.nz = fused_nz ? im->d_snz : nullptr;
         a.strict = c->split_full ? 0 : 1;
-        im->rate_in_lambda = full_rate != nullptr;
+        im->split_totals_from_model(full_rate != nullptr);
         a.order = (hw && tile_order_of(c, im)) ? im->d_order : nullptr;
         a.sums = fused_nz ? im->d_ssum : nullptr;
         a.nnz = lists ? im->d_nnz : nullptr;
@@ -2804,7 +2704,6 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
     }
     HIP_TRY(hipMemcpyAsync(c->mail->ll_band, im->d_llband, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
     if (lists) HIP_TRY(hipMemcpyAsync(&c->mail->sh.scan_total, im->d_nzoff + n, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    if (resident) im->hsum_valid = false;
     if (fused_nz) {
         // what a Gibbs sweep asks for next (the photons per source: the flux and sky steps; the patch areas) rides back now:
         // cel_samples_fetch then needs no wait of its own, and the list compaction queued below runs under the host's work
@@ -2819,9 +2718,8 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
         HIP_TRY(hipMemcpyAsync(samp, d_samp, sizeof(double) * total, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (fused_nz) im->hsum_valid = true;
+    im->split_ends(fused_nz, (use_massfx && hw && resident) ? src->gen : 0);
     if (noise) for (int b = 0; b < B; b++) noise[b] = c->mail->ll_band[b];
-    if (use_massfx && hw && resident) im->massfx_gen = src->gen;
     if (lists) {
         const int64_t nn = c->mail->sh.scan_total;
         HIP_TRY(im->d_nzlist.grow(nn, nn + nn / 4 + 1024, c->stream));
@@ -2829,26 +2727,26 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
         hipLaunchKernelGGL(k_nz_compact, dim3((unsigned)n), dim3(64), 0, c->stream, (const int4 *)im->d_sbox, (const int64_t *)im->d_soff,
                            (const int *)im->d_samp, (const int4 *)im->d_snz, (const int64_t *)im->d_nzoff, im->d_nzlist);
         HIP_TRY(hipGetLastError());
-        im->nz_valid = true;
+        im->split_lists_built();
     }
     return CEL_OK;
 }
 
 int cel_samples_info(cel_images *im, int64_t *S, int64_t *total) {
     if (!im || !S || !total) return fail(CEL_ERR_INVALID, "cel_samples_info: null argument");
-    *S = im->samp_S;
-    *total = im->samp_total;
+    *S = im->split.samp_S;
+    *total = im->split.samp_total;
     return CEL_OK;
 }
 
 int cel_samples_fetch(cel_images *im, int32_t *boxes, int64_t *offsets, double *data, double *sums) {
     if (!im) return fail(CEL_ERR_INVALID, "cel_samples_fetch: null argument");
-    if (im->samp_S <= 0) return fail(CEL_ERR_INVALID, "no resident photon split: call cel_photon_split with offsets = NULL first");
+    if (im->split.samp_S <= 0) return fail(CEL_ERR_INVALID, "no resident photon split: call cel_photon_split with offsets = NULL first");
     cel_ctx *c = im->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    const int64_t n = im->samp_S * im->B;
+    const int64_t n = im->split.samp_S * im->B;
     int rc = CEL_OK;
-    if (!boxes && !data && im->hsum_valid && n + 1 <= im->h_ssum.cap) {        // host copies made by the split itself: no wait
+    if (!boxes && !data && im->split.hsum_valid && n + 1 <= im->h_ssum.cap) {        // host copies made by the split itself: no wait
         if (offsets) memcpy(offsets, im->h_soff, sizeof(int64_t) * (n + 1));
         if (sums) memcpy(sums, im->h_ssum, sizeof(double) * n);
         return CEL_OK;
@@ -2861,13 +2759,13 @@ int cel_samples_fetch(cel_images *im, int32_t *boxes, int64_t *offsets, double *
         }
     }
     if (offsets && (rc = copy_out(offsets, im->d_soff, sizeof(int64_t) * (n + 1), CEL_HOST, c->stream))) return rc;
-    if (data && im->samp_total > 0) {           // int32 on the device, doubles across the ABI
-        std::vector<int> hs((size_t)im->samp_total);
-        if ((rc = copy_out(hs.data(), im->d_samp, sizeof(int) * im->samp_total, CEL_HOST, c->stream))) return rc;
-        for (int64_t i = 0; i < im->samp_total; i++) data[i] = (double)hs[(size_t)i];
+    if (data && im->split.samp_total > 0) {           // int32 on the device, doubles across the ABI
+        std::vector<int> hs((size_t)im->split.samp_total);
+        if ((rc = copy_out(hs.data(), im->d_samp, sizeof(int) * im->split.samp_total, CEL_HOST, c->stream))) return rc;
+        for (int64_t i = 0; i < im->split.samp_total; i++) data[i] = (double)hs[(size_t)i];
     }
     if (sums) {
-        if (im->ssum_valid) {       // the split kernel summed them itself (exact: integer-valued)
+        if (im->split.ssum_valid) {       // the split kernel summed them itself (exact: integer-valued)
             if ((rc = copy_out(sums, im->d_ssum, sizeof(double) * n, CEL_HOST, c->stream))) return rc;
         } else {
             double *d_sums = nullptr;
@@ -2881,11 +2779,11 @@ int cel_samples_fetch(cel_images *im, int32_t *boxes, int64_t *offsets, double *
 
 int cel_samples_photon_rects(cel_images *im, int32_t *rects) {
     if (!im || !rects) return fail(CEL_ERR_INVALID, "cel_samples_photon_rects: null argument");
-    if (im->samp_S <= 0 || !im->d_snz)
+    if (im->split.samp_S <= 0 || !im->d_snz)
         return fail(CEL_ERR_INVALID, "no resident photon split: call cel_photon_split with offsets = NULL first");
     cel_ctx *c = im->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    const int64_t n = im->samp_S * im->B;
+    const int64_t n = im->split.samp_S * im->B;
     std::vector<int4> hb((size_t)n);
     int rc = copy_out(hb.data(), im->d_snz, sizeof(int4) * n, CEL_HOST, c->stream);
     if (rc) return rc;
@@ -2920,7 +2818,7 @@ int cel_estep_stats(cel_images *im, cel_sources *src, double *xtilde, double *ma
     const int B = im->B;
     const int64_t S = src->S;
     const int nblk = im->ntx * im->nty;                 // d_partials holds B * nblk doubles
-    im->partials_gen = 0;                               // ... of this call's sky term from here on
+    im->partials_overwritten();                         // ... of this call's sky term from here on
     double *d_x = nullptr, *d_m = nullptr, *d_part = nullptr;
     // recurrence evaluator on the 32 x 64 layout: the tile-walking form (the render above left the
     // lists and boxes of exactly these sources on the device); CEL_OPT_DEBUG bit 64 keeps the per-source form

@@ -594,6 +594,23 @@ def test_hot_kernels_keep_their_resource_budget(built):
         assert k[name]["scratch"] <= budget[name]["max_scratch"]
 
 
+def test_state_events_drop_what_their_table_says(tmp_path):
+    """csrc/field_state.h on the CPU (it names no HIP type): tests/host/field_state_events.cpp sets every cached product "vouched
+    for catalogue A", fires each event once and asserts exactly which predicates still hold -- DESIGN.md's event table row by row,
+    and the catalogue's three functions -- as a stand-alone program under the address and undefined-behaviour sanitizers"""
+    import shutil
+    cxx = next((c for c in (os.environ.get("CXX"), "g++", "c++", "clang++") if c and shutil.which(c)), None)
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "field_state_events")
+    # (the sanitizers' runtimes linked INTO the program -- clang's default: it runs whatever else the loader brings along)
+    static = [] if "clang" in os.path.basename(cxx) else ["-static-libasan", "-static-libubsan"]
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] + static +
+                   ["-I", os.path.join(ROOT, "desi-mcmc_amd", "csrc"), os.path.join(ROOT, "tests", "host", "field_state_events.cpp"), "-o", exe],
+                   check=True, capture_output=True, text=True)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stdout.strip() == "field_state: ok", run.stdout + run.stderr
+
+
 def test_mog_sampling_api(built):
     """mog_samples / discrete / MixtureOfGaussians.rvs / var (util/dists/mog.py:25-37,69-73): host-side draws"""
     from desi_mcmc_amd.util.dists import mog

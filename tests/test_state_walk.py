@@ -23,8 +23,12 @@ type move, n_gal left stale by the type move, lambda_gen kept by cel_images_set_
 cel_stamp_mass_end without its check -- while test_stress.py, test_hip_parity.py and test_type_move.py pass on the first, second and
 fifth of them (the table is in the message of the change that added this file).
 
+The stamps' only writers are the events of csrc/field_state.h (DESIGN.md section 4b names, per event and product, the test that
+would notice its loss); the two the walk cannot reach -- a new window under cached products (in the walk the window only frames a
+refusal) and the observed pixels' address handed out -- are scripted in test_named_transitions (8., 9.).
+
 Timings, measured on the MI355X: a walk of 250 steps takes 0.5 - 1.6 s (the first of a session 3.2 s with the library's load and
-the scene's draw), test_named_transitions 0.4 s, the whole file 4.5 s.
+the scene's draw), test_named_transitions 0.3 - 0.4 s, the whole file 4.5 s.
 """
 import numpy as np
 import pytest
@@ -203,4 +207,44 @@ def test_named_transitions(cel):
     w = sw.Walker(cel)
     w.walk([_op("render", 1, loglik=True), _op("set_epsilon", 2), _op("set_rows_1", 3), _op("render_noll", 4)])
     w.walk([_op("render", 5, loglik=True), _op("set_epsilon", 6), _op("split_cold", 7), _op("flux", 8), _op("render", 9, loglik=True)])
+    w.close()
+
+    # 8. a new window cuts the boxes anew: the host's boxes, the split's stamp sums and (with the records of the same catalogue
+    #    written again, and row stamps to go by) the model image and tile lists of the old window must not be taken
+    w = sw.Walker(cel)
+    w.walk([_op("render", 1, loglik=True), _op("split_traced", 2), _op("mass", 3)])
+    old = w.im.source_boxes(w.ss)
+    assert w.im.stamp_mass_ready(w.ss)
+    w.run(_op("window_on", 4))
+    rim, rss = w.fresh(w.cur)
+    rim.set_window(32, sw.H + 64)
+    assert not w.im.stamp_mass_ready(w.ss)
+    new = w.im.source_boxes(w.ss)
+    assert not np.array_equal(new[0], old[0])
+    w.same("boxes behind a new window", new, rim.source_boxes(rss))
+    w.same("masses behind a new window", w.im.stamp_mass(w.ss), rim.stamp_mass(rss))
+    w.run(_op("set_rows_1", 5))
+    rss.set(*w.cur)
+    out = w.im.render(w.ss, loglik=True)
+    assert w.im.last_render_dirty_tiles() == -1
+    w.same("render behind a new window: log-likelihood", out, rim.render(rss, loglik=True))
+    w.same("render behind a new window: model images", w.im.model_images(), rim.model_images())
+    rim.close()
+    w.close()
+
+    # 9. the observed pixels' address handed out: the caller writes them when it likes, and no tile's Poisson partial outlives it
+    import ctypes as C
+    w = sw.Walker(cel)
+    w.walk([_op("render", 1, loglik=True), _op("set_rows_1", 2), _op("render", 3, loglik=True)])
+    assert w.im.last_render_dirty_tiles() >= 0                      # (the dirty-tile render is this set's, until ...)
+    pixels = np.ascontiguousarray(w.sc["nelec"][0] + 1.0)
+    hip = C.CDLL(cel._lib.LIB_PATH)                                 # (dlsym through the library finds the HIP runtime IT is linked to)
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    assert hip.hipMemcpy(w.im.device_ptrs()[0], pixels.ctypes.data, pixels.nbytes, 1) == 0
+    w.run(_op("set_rows_1", 4))
+    out = w.im.render(w.ss, loglik=True)
+    assert w.im.last_render_dirty_tiles() == -1
+    rim = cel.ImageSet(w.ctx, w.bands(w.eps), sw.H, sw.W, nelec=pixels)
+    w.same("render behind the caller's own pixels", out, rim.render(cel.SourceSet(w.ctx, w.n, sw.B).set(*w.cur), loglik=True))
+    rim.close()
     w.close()
