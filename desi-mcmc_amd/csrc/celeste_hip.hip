@@ -805,6 +805,7 @@ int cel_images_set_window(cel_images *im, int y0, int full_H) {
     if (!im) return fail(CEL_ERR_INVALID, "null images");
     if (y0 < 0 || full_H < 1 || (int64_t)y0 + im->H > full_H)
         return fail(CEL_ERR_INVALID, "window rows [%d, %d) do not fit a %d-row frame", y0, y0 + im->H, full_H);
+    if (y0 == im->win_y0 && full_H == im->full_H) return CEL_OK;       // the window it has: nothing is cut anew, nothing dropped
     im->win_y0 = y0;
     im->full_H = full_H;
     im->new_window();
@@ -1723,7 +1724,7 @@ int cel_patch_loglik(cel_images *im, cel_sources *src, const int32_t *boxes, con
 // other.  Removed again.)
 // may the masses come from the split's own stamp sums (cel_stamp_mass_ready answers it, cel_stamp_mass_begin acts on it)
 static bool masses_from_split(const cel_images *im, const cel_sources *src) {
-    return !honours_mask(im) && im->ctx->mass_reuse_of() && im->split.sums_of(*src) && src->S * im->B <= im->d_massfx.cap;
+    return !honours_mask(im) && im->ctx->mass_reuse_of() && im->split.sums_of(*src, im->ctx->tail_T) && src->S * im->B <= im->d_massfx.cap;
 }
 
 int cel_stamp_mass_ready(cel_images *im, cel_sources *src, int *ready) {
@@ -2562,7 +2563,7 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
     if (hw) {
         const int64_t npix = (int64_t)im->B * im->H * im->W;
         HIP_TRY(im->d_rate.grow(npix, npix, c->stream));
-        const bool current = im->model_current(*src);
+        const bool current = im->model_current(*src, c->render_T);
         if (c->split_full) {
             // CEL_OPT_SPLIT_FULL_BOX: a source takes part on its WHOLE box, so the totals are the model image itself -- the one
             // on the device when it is these sources', a render into the totals image otherwise
@@ -2718,7 +2719,7 @@ int cel_photon_split(cel_images *im, cel_sources *src, uint64_t seed, const int6
         HIP_TRY(hipMemcpyAsync(samp, d_samp, sizeof(double) * total, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
-    im->split_ends(fused_nz, (use_massfx && hw && resident) ? src->gen : 0);
+    im->split_ends(fused_nz, (use_massfx && hw && resident) ? src->gen : 0, c->tail_T);
     if (noise) for (int b = 0; b < B; b++) noise[b] = c->mail->ll_band[b];
     if (lists) {
         const int64_t nn = c->mail->sh.scan_total;

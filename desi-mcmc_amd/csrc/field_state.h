@@ -89,8 +89,10 @@ struct SplitStamps {
     bool rate_in_lambda = false;            // the last split read its totals from the model image itself
     uint64_t split_epoch = 0;               // photon splits of this set so far
     uint64_t massfx_gen = 0;                // d_massfx holds the stamp sums of the catalogue of this generation (0: of none)
+    double massfx_T = -1.0;                 // ... formed at this per-source drop threshold
     bool resident_of(int64_t S) const { return samp_S > 0 && samp_S == S; }
-    bool sums_of(const SourceStamps &src) const { return src.gen != 0 && massfx_gen == src.gen; }
+    // the stamp sums are this catalogue's, and they carry the drop rule the mass kernel would apply now
+    bool sums_of(const SourceStamps &src, double tail_T) const { return src.gen != 0 && massfx_gen == src.gen && massfx_T == tail_T; }
     void drop() { samp_S = samp_total = 0; ssum_valid = hsum_valid = nz_valid = false; massfx_gen = 0; }
 };
 
@@ -126,9 +128,11 @@ struct FieldState {
     bool nelec_shared = false;       // cel_images_device_ptrs handed the observed pixels' device pointer out
 
     // ---- what the short cuts ask ----
-    // model image, tile lists and records are all of exactly this catalogue: the split may take its totals from the image
-    bool model_current(const SourceStamps &src) const {
-        return src.gen != 0 && model.lambda_gen == src.gen && lists.lists_gen == src.gen && rec.recs_gen == src.gen;
+    // model image, tile lists and records are all of exactly this catalogue, the image rendered at the threshold a render
+    // would take now: the split may take its totals from the image
+    bool model_current(const SourceStamps &src, double render_T) const {
+        return src.gen != 0 && model.lambda_gen == src.gen && model.lambda_T == render_T && lists.lists_gen == src.gen &&
+               rec.recs_gen == src.gen;
     }
     // the image, lists, records (and, for a log-likelihood, partials) of an EARLIER generation of this catalogue object of S
     // sources, rendered at this threshold by one block per tile, with row stamps for everything since: the dirty-tile render
@@ -148,8 +152,9 @@ struct FieldState {
     void pixels_handed_out() { nelec_u16 = false; nelec_shared = true; model.partials_gen = 0; }
     // cel_images_set_epsilon: the image was rendered with the old sky level, the partials against it
     void new_sky_level() { model.lambda_gen = 0; model.partials_gen = 0; }
-    // cel_images_set_window: boxes are cut to the window
-    void new_window() { rec.recs_gen = rec.hbox_gen = 0; model.lambda_gen = lists.lists_gen = 0; split.massfx_gen = 0; }
+    // cel_images_set_window (another window than before): boxes are cut to the window, and the resident split's patches are
+    // boxes of the old one
+    void new_window() { rec.recs_gen = rec.hbox_gen = 0; model.lambda_gen = lists.lists_gen = 0; split.drop(); }
     void records_regrown() { rec.recs_gen = rec.hbox_gen = 0; }
     // k_prep ran on S sources; gen = 0: a partial table or one without boxes is nobody's
     void records_written(uint64_t gen, int64_t S) { rec.recs_gen = gen; rec.last_S = S; }
@@ -196,10 +201,11 @@ struct FieldState {
         split.hsum_valid = split.nz_valid = false;
     }
     void split_totals_from_model(bool yes) { split.rate_in_lambda = yes; }
-    // the split has run: host_sums -- its sums and offsets lie in the pinned copies; stamp_sums_gen != 0 -- d_massfx is this catalogue's
-    void split_ends(bool host_sums, uint64_t stamp_sums_gen) {
+    // the split has run: host_sums -- its sums and offsets lie in the pinned copies; stamp_sums_gen != 0 -- d_massfx is this
+    // catalogue's, summed under the per-source drop threshold tail_T
+    void split_ends(bool host_sums, uint64_t stamp_sums_gen, double tail_T) {
         if (host_sums) split.hsum_valid = true;
-        if (stamp_sums_gen) split.massfx_gen = stamp_sums_gen;
+        if (stamp_sums_gen) { split.massfx_gen = stamp_sums_gen; split.massfx_T = tail_T; }
     }
     void split_lists_built() { split.nz_valid = true; }
 };

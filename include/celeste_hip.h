@@ -260,7 +260,12 @@ int cel_images_set_epsilon(cel_images *img, int band, double eps);
 /* Declare that this image set holds rows [y0, y0 + H) of a full_H-row frame (row-strip partition
  * of one field across GPUs).  Source boxes and the overlap test are formed against
  * the full frame (celeste.py:130-140) and then cut to the window, so the strips tile the frame's
- * model image exactly.  WCS (rho) stays that of the full frame. */
+ * model image exactly.  WCS (rho) stays that of the full frame.
+ * ANOTHER window than the set has drops what was cut to the old one: records, boxes, tile lists, the model image, and the
+ * RESIDENT SPLIT, whose patches are boxes of the old window -- cel_samples_info reports S = 0, cel_stamp_mass_ready answers 0,
+ * the calls that need the split fail with CEL_ERR_INVALID naming the missing split (as after cel_images_set_nelec) and a pending
+ * cel_stamp_mass_begin is refused by its _end, until the next resident cel_photon_split.  Set the window when the set is
+ * created, before the first split.  The same (y0, full_H) again changes nothing and drops nothing. */
 int cel_images_set_window(cel_images *img, int y0, int full_H);
 /* The rows [y0, y1) of THIS image set (window-relative) that it OWNS; default: every row.  cel_photon_split's noise sums count
  * the left-over photons of these rows only, and cel_render_field's log-likelihood adds the Poisson terms of these rows only
@@ -277,7 +282,9 @@ int cel_images_get_lambda(cel_images *img, double *out, int mem);
  * 16-bit photons-left plane) until the next cel_images_set_nelec, and from then on keeps no per-tile Poisson sums between
  * renders (CEL_OPT_INCREMENTAL renders every tile when a log-likelihood is asked for).  nelec = NULL asks for neither.
  * The mask state (cel_images_set_nelec) is taken when cel_images_set_nelec runs: a caller who writes pixels through this pointer
- * must neither create nor remove NaNs */
+ * must neither create nor remove NaNs.  A resident photon split stays the split of the pixels it was drawn from: handing the
+ * address out drops none (the library cannot know when the caller writes), and cel_images_set_nelec is how a caller announces
+ * new pixels */
 int cel_images_device_ptrs(cel_images *img, void **nelec, void **lambda);
 /* device pointer of the B per-band log-likelihoods of the LAST render with CEL_RENDER_LOGLIK (doubles, valid until the next
  * render, photon split or E-step call on this image set -- they reduce into the same buffer; the stream has been synchronised
@@ -401,7 +408,9 @@ int cel_gamma_streams(cel_ctx *ctx, int64_t n, const double *a, uint64_t seed, d
  * Right after a resident cel_photon_split of the same catalogue that took its totals from the model image on the device
  * (CEL_OPT_SPLIT_REUSE = 2) the values are read off the sums that split made (see the option); cel_stamp_mass_ready says
  * whether this call would: a caller that could also ask for a part of the catalogue only (a rank of a dealt chain) then asks
- * for the whole, which costs nothing and gives every rank the numbers the single-rank chain has. */
+ * for the whole, which costs nothing and gives every rank the numbers the single-rank chain has.  The sums carry the drop rule of
+ * the split that made them: they serve while the per-source threshold (CEL_OPT_TAIL_LOG / CEL_OPT_TAIL_LOG_SOURCE) is the one
+ * that split ran at; under another one cel_stamp_mass_ready answers 0 and cel_stamp_mass / _begin run the mass kernel. */
 int cel_stamp_mass(cel_images *img, cel_sources *src, double *mass);
 int cel_stamp_mass_ready(cel_images *img, cel_sources *src, int *ready);
 /* The same in two halves: _begin queues the kernel and returns, _end waits and copies the S*B values out -- so that the host

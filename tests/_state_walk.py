@@ -12,6 +12,24 @@ the replay reference        for every operation that returns numbers: FRESH Imag
                             dropped.  The reference is the same library without memory, so every comparison is bit for bit
                             (stamp masses besides: also against an object that never had a split, to the short cut's bound).
 
+The replay rule, now that the walk also changes what every cached product depends on (the row window, the owned rows, the
+context's options):
+  * the fresh pair is given today's window and owned rows FIRST, before any call (Walker.fresh);
+  * a resident split is replayed with its own catalogue and seed and with the options OF ITS TIME (Walker.time_options: the
+    earlier snapshot extended by both thresholds and the kernel variant, and -- the header has them "agree to rounding between
+    settings", so the totals behind a split are a product of their time too -- by CEL_OPT_TILE_PARTS and CEL_OPT_STAR_TILES).
+    Its draws are a product of their time.  A split made under another window is never replayed: the generator's model, like
+    the library, says there is none;
+  * every deterministic reader -- the render in either form, model_images, stamp_mass / _begin / _end, estep, grad, pll,
+    source_boxes, and the split's totals via split_rates() -- is compared with a fresh computation under TODAY's options: a live
+    pair that answers from a product of another threshold, variant or window shows up as a bit difference.  Right after a split,
+    split_rates() equals that of a fresh pair that made EVERYTHING at the options in force at the split;
+  * the replay never sees the history of CEL_OPT_TILE_ORDER and CEL_OPT_SLICE_FUSE (nor, for the deterministic readers, of
+    CEL_OPT_TILE_PARTS and CEL_OPT_STAR_TILES): it is built under today's values, and no equality across values is asserted.
+A model image of one threshold under a split at another is "cold" by the documented rule, like a new sky level: the generator
+calls that split split_cold, and its replay renders nothing first (the two forms of the totals agree to 1e-10, not bit for bit:
+CEL_OPT_SPLIT_REUSE).
+
 The walker runs on a Context of its own: its option flips never reach the session's shared context.
 """
 import random
@@ -21,13 +39,51 @@ SET_ROWS = ("set_rows_1", "set_rows_3", "set_rows_20", "set_rows_70")
 SAMPLERS = ("flux", "slice_locations", "slice_sample0_comp", "slice_sample0_dirs", "slice_sample1", "type_move")
 EXACT = ("exact_slice0", "exact_slice1", "exact_type_move")
 OPTIONS = ("opt_incremental", "opt_split_reuse", "opt_honour_mask", "opt_split_full_box")
-#: every operation of the walk (what the coverage counts); window_on / window_off only frame the windowed refusal
-OPERATIONS = SET_ROWS + ("set", "render", "render_noll", "split_traced", "split_cold", "mass", "mass_begin", "mass_end") + SAMPLERS \
+#: the operations of the "gibbs" and "edits" walks (their window_to comes with the windowed refusal alone) ...
+BASE_OPERATIONS = SET_ROWS + ("set", "render", "render_noll", "split_traced", "split_cold", "mass", "mass_begin", "mass_end") + SAMPLERS \
     + EXACT + ("pll", "pll_isolated", "estep", "grad", "set_epsilon", "set_nelec") + OPTIONS
+#: ... and the inputs every cached product depends on, walked by "strips" and "options": the row window, the owned rows, the
+#: context options that change results (thresholds, kernel variant) and those that must not (tile order, tile parts, slice fuse),
+#: the observed pixels' address handed out
+INPUTS = ("window_to", "noise_rows", "opt_tail", "opt_kernel", "opt_tile_order", "opt_tile_parts", "opt_slice_fuse", "hand_out")
+#: every operation of the walk (what the coverage counts)
+OPERATIONS = BASE_OPERATIONS + INPUTS
+#: the walk on the stars_only scene: what keeps a catalogue without galaxies one, and CEL_OPT_STAR_TILES
+STAR_OPERATIONS = SET_ROWS + ("set", "render", "render_noll", "split_traced", "split_cold", "mass", "mass_begin", "mass_end", "flux", "slice_locations",
+                              "pll", "estep", "grad", "set_epsilon", "opt_incremental", "opt_split_reuse", "noise_rows", "opt_tail", "opt_tile_order",
+                              "opt_tile_parts", "opt_star_tiles", "hand_out")
+WINDOWS = ((0, 192), (32, 256), (64, 256), (0, 256))       # (y0, full_H) of cel_images_set_window: none, a strip inside, the last strip, the first
+NOISE_ROWS = ((0, 192), (0, 64), (64, 128), (64, 192))     # owned rows: all, and what 64-row render tiles allow a log-likelihood
+#: CEL_OPT_TAIL_LOG's presets, CEL_OPT_TAIL_LOG_SOURCE = 8 alone and CEL_OPT_TAIL_LOG = 8 (both): a component is dropped below
+#: e^-8 = 3e-4 of a sky pixel, so a product of the coarse threshold misses the others by orders of magnitude above rounding
+TAILS = ("default", "strict", "fast", "source8", "all8")
+#: what may run while the context is on the direct kernels: the deterministic readers and the inputs.  A split or a sampler
+#: under CEL_OPT_KERNEL = 0 is other tests' subject; the generator returns to the recurrence first
+DIRECT_OK = SET_ROWS + ("set", "render", "render_noll", "mass", "mass_begin", "mass_end", "estep", "grad", "set_epsilon", "set_nelec") + OPTIONS + INPUTS \
+    + ("opt_star_tiles",)
+
+
+def tail_of(now, name):
+    """(field render's threshold, per-source threshold) after opt_tail `name` from `now`"""
+    return {"default": (24.0, 32.0), "strict": (32.0, 32.0), "fast": (20.0, 20.0), "source8": (now[0], 8.0), "all8": (8.0, 8.0)}[name]
+
+
+#: what "strips" and "options" owe: the inputs, and the products and readers that depend on them (the masked sets, the exact
+#: conditional and the rest of BASE_OPERATIONS come as the weights have them: "gibbs" and "edits" owe those)
+INPUT_OPERATIONS = INPUTS + ("set_rows_1", "set_rows_3", "render", "render_noll", "split_traced", "split_cold", "mass", "mass_begin", "mass_end") \
+    + SAMPLERS + ("pll", "estep", "grad", "set_epsilon")
+
+
+def required(flavour):
+    return {"gibbs": BASE_OPERATIONS, "edits": BASE_OPERATIONS, "stars": STAR_OPERATIONS}.get(flavour, INPUT_OPERATIONS)
+
+
 #: the documented refusals: a masked set without CEL_OPT_HONOUR_MASK (split, flux); slice_*, the type move and the isolated
 #: patch_loglik on any masked set; the exact conditional on a windowed set; no resident split; _end behind a rebuilt catalogue
 REFUSALS = ("masked_unhonoured", "masked_sampler", "window", "no_split", "end_rebuilt")
 PATTERNS = ("pattern_dirty", "pattern_ready", "pattern_end_rebuilt", "pattern_eps")
+#: ("strips", "options") a product, then the input it depends on changed, then its reader
+INPUT_PATTERNS = ("pattern_tail_split", "pattern_tail_mass", "pattern_window_split", "pattern_rows_dirty", "pattern_kernel_dirty")
 PROBES = ("probe_no_split", "probe_masked_unhonoured", "probe_masked_sampler", "probe_window")
 
 _W_COMMON = {"set": 2, "render_noll": 2, "mass_begin": 3, "pll": 3, "pll_isolated": 2, "estep": 2, "grad": 2, "set_epsilon": 3, "set_nelec": 2,
@@ -43,6 +99,14 @@ FLAVOURS = {
                                 "split_cold": 3, "mass": 4, "flux": 3, "slice_locations": 2, "slice_sample0_comp": 1, "slice_sample0_dirs": 1,
                                 "slice_sample1": 2, "type_move": 3, "exact_slice0": 1, "exact_slice1": 1, "exact_type_move": 1}),
 }
+_W_INPUTS = {"window_to": 2, "noise_rows": 2, "opt_tail": 2, "opt_kernel": 1, "opt_tile_order": 1, "opt_tile_parts": 2, "opt_slice_fuse": 1, "hand_out": 1}
+# the row-strip deal's inputs under every sampler and the render
+FLAVOURS["strips"] = dict(FLAVOURS["gibbs"], **dict(_W_INPUTS, window_to=14, noise_rows=12, render=12, set_rows_1=5, hand_out=3))
+# the context's options between a product and its reader
+FLAVOURS["options"] = dict(FLAVOURS["edits"], **dict(_W_INPUTS, opt_tail=14, opt_kernel=5, opt_tile_order=5, opt_tile_parts=8, opt_slice_fuse=4,
+                                                    split_traced=9, split_cold=7, mass=12, flux=5, slice_locations=4))
+FLAVOURS["stars"] = {k: {"render": 10, "set_rows_1": 6, "opt_star_tiles": 8, "split_traced": 4, "mass": 4, "flux": 4, "opt_tile_parts": 4}.get(k, 2)
+                     for k in STAR_OPERATIONS}
 NEED = 3            # every operation at least so often
 
 
@@ -52,8 +116,10 @@ class _Abstract(object):
     def __init__(self):
         self.nelec = 0                  # 0 plain, 1 one pixel above 65 535, 2 a few NaNs (a MASKED set)
         self.inc, self.reuse, self.honour, self.full = 1, 2, 0, 0
-        self.split = None               # dict(full=, dirty=) of the resident split, None without one
-        self.window = False
+        self.split = None               # dict(full=, dirty=, sums=, tail=) of the resident split, None without one
+        self.window, self.noise = WINDOWS[0], NOISE_ROWS[0]
+        self.tail = (24.0, 32.0)        # the thresholds of the field render and of the per-source kernels
+        self.variant, self.parts, self.star = 1, 1, 1
 
     def refusal(self, name):
         masked = self.nelec == 2
@@ -66,11 +132,13 @@ class _Abstract(object):
         if name in SAMPLERS or name in EXACT or name == "pll_isolated":
             if masked:
                 return "masked_sampler"
-            if name in EXACT and self.window:
+            if name in EXACT and self.window != WINDOWS[0]:
                 return "window"
             return None if self.split else "no_split"
         if name == "pll":
             return None if self.split else "no_split"
+        if name == "grad":              # (cel_loglik_grad: no row window)
+            return "window" if self.window != WINDOWS[0] else None
         return None
 
 
@@ -82,14 +150,23 @@ def ops(seed, steps, flavour):
     names, w = list(weights), [weights[k] for k in weights]
     st = _Abstract()
     out = []
-    count = dict.fromkeys(OPERATIONS, 0)
+    count = dict.fromkeys(required(flavour), 0)
     backlog = list(PATTERNS) * 2 + list(PROBES)
+    if flavour in ("strips", "options"):
+        backlog = ["pattern_dirty", "pattern_ready", "probe_window", "probe_no_split"] + list(INPUT_PATTERNS)
+    elif flavour == "stars":            # (no masked pixels, no galaxies, no exact conditional: the star-only kernels' walk)
+        backlog = ["pattern_dirty", "pattern_ready", "pattern_tail_split"]
+    OPT = {"opt_incremental": "inc", "opt_split_reuse": "reuse", "opt_honour_mask": "honour", "opt_split_full_box": "full", "opt_kernel": "variant",
+           "opt_tile_parts": "parts", "opt_star_tiles": "star"}
+    samplers = SAMPLERS if flavour != "stars" else ("flux", "slice_locations")
 
     def emit(name, **kw):
         expect = kw.pop("expect", None) or st.refusal(name)
         op = dict(op=name, seed=rnd.randrange(1, 1 << 30), expect=expect, **kw)
+        if mark:
+            op["pattern"] = mark.pop()
         if name == "mass":          # (would the short cut be taken: the split's sums of this very catalogue, and the options still say so)
-            op["ready"] = bool(st.split and st.split["sums"] and not st.split["dirty"] and st.reuse == 2 and not st.full)
+            op["ready"] = bool(st.split and st.split["sums"] and not st.split["dirty"] and st.reuse == 2 and not st.full and st.split["tail"] == st.tail[1])
         out.append(op)
         if name in count:
             count[name] += 1
@@ -98,18 +175,35 @@ def ops(seed, steps, flavour):
                 if st.split:
                     st.split["dirty"] = True
             if name in ("split_traced", "split_cold"):
-                st.split = dict(full=bool(st.full), dirty=False, sums=name == "split_traced" and st.reuse == 2 and not st.full and st.nelec != 2)
+                st.split = dict(full=bool(st.full), dirty=False, sums=name == "split_traced" and st.reuse == 2 and not st.full and st.nelec != 2,
+                                tail=st.tail[1])
             elif name == "set_nelec":
                 st.nelec, st.split = kw["kind"], None
-            elif name.startswith("opt_"):
-                setattr(st, {"opt_incremental": "inc", "opt_split_reuse": "reuse", "opt_honour_mask": "honour", "opt_split_full_box": "full"}[name], kw["value"])
-            elif name == "window_on":
-                st.window = True
-            elif name == "window_off":
-                st.window = False
-                if st.split:
-                    st.split["dirty"] = True
+            elif name == "opt_tail":
+                st.tail = tail_of(st.tail, kw["value"])
+            elif name in OPT:
+                setattr(st, OPT[name], kw["value"])
+            elif name == "window_to" and kw["window"] != st.window:      # (the window it has drops nothing)
+                st.window, st.split = kw["window"], None                # a new window leaves no resident split
+            elif name == "noise_rows":
+                st.noise = kw["rows"]
         return op
+
+    used = {}
+
+    def pick(name, values):
+        """one of `values`, the least used so far first: every value of an input comes up in a walk"""
+        values = list(values)
+        least = min(used.get((name, v), 0) for v in values)
+        v = rnd.choice([v for v in values if used.get((name, v), 0) == least])
+        used[(name, v)] = least + 1
+        return v
+
+    def begin(pattern):
+        """the first operation of a named pattern carries its name (coverage counts them)"""
+        mark.append(pattern)
+
+    mark = []
 
     def split(kind=None):
         kind = kind or rnd.choice(("split_traced", "split_cold"))
@@ -134,9 +228,18 @@ def ops(seed, steps, flavour):
         elif not st.split:
             split()
 
+    def ready_options():
+        unmask()
+        if st.reuse != 2:
+            emit("opt_split_reuse", value=2)
+        if st.full:
+            emit("opt_split_full_box", value=0)
+
     def one(name):
         if name == "mass_end":              # (never without its _begin)
             name = "mass_begin"
+        if st.variant == 0 and name not in DIRECT_OK:
+            emit("opt_kernel", value=1)
         if name in SAMPLERS or name in EXACT or name in ("pll", "pll_isolated"):
             if name in EXACT or rnd.random() < 0.8:          # (the exact conditional is asked for only where it is defined)
                 acceptable(name)
@@ -150,29 +253,109 @@ def ops(seed, steps, flavour):
             emit("mass_end")
         elif name == "set_nelec":
             emit("set_nelec", kind=rnd.choice((0, 1, 2)))
-        elif name.startswith("opt_"):
+        elif name in OPTIONS:
             was = {"opt_incremental": st.inc, "opt_split_reuse": st.reuse, "opt_honour_mask": st.honour, "opt_split_full_box": st.full}[name]
             emit(name, value=(2 - was) if name == "opt_split_reuse" else (1 - was))
+        elif name == "window_to":           # (one time in six the window it has: the no-op, which keeps a resident split)
+            emit("window_to", window=st.window if rnd.random() < 1 / 6. else pick(name, [x for x in WINDOWS if x != st.window]))
+        elif name == "noise_rows":
+            emit("noise_rows", rows=pick(name, NOISE_ROWS))
+        elif name == "opt_tail":            # (half the time back to the shipping thresholds: the dirty-tile render and the short cut need two calls at one)
+            emit("opt_tail", value="default" if st.tail != (24.0, 32.0) and rnd.random() < 0.5 else pick(name, TAILS))
+        elif name == "opt_kernel":          # the direct kernels for a few deterministic readers (its render vouches for no image) ...
+            if st.variant:
+                emit("opt_kernel", value=0)
+                emit("render", loglik=True)
+                emit(rnd.choice(("set_rows_1", "set_rows_3")))
+                emit(rnd.choice(("render", "render_noll")))
+            else:                           # ... and back (the next call of anything else brings the recurrence back as well)
+                emit("opt_kernel", value=1)
+        elif name == "opt_tile_order":
+            emit(name, value=pick(name, (0, 1, 2)))
+        elif name == "opt_tile_parts":      # (the dirty-tile render is the one-block-per-tile kernel's: 1 as often as the rest together)
+            emit(name, value=1 if st.parts != 1 and rnd.random() < 0.5 else pick(name, (0, 1, 2, 4)))
+        elif name == "opt_slice_fuse":
+            emit(name, value=pick(name, (0, 2)))
+        elif name == "opt_star_tiles":
+            emit(name, value=pick(name, (0, 1, 2)))
+        elif name == "hand_out":
+            # from the hand-out on this set keeps no Poisson partials: its log-likelihood renders every tile.  So it comes in the
+            # walk's second half, behind one of each pattern that ends in a dirty-tile render with a log-likelihood
+            if len(out) < steps // 2:
+                return
+            for p in ("pattern_dirty", "pattern_rows_dirty", "pattern_kernel_dirty"):
+                if p in backlog:
+                    backlog.remove(p)
+                    one(p)
+            emit("hand_out")
+        elif name == "pattern_tail_split":  # a model image of one threshold, the split's totals at another: "cold", like a new sky level
+            unmask()
+            begin(name)
+            emit("render", loglik=True)
+            emit("opt_tail", value=rnd.choice([t for t in ("default", "strict", "fast", "all8") if tail_of(st.tail, t)[0] != st.tail[0]]))
+            emit("split_cold")
+            emit("mass")
+        elif name == "pattern_tail_mass":   # the split's stamp sums of one per-source threshold, the masses at another
+            ready_options()
+            begin(name)
+            split("split_traced")
+            emit("mass")
+            emit("opt_tail", value="source8" if st.tail[1] != 8.0 else "default")
+            emit("mass")
+            emit("mass_begin")
+            emit("mass_end")
+        elif name == "pattern_window_split":    # a resident split, another window: every reader of the split refuses, then a new split serves
+            s = rnd.choice(SAMPLERS)
+            acceptable(s)
+            begin(name)
+            emit("window_to", window=rnd.choice([w for w in WINDOWS if w != st.window]))
+            emit(s)
+            emit("mass")
+            acceptable(s)
+            emit(s)
+        elif name == "pattern_rows_dirty":  # other owned rows under the per-tile partials: the dirty-tile render adds the new rows' tiles
+            if not st.inc:
+                emit("opt_incremental", value=1)
+            if st.parts != 1:
+                emit("opt_tile_parts", value=1)
+            begin(name)
+            emit("render", loglik=True)
+            emit("noise_rows", rows=rnd.choice([r for r in NOISE_ROWS if r != st.noise]))
+            emit(rnd.choice(("set_rows_1", "set_rows_3")))
+            emit("render", loglik=True)
+        elif name == "pattern_kernel_dirty":    # a render under one variant, then the other, then one changed row
+            if not st.inc:
+                emit("opt_incremental", value=1)
+            if st.parts != 1:
+                emit("opt_tile_parts", value=1)
+            begin(name)
+            emit("render", loglik=True)
+            emit("opt_kernel", value=0)
+            emit("set_rows_1")
+            emit("render", loglik=True)
+            emit("opt_kernel", value=1)
+            emit("set_rows_1")
+            emit("render", loglik=True)
         elif name == "render":
             emit("render", loglik=True)
         elif name == "pattern_dirty":       # device sampler -> full render -> set_rows -> render: the dirty-tile path, if it is legal
             if not st.inc:
                 emit("opt_incremental", value=1)
-            s = rnd.choice(SAMPLERS)
+            if st.parts != 1:
+                emit("opt_tile_parts", value=1)
+            if flavour == "stars" and st.star != 0:     # (neither star-only kernel leaves a base for the dirty-tile render)
+                emit("opt_star_tiles", value=0)
+            s = rnd.choice(samplers)
             acceptable(s)
             emit(s)
             emit("render", loglik=True)
             emit(rnd.choice(("set_rows_1", "set_rows_3")))
             emit("render", loglik=True)
         elif name == "pattern_ready":       # the mass short cut right behind a traced split ...
-            unmask()
-            if st.reuse != 2:
-                emit("opt_split_reuse", value=2)
-            if st.full:
-                emit("opt_split_full_box", value=0)
+            ready_options()
             split("split_traced")
             emit("mass")
-            emit(rnd.choice(SAMPLERS))      # ... and not behind a sampler's rewrite
+            emit(rnd.choice(samplers))      # ... and not behind a sampler's rewrite
             emit("mass")
         elif name == "pattern_end_rebuilt":
             s = rnd.choice(SAMPLERS)
@@ -205,14 +388,14 @@ def ops(seed, steps, flavour):
             emit(rnd.choice(SAMPLERS[1:] + ("pll_isolated",)))
         elif name == "probe_window":
             acceptable("exact_slice0")
-            emit("window_on")
+            emit("window_to", window=WINDOWS[1])
             emit(rnd.choice(EXACT))
-            emit("window_off")
+            emit("window_to", window=WINDOWS[0])
         else:
             emit(name)
 
     while len(out) < steps:
-        short = [k for k in OPERATIONS if count[k] < NEED]
+        short = [k for k in count if count[k] < NEED]
         left = steps - len(out)
         owed = 6 * len(backlog) + 2 * sum(NEED - count[k] for k in short)       # (roughly the steps still owed to the coverage)
         forced = rnd.random() < max(0.15, owed / float(left))
@@ -225,12 +408,14 @@ def ops(seed, steps, flavour):
     return out
 
 
-def coverage(seq):
-    """what a sequence of ops() holds: counts per operation, per expected refusal, per named pattern; and whether every mass_end
-    has its mass_begin"""
-    count = dict.fromkeys(OPERATIONS, 0)
+def coverage(seq, flavour="gibbs"):
+    """what a sequence of ops() holds: counts per operation the flavour owes, per expected refusal, per named pattern; and whether
+    every mass_end has its mass_begin"""
+    count = dict.fromkeys(required(flavour), 0)
     refused = dict.fromkeys(REFUSALS, 0)
     pat = dict(dirty=0, ready=0, not_ready=0, end_rebuilt=0, eps_render=0, eps_split=0)
+    if flavour in ("strips", "options"):
+        pat = dict(dict.fromkeys(INPUT_PATTERNS, 0), dirty=0, ready=0, not_ready=0)
     pending, paired, stage = False, True, 0
     for i, op in enumerate(seq):
         n = op["op"]
@@ -238,17 +423,20 @@ def coverage(seq):
             count[n] += 1
         if op["expect"]:
             refused[op["expect"]] += 1
+        if op.get("pattern") in pat:
+            pat[op["pattern"]] += 1
         if n == "mass_begin":
             pending = True
         elif n == "mass_end":
             paired, pending = paired and pending, False
-            pat["end_rebuilt"] += op["expect"] == "end_rebuilt"
+            if "end_rebuilt" in pat:
+                pat["end_rebuilt"] += op["expect"] == "end_rebuilt"
         elif n == "mass":
             pat["ready" if op["ready"] else "not_ready"] += 1
         last = [o["op"] for o in seq[max(i - 3, 0):i]]
-        if n == "render_noll" and last[-3:-1] == ["render", "set_epsilon"] and last[-1] in SET_ROWS[:3]:
+        if n == "render_noll" and last[-3:-1] == ["render", "set_epsilon"] and last[-1] in SET_ROWS[:3] and "eps_render" in pat:
             pat["eps_render"] += 1
-        if n == "split_cold" and last[-2:] == ["render", "set_epsilon"]:
+        if n == "split_cold" and last[-2:] == ["render", "set_epsilon"] and "eps_split" in pat:
             pat["eps_split"] += 1
         # device sampler -> render -> set_rows -> render
         ok = not op["expect"]
@@ -325,25 +513,28 @@ class Mismatch(AssertionError):
 
 
 class Walker(object):
-    def __init__(self, cel, stars_only=False):
+    def __init__(self, cel, stars_only=False, required=OPERATIONS):
         import numpy as np
         self.np, self.cel, self.L = np, cel, cel._lib
         sc = scene(cel, stars_only)
         self.sc, self.n = sc, sc["n"]
         self.ctx = cel.Context(0)
         self.ctx.set_option(self.L.CEL_OPT_TILE_PARTS, 1)           # (the dirty-tile path is the one-wave-per-tile kernel's)
-        self.keys = dict(inc=self.L.CEL_OPT_INCREMENTAL, reuse=self.L.CEL_OPT_SPLIT_REUSE, honour=self.L.CEL_OPT_HONOUR_MASK,
-                         full=self.L.CEL_OPT_SPLIT_FULL_BOX, lists=self.L.CEL_OPT_PHOTON_LISTS)
+        L = self.L
+        self.keys = dict(inc=L.CEL_OPT_INCREMENTAL, reuse=L.CEL_OPT_SPLIT_REUSE, honour=L.CEL_OPT_HONOUR_MASK, full=L.CEL_OPT_SPLIT_FULL_BOX,
+                         lists=L.CEL_OPT_PHOTON_LISTS, render_T=L.CEL_OPT_TAIL_LOG, tail_T=L.CEL_OPT_TAIL_LOG_SOURCE, variant=L.CEL_OPT_KERNEL,
+                         parts=L.CEL_OPT_TILE_PARTS, star=L.CEL_OPT_STAR_TILES, order=L.CEL_OPT_TILE_ORDER, fuse=L.CEL_OPT_SLICE_FUSE)
         self.opt = {k: self.ctx.get_option(v) for k, v in self.keys.items()}
+        self.noise = NOISE_ROWS[0]
         self.cur = [np.array(a, copy=True) for a in sc["cat"]]
         self.eps = sc["bands"][:, 0].copy()
         self.kind = 0
         self.im = cel.ImageSet(self.ctx, sc["bands"], H, W, nelec=sc["nelec"][0])
         self.ss = cel.SourceSet(self.ctx, self.n, B).set(*self.cur)
         self.split = None               # dict(cat, seed, traced, opt, eps, dirty) of the live pair's resident split
-        self.window = False
+        self.window = WINDOWS[0]
         self.log = []
-        self.count = dict.fromkeys(OPERATIONS, 0)
+        self.count = dict.fromkeys(required, 0)
         self.refused = dict.fromkeys(REFUSALS, 0)
         self.seen = dict(ready1=0, ready0=0, dirty_after_pattern=0, dirty=0, full=0, sampler_ok=0)
         self.stage = 0
@@ -355,23 +546,41 @@ class Walker(object):
         b[:, 0] = eps
         return b
 
-    def fresh(self, cat, eps=None):
-        im = self.cel.ImageSet(self.ctx, self.bands(self.eps if eps is None else eps), H, W, nelec=self.sc["nelec"][self.kind])
+    def fresh(self, cat, eps=None, pixels=None):
+        """a pair without memory: today's window and owned rows FIRST, before any call"""
+        im = self.cel.ImageSet(self.ctx, self.bands(self.eps if eps is None else eps), H, W, nelec=self.sc["nelec"][self.kind] if pixels is None else pixels)
+        if self.window != WINDOWS[0]:
+            im.set_window(*self.window)
+        if self.noise != NOISE_ROWS[0]:
+            im.set_noise_rows(*self.noise)
         return im, self.cel.SourceSet(self.ctx, self.n, B).set(*cat)
 
     def options(self, want):
         """set the options `want` now -> what they were"""
         was = dict(self.opt)
+        want = dict(want)
+        T = (want.pop("render_T", self.opt["render_T"]), want.pop("tail_T", self.opt["tail_T"]))
+        if T != (self.opt["render_T"], self.opt["tail_T"]):         # (CEL_OPT_TAIL_LOG sets both, CEL_OPT_TAIL_LOG_SOURCE the second)
+            self.ctx.set_option(self.keys["render_T"], T[0])
+            self.ctx.set_option(self.keys["tail_T"], T[1])
+            self.opt["render_T"], self.opt["tail_T"] = T
         for k, v in want.items():
             if self.opt[k] != v:
                 self.ctx.set_option(self.keys[k], v)
                 self.opt[k] = v
         return was
 
+    def time_options(self):
+        """what a resident split remembers of the options: everything that changes a bit of it -- thresholds, variant, and the
+        blocks per tile / the star-tile kernel of the render behind its totals (values "agree to rounding between settings",
+        include/celeste_hip.h) -- and not what never changes a result (tile order, slice fuse: the replay runs under today's)"""
+        return {k: v for k, v in self.opt.items() if k not in ("order", "fuse")}
+
     def with_split(self, eps=None):
         """a fresh pair brought to the live pair's state the documented way: the catalogue of the split, the options of the
-        split, the trace render if there was one, the split with its seed; then today's options, sky levels, catalogue (only if
-        it changed: an unchanged one keeps the mass short cut on both sides) and window"""
+        split, the trace render if there was one, the split with its seed; then today's options, sky levels and catalogue (only if
+        it changed: an unchanged one keeps the mass short cut on both sides).  Window and owned rows are today's from the start: a
+        split of another window does not exist (cel_images_set_window drops it)"""
         sp = self.split
         if sp is None:
             im, ss = self.fresh(self.cur, eps)
@@ -390,15 +599,14 @@ class Walker(object):
                     im.set_epsilon(b, eps[b])
             if sp["dirty"]:
                 ss.set(*self.cur)
-        if self.window:
-            im.set_window(32, H + 64)
         return im, ss
 
     # -- comparisons -------------------------------------------------------------------------------------------------------------
     def fail(self, what):
         raise Mismatch("step %d: %s\n   last operations: %s\n   options %s, pixels %d, split %s" % (
             len(self.log), what, self.log[-14:], self.opt, self.kind,
-            None if self.split is None else {k: self.split[k] for k in ("seed", "traced", "opt", "dirty")}))
+            None if self.split is None else {k: self.split[k] for k in ("seed", "traced", "opt", "dirty")})
+            + "\n   window %s, owned rows %s" % (self.window, self.noise))
 
     def same(self, what, a, b):
         """bit for bit (a NaN where a source was left alone equals a NaN)"""
@@ -549,7 +757,7 @@ class Walker(object):
             # (the generator put render(loglik=True) / a set_rows edit immediately before: both sides form the totals image by
             # the documented rule of CEL_OPT_SPLIT_REUSE)
             seed = op["seed"]
-            sp = dict(cat=[a.copy() for a in self.cur], seed=seed, traced=name == "split_traced", opt=dict(self.opt), eps=self.eps.copy(), dirty=False)
+            sp = dict(cat=[a.copy() for a in self.cur], seed=seed, traced=name == "split_traced", opt=self.time_options(), eps=self.eps.copy(), dirty=False)
 
             def values(im, noise):
                 return dict(noise=noise, sums=im.sample_sums(), samples=im.fetch_samples(), rects=im.photon_rects(), rates=im.split_rates(),
@@ -573,7 +781,7 @@ class Walker(object):
             self.seen["ready1" if ready else "ready0"] += 1
             a = self.both("mass", None, lambda: (self.im.stamp_mass_ready(self.ss), self.im.stamp_mass(self.ss)),
                           lambda im, ss: (im.stamp_mass_ready(ss), im.stamp_mass(ss)))
-            self.third_mass("mass", a[1][1])
+            self.third_mass("mass", a[1][1], exact=not ready)
             note = "mass(ready=%d)" % ready
         elif name == "mass_begin":
             self.im.stamp_mass_begin(self.ss)
@@ -637,7 +845,15 @@ class Walker(object):
             rim.close()
         elif name == "grad":
             rim, rss = self.fresh(self.cur)
-            self.same("loglik_grad", self.im.loglik_grad(self.ss), rim.loglik_grad(rss))
+            a, b = self.outcome(lambda: self.im.loglik_grad(self.ss)), self.outcome(lambda: rim.loglik_grad(rss))
+            if expect:
+                if not (a[0] == "error" and a[1] == "ValueError" and "row window" in a[2]) or b[:2] != ("error", "ValueError"):
+                    self.fail("grad must be refused (%s): live %r, replay %r" % (expect, a[:3] if a[0] == "error" else "accepted", b[:3] if b[0] == "error" else "accepted"))
+                self.refused[expect] += 1
+            else:
+                if a[0] != "ok" or b[0] != "ok":
+                    self.fail("loglik_grad: live %r, replay %r" % (a[:3], b[:3]))
+                self.same("loglik_grad", a[1], b[1])
             rim.close()
         elif name == "set_epsilon":
             b = int(rs.randint(B))
@@ -650,30 +866,72 @@ class Walker(object):
             self.same("cel_samples_info behind set_nelec", self.samples_info(self.im), (0, 0))
             self.same("stamp_mass_ready behind set_nelec", self.im.stamp_mass_ready(self.ss), False)
             note = "set_nelec(%d)" % self.kind
+        elif name == "opt_tail":
+            T = tail_of((self.opt["render_T"], self.opt["tail_T"]), op["value"])
+            if op["value"] in ("default", "strict", "fast"):    # (the presets go the way a caller's do)
+                self.ctx.set_tail_log(op["value"])
+                self.opt["render_T"], self.opt["tail_T"] = T
+            else:
+                self.options(dict(render_T=T[0], tail_T=T[1]))
+            self.same("the thresholds behind opt_tail", (self.ctx.get_option(self.keys["render_T"]), self.ctx.get_option(self.keys["tail_T"])), T)
+            note = "opt_tail=%s" % op["value"]
         elif name.startswith("opt_"):
-            self.options({{"opt_incremental": "inc", "opt_split_reuse": "reuse", "opt_honour_mask": "honour", "opt_split_full_box": "full"}[name]: float(op["value"])})
+            key = {"opt_incremental": "inc", "opt_split_reuse": "reuse", "opt_honour_mask": "honour", "opt_split_full_box": "full", "opt_kernel": "variant",
+                   "opt_tile_order": "order", "opt_tile_parts": "parts", "opt_slice_fuse": "fuse", "opt_star_tiles": "star"}[name]
+            self.options({key: float(op["value"])})
             note = "%s=%d" % (name, op["value"])
-        elif name == "window_on":
-            self.im.set_window(32, H + 64)
-            self.window = True
-        elif name == "window_off":
-            self.im.set_window(0, H)
-            self.window = False
-            self.touched()                                      # (the window dropped the stamp sums: a replay that sets the catalogue again has none either)
+        elif name == "window_to":
+            window = tuple(op["window"])
+            info = self.samples_info(self.im)
+            self.im.set_window(*window)
+            if window != self.window:                           # a new window drops the resident split (include/celeste_hip.h) ...
+                self.window, self.split = window, None
+                self.same("cel_samples_info behind a new window", self.samples_info(self.im), (0, 0))
+                self.same("stamp_mass_ready behind a new window", self.im.stamp_mass_ready(self.ss), False)
+            else:                                               # ... the window it has drops nothing
+                self.same("cel_samples_info behind the same window", self.samples_info(self.im), info)
+            note = "window_to%s" % (window,)
+        elif name == "noise_rows":
+            self.noise = tuple(op["rows"])
+            self.im.set_noise_rows(*self.noise)
+            note = "noise_rows%s" % (self.noise,)
+        elif name == "hand_out":
+            # the observed pixels' address, and the SAME pixels written through it: the numbers stay comparable, and the library
+            # has to treat the pixels as the caller's from now on (a resident split stays the split of the pixels it was drawn from)
+            self.write_pixels(self.sc["nelec"][self.kind])
         else:
             raise KeyError(name)
         if name in self.count:
             self.count[name] += 1
         self.log[-1] = note + ("!" + expect if expect else "")
 
-    def third_mass(self, what, got):
+    def write_pixels(self, pixels):
+        """cel_images_device_ptrs for the observed pixels, and `pixels` copied to that address"""
+        import ctypes as C
+        np = self.np
+        pixels = np.ascontiguousarray(pixels, dtype=np.float64)
+        assert pixels.shape == (B, H, W)                        # (the device buffer's size: nothing is written past it)
+        hip = C.CDLL(self.L.LIB_PATH)                           # (dlsym through the library finds the HIP runtime IT is linked to)
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        self.ctx.synchronize()
+        if hip.hipMemcpy(self.im.device_ptrs()[0], pixels.ctypes.data, pixels.nbytes, 1) != 0:
+            raise RuntimeError("hipMemcpy to the observed pixels failed")
+
+    def third_mass(self, what, got, exact=False):
         """the mass kernel alone, on an object that never had a split: the short cut's bound (CEL_OPT_SPLIT_REUSE: 1.6e-10 at
-        the thresholds; tools/dbg/reuse_stress.py's rtol = 1e-9, atol = 1e-15)"""
+        the thresholds; tools/dbg/reuse_stress.py's rtol = 1e-9, atol = 1e-15).  That figure is the shipping per-source threshold's,
+        T = 32: the sums carry the SPLIT's drop rule (per tile), the mass kernel drops per source, and either leaves out terms
+        below eps e^-T -- under a coarser threshold the ceiling of every such term, and with it the bound, is e^(32 - T) times
+        higher (measured at T = 20: 8.9e-8 against 1.6e-4).  exact: the live pair did not take the short cut either, so the two
+        are the same kernel on the same records -- bit for bit"""
         np = self.np
         im, ss = self.fresh(self.cur)
         want = im.stamp_mass(ss)
         im.close()
-        if not np.allclose(got, want, rtol=1e-9, atol=1e-15):
+        if exact:
+            self.same("%s by the mass kernel, against an object without a split" % what, got, want)
+        rtol = 1e-9 * max(1.0, float(np.exp(32.0 - self.opt["tail_T"])))
+        if not np.allclose(got, want, rtol=rtol, atol=1e-15):
             i = np.unravel_index(int(np.argmax(np.abs(got - want) / np.maximum(np.abs(want), 1e-300))), want.shape)
             self.fail("%s off the mass kernel's values: source %d band %d %r against %r (type %d, counts %r, shape %r)"
                       % (what, i[0], i[1], got[i], want[i], self.cur[0][i[0]], self.cur[2][i[0]].tolist(), self.cur[3][i[0]].tolist()))

@@ -14,7 +14,7 @@ static int failures = 0;
     } while (0)
 
 static const int64_t S = 4;
-static const double T = 24.0;
+static const double T = 24.0, TS = 32.0;     // the field render's drop threshold and the per-source kernels'
 static const int todo_list[1] = {0};
 static double mass_values[8];
 
@@ -39,7 +39,7 @@ static World vouched() {
     f.split_begins(true);
     f.split_laid_out(S, 100, true);
     f.split_totals_from_model(false);
-    f.split_ends(true, w.now.gen);
+    f.split_ends(true, w.now.gen, TS);
     f.split_lists_built();
     f.mass.begin(w.now.gen, f.split.split_epoch, S * 2, S, todo_list, mass_values);
     w.was = w.now;
@@ -61,14 +61,14 @@ static std::string held(const World &w) {
     if (f.lists.costs_of(S)) s += 'c';
     if (f.model.lambda_gen == w.was.gen) s += 'm';
     if (f.model.partials_gen == w.was.gen) s += 'p';
-    if (f.model_current(w.was)) s += 't';
+    if (f.model_current(w.was, T)) s += 't';
     if (f.incremental_base(w.now, S, T, true)) s += 'i';
     if (f.incremental_base(w.now, S, T, false)) s += 'j';
     if (f.split.resident_of(S)) s += 's';
     if (f.split.ssum_valid) s += 'u';
     if (f.split.hsum_valid) s += 'h';
     if (f.split.nz_valid) s += 'z';
-    if (f.split.sums_of(w.was)) s += 'x';
+    if (f.split.sums_of(w.was, TS)) s += 'x';
     if (f.mass.pending >= 0 && f.mass.intact(f.rec, f.split)) s += 'q';
     if (f.nelec_u16) s += '6';
     return s;
@@ -128,7 +128,7 @@ int main() {
     AFTER(new_pixels(), "rblocmtjq");
     AFTER(pixels_handed_out(), "rblocmtjsuhzxq");
     AFTER(new_sky_level(), "rblocsuhzxq6");
-    AFTER(new_window(), "ocpsuhz6");
+    AFTER(new_window(), "ocp6");                                    // (the resident split's patches are boxes of the old window)
     AFTER(records_regrown(), "locmpsuhzx6");
     AFTER(records_written(0, S), "locmpsuhzx6");                    // a partial table, or one without boxes
     AFTER(records_written(w.was.gen, S), "rblocmptijsuhzxq6");      // the same catalogue again
@@ -147,7 +147,7 @@ int main() {
     AFTER(split_laid_out(S, 90, true), "rblocmptijsuxq6");
     AFTER(split_laid_out(S, 90, false), "rblocmptijsxq6");
     AFTER(split_laid_out(S + 1, 90, true), "rblocmptijuxq6");
-    AFTER(split_ends(false, 0), "rblocmptijsuhzxq6");
+    AFTER(split_ends(false, 0, 8.0), "rblocmptijsuhzxq6");          // (no stamp sums made: those that lie there keep their threshold)
     {   // a render of the catalogue as it is now: what it vouches for depends on what it did
         World w = vouched();
         w.f.render_begins(true, true);
@@ -185,7 +185,7 @@ int main() {
         w.f.split_begins(true);
         w.f.split_laid_out(S, 80, true);
         CHECK(held(w) == "rblocmptijsu6");
-        w.f.split_ends(true, w.was.gen);
+        w.f.split_ends(true, w.was.gen, TS);
         CHECK(held(w) == "rblocmptijsuhx6");
         w.f.split_lists_built();
         CHECK(held(w) == "rblocmptijsuhzx6");
@@ -199,6 +199,23 @@ int main() {
         w.f.mass.begin(w.was.gen, w.f.split.split_epoch, 8, -1, nullptr, mass_values);
         w.f.mass.cancel();
         CHECK(!w.f.mass.take(&n, &todo));
+    }
+    {   // the thresholds the products were made at: a reader at another one is not served
+        World w = vouched();
+        CHECK(w.f.model_current(w.was, T) && !w.f.model_current(w.was, TS) && !w.f.model_current(w.was, 8.0));   // the split's totals
+        CHECK(w.f.split.sums_of(w.was, TS) && !w.f.split.sums_of(w.was, T) && !w.f.split.sums_of(w.was, 8.0));   // the mass short cut
+        CHECK(!w.f.split.sums_of(w.now, TS));                              // (and never another generation's)
+        w.f.split_begins(true);
+        w.f.split_laid_out(S, 100, true);
+        w.f.split_ends(true, w.was.gen, 8.0);                              // a split under a coarse per-source threshold ...
+        CHECK(w.f.split.sums_of(w.was, 8.0) && !w.f.split.sums_of(w.was, TS));     // ... vouches for masses at that one alone
+        CHECK(w.f.model_current(w.was, T));                                // (the field render's threshold is not the split's business)
+    }
+    {   // a new window behind a pending cel_stamp_mass_begin: the records it summed are nobody's, _end refuses
+        World w = vouched();
+        w.f.new_window();
+        CHECK(w.f.mass.pending >= 0 && !w.f.mass.intact(w.f.rec, w.f.split));
+        CHECK(w.f.split.samp_S == 0 && w.f.split.samp_total == 0 && !w.f.split.resident_of(S));
     }
     if (failures) { fprintf(stderr, "%d checks failed\n", failures); return 1; }
     puts("field_state: ok");

@@ -24,11 +24,33 @@ cel_stamp_mass_end without its check -- while test_stress.py, test_hip_parity.py
 fifth of them (the table is in the message of the change that added this file).
 
 The stamps' only writers are the events of csrc/field_state.h (DESIGN.md section 4b names, per event and product, the test that
-would notice its loss); the two the walk cannot reach -- a new window under cached products (in the walk the window only frames a
-refusal) and the observed pixels' address handed out -- are scripted in test_named_transitions (8., 9.).
+would notice its loss).
 
-Timings, measured on the MI355X: a walk of 250 steps takes 0.5 - 1.6 s (the first of a session 3.2 s with the library's load and
-the scene's draw), test_named_transitions 0.3 - 0.4 s, the whole file 4.5 s.
+The inputs every cached product depends on are walked as well ("strips", "options" and the stars_only scene's "stars"; the replay
+rule is in tests/_state_walk.py): the row window (window_to), the owned rows (noise_rows), the context options that change
+results (opt_tail: both thresholds; opt_kernel) and those that must not (opt_tile_order, opt_tile_parts, opt_slice_fuse,
+opt_star_tiles), and the observed pixels' address handed out with the same pixels written back through it (hand_out).  What was
+decided with them, fixed in the same change and scripted in test_named_transitions (10. - 15.):
+  * a new window left the resident split of the OLD window's boxes in place (cel_slice_locations scored new records against old
+    patches): cel_images_set_window with another window now drops the split, the window it already has drops nothing (10.);
+  * the split took its totals from the model image on the device whatever threshold that image was rendered at: model_current
+    now asks (11.);
+  * the stamp-mass short cut read the split's stamp sums whatever per-source threshold they were formed at (6.9e-2 off at
+    T = 8 against the default): sums_of now asks (12.);
+  * CEL_OPT_KERNEL needs no stamp (13.), cel_images_set_noise_rows drops nothing (14.), cel_images_device_ptrs keeps the split (15.).
+Found by the new walks' first run, in the TEST: the short cut's bound of 1e-9 is the shipping per-source threshold's; under a
+coarser one it scales with the dropped terms' ceiling (Walker.third_mass).  No mismatch of the library's beyond the decided cases.
+
+That these can fail: libraries with ONE comparison removed each -- model_current without the threshold: 11. (the split's noise
+sums, 834 727 against 834 749 photons) and the walks strips/1, options/1 and stars/1 (pattern_tail_split: totals 1e-8 off);
+sums_of without it: 12. (stamp_mass_ready stays 1).  The window's fix is shown on the CPU alone (tests/host/field_state_events.cpp:
+without the drop, the new_window row and the pending-mass block fail): a library without it would score against patches of
+another window.
+
+Timings, measured on the MI355X: a walk of 250 steps takes 0.5 - 1.5 s for "gibbs" and "edits" (the first of a session more, with
+the library's load and the scene's draw), 0.3 - 0.4 s for "strips" and "options" (below the earlier walks' range, not above it: fewer of
+their steps are device samplers), 0.15 s for "stars" (12 sources); test_named_transitions 0.6 s (0.3 s
+before 10. - 15.); the whole file 5.5 s (4.4 s before).
 """
 import numpy as np
 import pytest
@@ -38,7 +60,8 @@ import _state_walk as sw
 gpu = pytest.mark.gpu
 #: the walks: (seed, flavour), and their length (0.5 - 1.6 s per walk on the MI355X: no need to halve it)
 STEPS = 250
-WALKS = [(1, "gibbs"), (2, "gibbs"), (1, "edits"), (2, "edits")]
+WALKS = [(1, "gibbs"), (2, "gibbs"), (1, "edits"), (2, "edits"), (1, "strips"), (1, "options")]
+STAR_WALKS = [(1, "stars")]             # the stars_only scene (12 stars): CEL_OPT_STAR_TILES and the star-only kernels
 
 
 @pytest.fixture(scope="module")
@@ -51,19 +74,39 @@ def test_generator_meets_its_coverage():
     """ops() alone, for the seeds and step counts the GPU walks use: every operation at least 3 times, every named pattern and
     every documented refusal at least once, no _end without its _begin, and the same sequence for the same seed -- the walks'
     coverage assertions are met by construction"""
-    for seed, flavour in WALKS:
+    for seed, flavour in WALKS + STAR_WALKS:
         seq = sw.ops(seed, STEPS, flavour)
         assert STEPS <= len(seq) < STEPS + 12
         assert seq == sw.ops(seed, STEPS, flavour)
-        count, refused, pat, paired = sw.coverage(seq)
+        count, refused, pat, paired = sw.coverage(seq, flavour)
         assert paired
+        assert set(count) == set(sw.required(flavour))
         assert min(count.values()) >= 3, {k: v for k, v in count.items() if v < 3}
-        assert min(refused.values()) >= 1, refused
-        assert min(pat.values()) >= 1, pat
-        assert all(op["op"] in sw.OPERATIONS or op["op"] in ("window_on", "window_off") for op in seq)
+        if flavour in ("gibbs", "edits"):
+            assert min(refused.values()) >= 1, refused
+            assert min(pat.values()) >= 1, pat
+        elif flavour != "stars":            # (the inputs' walks owe the refusals that an input causes; no masked pixels, no window on the stars' walk)
+            assert refused["window"] >= 1 and refused["no_split"] >= 2, refused
+            assert min(pat.values()) >= 1, pat
+        assert all(op["op"] in sw.OPERATIONS + ("opt_star_tiles",) for op in seq)
+        if flavour in ("strips", "options"):
+            # strips: every window and every choice of owned rows; options: every threshold, both variants, every value of the result-preserving options
+            seen = lambda name, key: set(tuple(op[key]) if isinstance(op[key], (tuple, list)) else op[key] for op in seq if op["op"] == name)
+            if flavour == "strips":
+                assert seen("window_to", "window") == set(sw.WINDOWS) and seen("noise_rows", "rows") == set(sw.NOISE_ROWS)
+            else:
+                assert seen("opt_tail", "value") == set(sw.TAILS) and seen("opt_kernel", "value") == {0, 1}
+                assert seen("opt_tile_parts", "value") == {0, 1, 2, 4} and seen("opt_slice_fuse", "value") == {0, 2} and seen("opt_tile_order", "value") == {0, 1, 2}
+        if flavour == "stars":
+            assert set(op["value"] for op in seq if op["op"] == "opt_star_tiles") == {0, 1, 2}
     a, b = sw.ops(1, STEPS, "gibbs"), sw.ops(1, STEPS, "edits")
     heavy = lambda seq: sum(op["op"] in sw.SAMPLERS + sw.EXACT for op in seq) / float(sum(op["op"] in sw.SET_ROWS + ("render", "render_noll") for op in seq))
     assert heavy(a) > 2 * heavy(b)                              # (the flavours are different walks)
+    share = lambda seq, names: sum(op["op"] in names for op in seq) / float(len(seq))
+    c, d = sw.ops(1, STEPS, "strips"), sw.ops(1, STEPS, "options")
+    assert share(c, ("window_to", "noise_rows")) > 2 * share(d, ("window_to", "noise_rows"))
+    assert share(d, ("opt_tail", "opt_kernel", "opt_tile_order", "opt_tile_parts", "opt_slice_fuse")) > \
+        1.5 * share(c, ("opt_tail", "opt_kernel", "opt_tile_order", "opt_tile_parts", "opt_slice_fuse"))        # (both owe three of each)
 
 
 @gpu
@@ -71,7 +114,7 @@ def test_generator_meets_its_coverage():
 def test_walk(cel, seed, flavour):
     """STEPS random operations on one live pair, every returned number equal to the replay's; then the coverage, counted on the
     live pair: conditions, not measurements"""
-    w = sw.Walker(cel)
+    w = sw.Walker(cel, required=sw.required(flavour))
     try:
         w.walk(sw.ops(seed, STEPS, flavour))
     finally:
@@ -79,7 +122,23 @@ def test_walk(cel, seed, flavour):
     assert w.seen["dirty_after_pattern"] >= 1, (w.seen, "no dirty-tile render behind device sampler -> full render -> set_rows")
     assert w.seen["ready1"] >= 1 and w.seen["ready0"] >= 1, w.seen
     assert min(w.count.values()) >= 3, {k: v for k, v in w.count.items() if v < 3}
-    assert min(w.refused.values()) >= 1, w.refused
+    assert min(w.refused[k] for k in (sw.REFUSALS if flavour in ("gibbs", "edits") else ("window", "no_split"))) >= 1, w.refused
+    w.close()
+
+
+@gpu
+@pytest.mark.parametrize("seed,flavour", STAR_WALKS)
+def test_walk_stars(cel, seed, flavour):
+    """the same on the stars_only scene: a catalogue without galaxies stays one (no type move, no star <-> galaxy edit), so the
+    one-launch render of a small star field, the star-tile kernel and the general kernel take turns under CEL_OPT_STAR_TILES"""
+    w = sw.Walker(cel, stars_only=True, required=sw.required(flavour))
+    try:
+        w.walk(sw.ops(seed, STEPS, flavour))
+    finally:
+        print("walk %s/%d: %d operations; %s; refused %s" % (flavour, seed, len(w.log), w.seen, w.refused))
+    assert not np.any(w.cur[0])
+    assert w.seen["ready1"] >= 1 and w.seen["ready0"] >= 1 and w.seen["full"] >= 1 and w.seen["dirty"] >= 1, w.seen
+    assert min(w.count.values()) >= 3, {k: v for k, v in w.count.items() if v < 3}
     w.close()
 
 
@@ -187,7 +246,9 @@ def test_named_transitions(cel):
     with pytest.raises(ValueError, match="finite"):
         w.im.type_move(w.ss, np.tile([0.5, 1.0, 30.0, 0.5], (w.n, 1)), np.full(w.n, np.nan), 4)
     assert w.im.stamp_mass_ready(w.ss)
-    w.walk([_op("mass", 5), _op("window_on", 6), _op("exact_type_move", 7, expect="window"), _op("window_off", 8), _op("flux", 9)])
+    w.walk([_op("mass", 5), _op("window_to", 6, window=(32, sw.H + 64)), _op("exact_type_move", 7, expect="window"),
+            _op("window_to", 8, window=(0, sw.H)), _op("flux", 9, expect="no_split")])     # (the window took the split with it: 10.)
+    w.walk([_op("render", 9, loglik=True), _op("split_traced", 9), _op("flux", 9)])
     w.walk([_op("set_nelec", 10, kind=2), _op("opt_honour_mask", 11, value=1), _op("render", 12, loglik=True), _op("split_traced", 13), _op("flux", 14),
             _op("opt_honour_mask", 15, value=0), _op("flux", 16, expect="masked_unhonoured"), _op("split_cold", 17, expect="masked_unhonoured"),
             _op("slice_locations", 18, expect="masked_sampler"), _op("opt_honour_mask", 19, value=1), _op("flux", 20), _op("mass", 21)])
@@ -215,7 +276,7 @@ def test_named_transitions(cel):
     w.walk([_op("render", 1, loglik=True), _op("split_traced", 2), _op("mass", 3)])
     old = w.im.source_boxes(w.ss)
     assert w.im.stamp_mass_ready(w.ss)
-    w.run(_op("window_on", 4))
+    w.run(_op("window_to", 4, window=(32, sw.H + 64)))
     rim, rss = w.fresh(w.cur)
     rim.set_window(32, sw.H + 64)
     assert not w.im.stamp_mass_ready(w.ss)
@@ -247,4 +308,147 @@ def test_named_transitions(cel):
     rim = cel.ImageSet(w.ctx, w.bands(w.eps), sw.H, sw.W, nelec=pixels)
     w.same("render behind the caller's own pixels", out, rim.render(cel.SourceSet(w.ctx, w.n, sw.B).set(*w.cur), loglik=True))
     rim.close()
+    w.close()
+
+    # 10. a new window drops the resident split: its patches are boxes of the OLD window.  Every call that needs a split names
+    #     the missing one, a pending cel_stamp_mass_begin is refused like one behind a rebuilt catalogue, the catalogue is
+    #     untouched; then everything equals a fresh windowed pair.  The window it already has drops nothing
+    w = sw.Walker(cel)
+    win = (32, sw.H + 64)
+    w.walk([_op("render", 1, loglik=True), _op("split_traced", 2), _op("mass", 3)])
+    assert w.seen["ready1"] == 1 and w.samples_info(w.im)[0] == w.n
+    w.run(_op("mass_begin", 4))
+    w.run(_op("window_to", 5, window=win))
+    assert w.samples_info(w.im) == (0, 0) and not w.im.stamp_mass_ready(w.ss)
+    for name, call in calls.items():
+        with pytest.raises(ValueError, match="resident photon split"):
+            call()
+    with pytest.raises(ValueError, match="rebuilt since"):          # (mass.intact: the records _begin summed are nobody's)
+        w.im.stamp_mass_end()
+    w.same("catalogue behind a new window", w.ss.get(), tuple(w.cur))
+    w.walk([_op("render", 6, loglik=True), _op("split_traced", 7), _op("flux", 8), _op("slice_locations", 9), _op("mass", 10)])
+    info = w.samples_info(w.im)
+    assert info[0] == w.n
+    w.run(_op("window_to", 11, window=win))                         # the same window again: a no-op
+    assert w.samples_info(w.im) == info
+    w.walk([_op("flux", 12), _op("pll", 13), _op("window_to", 14, window=(0, sw.H)), _op("window_to", 15, window=(0, sw.H)),
+            _op("pll", 16, expect="no_split")])
+    w.close()
+
+    # 11. a model image of the coarse threshold, then the strict one, then the split: its totals, sums and draws are those of a
+    #     pair that never saw the coarse threshold.  With its image at another threshold the split is "cold" by the documented rule
+    #     (split_cold: bit for bit against a fresh strict pair's cold split); against a fresh strict pair's render + split the
+    #     totals are the same image under CEL_OPT_SPLIT_FULL_BOX (bit for bit) and agree to the 1e-10 the header gives for the
+    #     two forms of the strict totals otherwise (1e-9 asserted: tools/dbg/reuse_stress.py's figure)
+    for reuse, full in ((1, 0), (2, 0), (2, 1)):
+        w = sw.Walker(cel)
+        w.options(dict(reuse=float(reuse), full=float(full)))
+        w.walk([_op("opt_tail", 1, value="all8"), _op("render", 2, loglik=True)])
+        coarse = w.im.model_images()
+        w.walk([_op("opt_tail", 3, value="strict"), _op("split_cold", 4)])
+        rim, rss = w.fresh(w.cur)
+        rim.render(rss, loglik=True)
+        strict = rim.model_images()
+        rim.photon_split_resident(rss, 4)
+        gap = np.max(np.abs(w.im.split_rates() - rim.split_rates()) / rim.split_rates())
+        stale = np.max(np.abs(coarse - strict) / strict)
+        print("11. reuse %d full %d: totals against a strict render + split %.3e relative; the T = 8 image against the strict one %.3e" % (reuse, full, gap, stale))
+        if full:
+            w.same("totals, sums and draws behind a threshold change (full boxes)", (w.im.split_rates(), w.im.sample_sums(), w.im.fetch_samples()),
+                   (rim.split_rates(), rim.sample_sums(), rim.fetch_samples()))
+        assert gap <= 1e-9
+        assert stale > 1e-6                                         # (non-vacuity, on fresh values alone: the stale image is far off)
+        rim.close()
+        w.walk([_op("flux", 5), _op("mass", 6)])
+        w.close()
+
+    # 12. the split's stamp sums of one per-source threshold are not the masses of another: the short cut steps aside
+    w = sw.Walker(cel)
+    w.walk([_op("opt_tail", 1, value="source8"), _op("render", 2, loglik=True), _op("split_traced", 3)])
+    assert w.im.stamp_mass_ready(w.ss)
+    coarse = w.im.stamp_mass(w.ss)                                  # (the short cut, at T = 8)
+    w.options(dict(tail_T=32.0))                                    # the per-source threshold back to its default
+    assert not w.im.stamp_mass_ready(w.ss)
+    rim, rss = w.fresh(w.cur)
+    want = rim.stamp_mass(rss)                                      # (the mass kernel: this pair never had a split)
+    rim.close()
+    w.same("stamp_mass behind a threshold change", w.im.stamp_mass(w.ss), want)
+    w.im.stamp_mass_begin(w.ss)
+    w.same("stamp_mass_begin / _end behind a threshold change", w.im.stamp_mass_end(), want)
+    w.run(_op("mass", 4))
+    assert w.seen["ready0"] == 1 and w.seen["ready1"] == 0
+    off = np.max(np.abs(coarse - want) / np.maximum(want, 1e-300))
+    print("12. the T = 8 short-cut masses against the mass kernel's: %.3e relative" % off)
+    assert off > 1e-6
+    w.options(dict(tail_T=8.0))                                     # ... and back at the split's threshold the sums serve again
+    assert w.im.stamp_mass_ready(w.ss)
+    w.same("the short cut at the split's own threshold", w.im.stamp_mass(w.ss), coarse)
+    w.close()
+
+    # 13. the kernel variant between a product and its reader.  A render by the direct kernels vouches for no model image
+    #     (render_succeeded: `vouches` needs the recurrence), the dirty-tile render and the split's totals from the image are the
+    #     recurrence's alone, records and tile lists do not depend on the variant: nothing has to remember it
+    w = sw.Walker(cel)
+    dirty = lambda: w.im.last_render_dirty_tiles()
+    w.walk([_op("opt_kernel", 1, value=0), _op("render", 2, loglik=True), _op("opt_kernel", 3, value=1), _op("set_rows_1", 4), _op("render", 5, loglik=True)])
+    assert dirty() == -1                                            # (direct -> recurrence: no image to start from)
+    w.walk([_op("set_rows_1", 6), _op("render_noll", 7)])
+    assert dirty() >= 0                                             # (the recurrence's own image: legal)
+    w.walk([_op("opt_kernel", 8, value=0), _op("set_rows_1", 9), _op("render", 10, loglik=True)])
+    assert dirty() == -1                                            # (recurrence -> direct: the direct kernels render every tile)
+    w.walk([_op("set_rows_1", 11), _op("render_noll", 12)])
+    assert dirty() == -1
+    w.walk([_op("opt_kernel", 13, value=1), _op("set_rows_1", 14), _op("render_noll", 15)])
+    assert dirty() == -1
+    w.walk([_op("opt_kernel", 16, value=0), _op("render", 17, loglik=True), _op("opt_kernel", 18, value=1), _op("split_cold", 19), _op("flux", 20),
+            _op("mass", 21), _op("render", 22, loglik=True), _op("opt_kernel", 23, value=0)])
+
+    def direct_split(im, ss):
+        noise = im.photon_split_resident(ss, 24)
+        return dict(noise=noise, sums=im.sample_sums(), samples=im.fetch_samples(), info=w.samples_info(im))
+    a = w.outcome(lambda: direct_split(w.im, w.ss))                 # the recurrence's image on the device, the direct split
+    rim, rss = w.fresh(w.cur)
+    b = w.outcome(lambda: direct_split(rim, rss))
+    assert a[0] == "ok" and b[0] == "ok", (a, b)
+    w.same("the direct split behind a recurrence render", a[1], b[1])
+    rim.close()
+    w.close()
+
+    # 14. other owned rows under the per-tile Poisson partials: the reduce takes the owned tile rows of THIS render, so the dirty
+    #     tiles' render is legal and equal; the split's noise sums are a product of their time
+    w = sw.Walker(cel)
+    w.walk([_op("render", 1, loglik=True), _op("noise_rows", 2, rows=(64, 128)), _op("set_rows_1", 3), _op("render", 4, loglik=True)])
+    assert dirty() >= 0
+    noise = w.im.photon_split_resident(w.ss, 5)
+    rim, rss = w.fresh(w.cur)
+    rim.render(rss, loglik=True)
+    w.same("noise sums of the owned rows", noise, rim.photon_split_resident(rss, 5))
+    rim.close()
+    w.run(_op("noise_rows", 6, rows=(0, sw.H)))
+    kept = np.zeros(sw.B)
+    hip = C.CDLL(cel._lib.LIB_PATH)
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    assert hip.hipMemcpy(kept.ctypes.data, w.im.loglik_device_ptr(), kept.nbytes, 2) == 0
+    w.same("the split's noise sums behind other owned rows", kept, noise)
+    w.walk([_op("render", 7, loglik=True), _op("split_traced", 8)])
+    whole = np.zeros(sw.B)
+    assert hip.hipMemcpy(whole.ctypes.data, w.im.loglik_device_ptr(), whole.nbytes, 2) == 0
+    assert np.all(whole > noise)                                    # (non-vacuity: three tile rows hold more sky photons than one)
+    w.close()
+
+    # 15. the observed pixels' address handed out keeps the resident split: it stays the split of the pixels it was drawn from
+    #     (the library cannot know when the caller writes); cel_images_set_nelec is how a caller announces new pixels
+    w = sw.Walker(cel)
+    w.walk([_op("render", 1, loglik=True), _op("split_traced", 2)])
+    info = w.samples_info(w.im)
+    w.write_pixels(pixels)                                          # (9.'s pixels: every count one more)
+    assert w.samples_info(w.im) == info
+    rim, rss = w.with_split()                                       # a replay that split on the old pixels
+    w.same("sample_sums behind foreign pixels", w.im.sample_sums(), rim.sample_sums())
+    rim.close()
+    w.walk([_op("flux", 3), _op("mass", 4)])
+    w.im.set_nelec(pixels)
+    assert w.samples_info(w.im) == (0, 0) and not w.im.stamp_mass_ready(w.ss)
+    with pytest.raises(ValueError, match="resident photon split"):
+        calls["flux"]()
     w.close()
