@@ -576,6 +576,32 @@ def gen_src_psf_image(src, image):
     raise NotImplementedError("not implemented!")
 
 
+def gen_src_image_jac(src, image, xlim=None, ylim=None):
+    """gen_src_image and its per-pixel derivatives with respect to the source's own parameters, for one star or galaxy
+    -> (planes, ylim, xlim).  planes[0] is the expected photon image on the source's box (or on the limits given), planes[1],
+    planes[2] its derivatives with respect to src.u (ra, dec, per degree), and for a galaxy planes[3 .. 6] those with respect to
+    theta, sigma [arcsec], phi [degrees] and rho; the integer box is held fixed (ImageSet.stamp_jacobians).  (None, None, None)
+    where the source has no stamp.  No counterpart in the reference, whose galaxy_source_like_grad differences whole
+    likelihoods."""
+    if src.a == 1:
+        typ, shape = 1, [src.theta, src.sigma, src.phi, src.rho]
+    elif src.a == 0:
+        typ, shape = 0, (0.0, 0.0, 0.0, 0.0)
+    else:
+        raise NotImplementedError("gen_src_image_jac: a star (a = 0) or a galaxy (a = 1)")
+    iset = _image_set((image,))
+    srcs = iset._sources(np.array([typ], dtype=np.int32), np.asarray(src.u, dtype=np.float64)[None, :],
+                         np.array([[expected_photons(src, image)]]), np.asarray(shape, dtype=np.float64)[None, :])
+    boxes_in = None
+    if xlim is not None and ylim is not None:
+        boxes_in = np.array([[int(ylim[0]), int(ylim[1]), int(xlim[0]), int(xlim[1])]], dtype=np.int32)
+    planes, boxes = iset.stamp_jacobians(srcs, 0, scaled=True, boxes_in=boxes_in)
+    if planes[0] is None:
+        return None, None, None
+    y0, y1, x0, x1 = (int(v) for v in boxes[0])
+    return planes[0], (y0, y1), (x0, x1)
+
+
 # ---- celeste.py:193-199 -----------------------------------------------------------------------
 def gen_psf_src_image_bound(src, img):
     """radius about the source's pixel position that holds 1 - epsilon of its photons in this image: the band's PSF radius

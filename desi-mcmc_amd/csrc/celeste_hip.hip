@@ -93,6 +93,7 @@ static int fail(int code, const char *fmt, ...) {
 #include "k_render_qw.h"
 #include "k_mask.h"
 #include "k_misc.h"
+#include "k_stamp_jac.h"
 #include "k_patch_ll.h"
 #include "k_slice_gen.h"
 #include "k_type_move.h"
@@ -1491,11 +1492,22 @@ int cel_render_stamps(cel_images *im, cel_sources *src, int band, int scaled, co
     if (!im || !src || !offsets || !out) return fail(CEL_ERR_INVALID, "cel_render_stamps: null argument");
     if (band < 0 || band >= im->B) return fail(CEL_ERR_INVALID, "band %d out of range", band);
     if (src->B != im->B || src->ctx != im->ctx) return fail(CEL_ERR_INVALID, "sources do not match images");
+    if (scaled < 0 || scaled > 3)
+        return fail(CEL_ERR_INVALID, "cel_render_stamps: scaled must be 0, 1 (stamps) or 2, 3 (derivative planes), not %d", scaled);
+    const bool jac = scaled >= 2;              // k_stamp_jac.h: the stamp and its parameter derivatives, 3 or 7 planes per source
     cel_ctx *c = im->ctx;
     HIP_TRY(hipSetDevice(c->device));
     int64_t S = src->S;
     if (S == 0) return CEL_OK;
     if (offsets[0] != 0) return fail(CEL_ERR_INVALID, "cel_render_stamps: offsets[0] must be 0");
+    // the planes of a slot follow the source's type: the host's copy of the types, read back where the device wrote them last
+    std::vector<int32_t> types_now;
+    if (jac && (int64_t)src->h_type.size() != S) {
+        types_now.resize((size_t)S);
+        HIP_TRY(hipMemcpyAsync(types_now.data(), src->d_type, sizeof(int) * S, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    const int32_t *h_type = !jac ? nullptr : (types_now.empty() ? src->h_type.data() : types_now.data());
     std::vector<int32_t> hb((size_t)S * 4), hs((size_t)S);
     int rc = cel_stamp_boxes(im, src, band, hb.data(), hs.data());
     if (rc) return rc;
@@ -1523,9 +1535,10 @@ int cel_render_stamps(cel_images *im, cel_sources *src, int band, int scaled, co
             continue;
         }
         int64_t area = (int64_t)(y1 - y0) * (x1 - x0);
-        if (offsets[s + 1] - offsets[s] != area)
-            return fail(CEL_ERR_INVALID, "offsets[%lld+1]-offsets[%lld] = %lld but the stamp has %lld pixels",
-                        (long long)s, (long long)s, (long long)(offsets[s + 1] - offsets[s]), (long long)area);
+        const int planes = !jac ? 1 : ((h_type[s] == 1 || h_type[s] == 2) ? 7 : 3);
+        if (offsets[s + 1] - offsets[s] != planes * area)
+            return fail(CEL_ERR_INVALID, "offsets[%lld+1]-offsets[%lld] = %lld but the stamp has %d plane(s) of %lld pixels",
+                        (long long)s, (long long)s, (long long)(offsets[s + 1] - offsets[s]), planes, (long long)area);
         for (int xs = x0; xs < x1; xs += strip_w)
             for (int ys = y0; ys < y1; ys += ROWS)
                 jobs.push_back(StampJob{(int)s, xs, ys, ys + ROWS < y1 ? ys + ROWS : y1});
@@ -1553,7 +1566,12 @@ int cel_render_stamps(cel_images *im, cel_sources *src, int band, int scaled, co
         HIP_TRY(hipMemcpyAsync(d_obox, obox.data(), sizeof(int4) * S, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(d_off, offsets, sizeof(int64_t) * (S + 1), hipMemcpyHostToDevice, c->stream));
         int pi = prof_begin(c, CEL_K_STAMPS);
-        if (c->variant == 0)
+        if (jac)
+            hipLaunchKernelGGL(k_stamp_jac, dim3((unsigned)jobs.size()), dim3(64), 0, c->stream, (const BandDev *)im->d_bands, band,
+                               (const SrcRec *)(im->d_recs + (int64_t)band * S), (const StampJob *)d_jobs, (const int4 *)d_obox,
+                               (const int64_t *)d_off, (const int *)src->d_type, (const double *)src->d_shape, im->win_y0, strip_w,
+                               scaled == 3, d_out);
+        else if (c->variant == 0)
             hipLaunchKernelGGL(k_stamps, dim3((unsigned)jobs.size()), dim3(64), 0, c->stream, im->d_bands, band,
                                im->d_recs + (int64_t)band * S, d_jobs, d_obox, d_off, scaled, d_out);
         else

@@ -672,8 +672,8 @@ class ImageSet(object):
                                         boxes.ctypes.data_as(L.c_int32_p), status.ctypes.data_as(L.c_int32_p)))
         return boxes, status
 
-    def stamps(self, sources, band, scaled=False, boxes_in=None):
-        """Per-source stamps in one band -> (list of 2-D arrays or None, boxes[S,4] = y0,y1,x0,x1)."""
+    def _render_stamps(self, sources, band, mode, boxes_in, planes):
+        """cel_render_stamps with `scaled` = mode; planes: None (one 2-D stamp per source) or the planes of each source's slot"""
         S = sources.S
         # the sources' own boxes + status (one k_prep + a 20-byte-per-source copy, shared with the
         # render call below: the library keeps them until the sources change)
@@ -685,19 +685,34 @@ class ImageSet(object):
             status = (((boxes[:, 1] > boxes[:, 0]) & (boxes[:, 3] > boxes[:, 2])) & (status != -1)).astype(np.int32)
         area = np.where(status > 0, (boxes[:, 1] - boxes[:, 0]).astype(np.int64) * (boxes[:, 3] - boxes[:, 2]), 0)
         offs = np.zeros(S + 1, dtype=np.int64)
-        np.cumsum(area, out=offs[1:])
+        np.cumsum(area if planes is None else planes * area, out=offs[1:])
         flat = np.zeros(max(int(offs[-1]), 1))
         L.check(L.lib().cel_render_stamps(
-            self._h, sources._h, int(band), 1 if scaled else 0,
+            self._h, sources._h, int(band), mode,
             boxes.ctypes.data_as(L.c_int32_p) if boxes_in is not None else None,
             offs.ctypes.data_as(L.c_int64_p), flat.ctypes.data, L.CEL_HOST))
         out = []
         for s in range(S):
             if status[s] > 0:
-                out.append(flat[offs[s]:offs[s + 1]].reshape(boxes[s, 1] - boxes[s, 0], boxes[s, 3] - boxes[s, 2]))
+                hw = (boxes[s, 1] - boxes[s, 0], boxes[s, 3] - boxes[s, 2])
+                out.append(flat[offs[s]:offs[s + 1]].reshape(hw if planes is None else (int(planes[s]),) + hw))
             else:
                 out.append(None)
         return out, boxes
+
+    def stamps(self, sources, band, scaled=False, boxes_in=None):
+        """Per-source stamps in one band -> (list of 2-D arrays or None, boxes[S,4] = y0,y1,x0,x1)."""
+        return self._render_stamps(sources, band, 1 if scaled else 0, boxes_in, None)
+
+    def stamp_jacobians(self, sources, band, scaled=False, boxes_in=None):
+        """Per-source derivative stamps in one band (cel_render_stamps, scaled = 2 | 3; k_stamp_jac.h)
+        -> (list of arrays (3 or 7, h, w) or None, boxes[S,4] = y0,y1,x0,x1).  Plane 0 is the stamp `stamps` returns (unit, or
+        times counts when `scaled`), planes 1, 2 its derivatives with respect to ra and dec per degree, and a galaxy's planes
+        3 .. 6 those with respect to its four shape coordinates, in the units and conventions of loglik_grad (the integer box
+        held fixed).  Nothing is dropped.  None exactly where `stamps` gives None."""
+        typ = sources.get()[0]
+        planes = np.where((typ == 1) | (typ == 2), 7, 3).astype(np.int64)
+        return self._render_stamps(sources, band, 3 if scaled else 2, boxes_in, planes)
 
 
 def bounding_radius(weights, means, covars, error, center=(0.0, 0.0)):

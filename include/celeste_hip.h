@@ -360,6 +360,23 @@ int cel_debug_last_render(cel_images *img, int64_t *dirty_tiles);
  *         the caller-imposed box in boxes_in) and the stamps are written into it, row-major.
  *   scaled: 0 = unit flux, 1 = multiplied by counts[s][band] (gen_src_image_with_fluxes,
  *           celeste.py:84-96)
+ *           2, 3 = DERIVATIVE STAMPS of the unit (2) / counts-scaled (3) stamp: the slot of a source holds several planes of
+ *           the box's size, packed row-major one after another, and offsets[s+1]-offsets[s] = planes * area (checked before
+ *           anything is launched or written, as mode 4 of cel_patch_loglik checks its two planes):
+ *             plane 0     the stamp itself
+ *             plane 1, 2  d / d ra, d / d dec, per degree
+ *             plane 3-6   galaxies only: d / d of the four shape coordinates cel_sources_set takes -- theta, sigma
+ *                         [arcsec], phi [degrees], rho for type 1; theta, W00, W01, W11 for type 2
+ *           so a star's slot holds 3 planes and a galaxy's 7.  Units and conventions are cel_loglik_grad's: the integer box
+ *           is held fixed; ra / dec act through equa2pixel and, for type 1, through cd_at_pixel's cos(dec) term in W;
+ *           d / d sigma is 0 where the floor max(1/30, sigma) holds; d / d theta keeps both profiles.  Contracted with
+ *           r = nelec / lambda - 1 over the boxes and summed over the bands, the scaled = 3 planes are cel_loglik_grad's
+ *           g_radec / g_shape and plane 0 of scaled = 2 is g_counts.  Nothing is dropped: every component is evaluated at
+ *           every pixel of the box and CEL_OPT_TAIL_LOG[_SOURCE] is not read (a derivative can vanish where the value does
+ *           not, so a rule relative to the pixel's value bounds nothing); CEL_OPT_KERNEL 0 and 1 take the same kernel
+ *           (k_stamp_jac.h) and give the same bits.  A source without a stamp has its whole slot, every plane, zero-filled.
+ *           Any other value is CEL_ERR_INVALID.  (Before the derivative stamps every non-zero value meant "scaled"; that
+ *           was never documented, and only 0 and 1 keep their meaning.)
  *   boxes_in: NULL = each source's own box; else S*4 caller limits (xlim/ylim arguments of
  *           celeste.py:145-152); a source with an empty box is skipped. */
 int cel_stamp_boxes(cel_images *img, cel_sources *src, int band, int32_t *boxes, int32_t *status);

@@ -46,8 +46,19 @@ def short(name):
     return name
 
 
+_COLLECTED = None
+
+
 def collect():
-    """-> {kernel: {vgpr, sgpr, scratch, occupancy, lds, ...}} for every __global__ function of the library"""
+    """-> {kernel: {vgpr, sgpr, scratch, occupancy, lds, ...}} for every __global__ function of the library (compiled once per
+    process: the second caller of a test run gets the first one's table)"""
+    global _COLLECTED
+    if _COLLECTED is None:
+        _COLLECTED = _collect()
+    return _COLLECTED
+
+
+def _collect():
     p = subprocess.run(["make", "-C", CSRC, "resource-usage"], capture_output=True, text=True)
     text = p.stderr + p.stdout
     if p.returncode != 0:

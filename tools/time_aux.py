@@ -30,6 +30,7 @@ timed("render + loglik", lambda: f.images.render(f.sources, loglik=True), 10)
 timed("photon split (5 bands)", lambda: f.images.photon_split(f.sources, seed=1), 2)
 timed("E-step statistics", lambda: f.images.estep_stats(f.sources), 2)
 timed("stamps, band r, all sources", lambda: f.images.stamps(f.sources, 2, scaled=True), 2)
+timed("stamp planes, band r, all", lambda: f.images.stamp_jacobians(f.sources, 2, scaled=True), 2)
 
 ctx.profile(True)
 f.images.photon_split(f.sources, seed=1)
@@ -37,6 +38,13 @@ print("k_photon_split kernel alone: %.2f ms" % ctx.profile_get("split")[0])
 ctx.profile(True)
 f.images.estep_stats(f.sources)
 print("k_estep_src kernel alone: %.2f ms" % ctx.profile_get("estep")[0])
+ctx.profile(True)
+f.images.stamps(f.sources, 2, scaled=True)
+print("k_stamps_hw kernel alone: %.2f ms" % ctx.profile_get("stamps")[0])
+ctx.profile(True)
+planes, _ = f.images.stamp_jacobians(f.sources, 2, scaled=True)
+print("k_stamp_jac kernel alone: %.2f ms (%.2f GB of planes)" % (ctx.profile_get("stamps")[0], sum(p.nbytes for p in planes if p is not None) / 1e9))
+del planes
 
 # conditional log-likelihoods of 16 proposals per source against the resident split
 P = 16
