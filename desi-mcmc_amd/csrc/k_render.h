@@ -213,6 +213,7 @@ __device__ __forceinline__ double wave_sum_lane63(double v) {
     return v;
 }
 
+// [host-checked: begin]  (tests/test_setup_rules.py compiles this span for the CPU: plain functions of their arguments only)
 // Minimum of the positive-definite form a x^2 + 2 b x y + c y^2 over the rectangle
 // [x1,x2] x [y1,y2] (coordinates relative to the component mean).  0 when the mean is inside;
 // otherwise the minimum lies on the boundary: the smallest of the four 1-D constrained edge
@@ -240,17 +241,67 @@ __device__ inline double quad_min_rect(double a, double b, double c, double x1, 
 // minimum at +b sqrt(R / (det a)) -- on an interval, at those points clamped into it.  A tile on the
 // flank of a wide component needs fewer rows than the component's full height (config 3: 9 % fewer
 // component-rows).  fp32 reciprocal / square roots: the callers round outwards by more than their error.
-__device__ inline void quad_rows_on_columns(double a, double b, double c, double R, double x1, double x2,
-                                            float &ylo, float &yhi) {
+// (st, sb: the square roots at the two ends, c times the half-height of the ellipse on the columns xt and xb; detf: det in fp32)
+__device__ __forceinline__ void quad_rows_on_columns(double a, double b, double c, double R, double x1, double x2,
+                                                     float &ylo, float &yhi, float &st, float &sb, float &detf) {
     const double det = a * c - b * b;
     const double xs = b * (double)sqrt_f32((float)R * rcp_f32((float)(det * a)));
     const double xt = fmin(fmax(-xs, x1), x2), xb = fmin(fmax(xs, x1), x2);
     const float rc = rcp_f32((float)c);
-    const float st = sqrt_f32(fmaxf((float)(c * R - det * xt * xt), 0.0f));
-    const float sb = sqrt_f32(fmaxf((float)(c * R - det * xb * xb), 0.0f));
+    st = sqrt_f32(fmaxf((float)(c * R - det * xt * xt), 0.0f));
+    sb = sqrt_f32(fmaxf((float)(c * R - det * xb * xb), 0.0f));
     yhi = ((float)(-b * xt) + st) * rc;
     ylo = ((float)(-b * xb) - sb) * rc;
+    detf = (float)det;
 }
+__device__ inline void quad_rows_on_columns(double a, double b, double c, double R, double x1, double x2,
+                                            float &ylo, float &yhi) {
+    float st, sb, detf;
+    quad_rows_on_columns(a, b, c, R, x1, x2, ylo, yhi, st, sb, detf);
+}
+
+// The same rows and, from the same ellipse, whether the drop test 0.5 * quad_min_rect(...) <= R / 2 keeps the component on the
+// rectangle [x1, x2] x [y1, y2]: the set {form <= R, x1 <= x <= x2} is convex, it is empty exactly when the column nearest
+// the centre lies outside the ellipse's x-extent (det xc^2 > c R), its projection on y is [ylo, yhi], and it meets the
+// rectangle exactly when that interval meets [y1, y2].  So the answer is a sign and two compares on what the rows need
+// anyhow -- in fp32, against a test that shrinks its minimum by 1e-5, so only AWAY from the threshold:
+//   +1  the ellipse surely meets the rectangle (quad_min_rect's test keeps), 0 surely not (it drops), -1 too close to call:
+//       the caller runs quad_min_rect's test itself, and every decision is the one that test makes.
+// "Too close" is, in columns: |c R - det xc^2| <= QUAD_MEET_REL c R (a relative 1e-4: ten times the shrink, a thousand times
+// the fp32 rounding of the three products); in rows: an end of [ylo, yhi] within QUAD_MEET_ROW of the rectangle's edge, plus
+// what the end moves when R grows by the shrink -- d yhi / dR = 1 / (2 st) at the column xt (the envelope theorem: also where
+// xt is the interior maximiser), so R * 1e-5 / (2 st) to first order, taken four times over (QUAD_MEET_GROW) and multiplied
+// through by st: no division, and an end whose square root is near zero (the rectangle's corner at the ellipse's flank) is
+// always too close.  For a CLAMPED xt the square root's concavity makes the first-order step an upper bound for any step; for
+// an interior xt, yhi(R) is a maximum over x of such functions and not itself concave, and beyond first order the factor four
+// and the 5e-4 row are what carry it -- checked, not proved: tests/test_setup_rules.py finds no sure answer against the old
+// test among 2 10^5 pairs placed inside 1e-7 .. 1e-1 of an end, down to 5e-7 from the threshold.  QUAD_MEET_ROW = 5e-4
+// row is five times the bound on the fp32 ends' rounding (a few ulp of |cy| + |y| < 256 rows: < 1e-4 row) and a fortieth of
+// the 0.02 row by which the callers round the rows outwards.
+#define QUAD_MEET_REL 1e-4f
+#define QUAD_MEET_ROW 5e-4f
+#define QUAD_MEET_GROW 2e-5f
+__device__ __forceinline__ int quad_rows_and_meet(double a, double b, double c, double T /* R = 2 max(T, 0) */, double x1, double x2,
+                                                  double y1, double y2, float &ylo, float &yhi) {
+    const double R = 2.0 * fmax(T, 0.0);
+    float st, sb, detf;
+    quad_rows_on_columns(a, b, c, R, x1, x2, ylo, yhi, st, sb, detf);
+    const float Rf = (float)R;
+    const float xc = fminf(fmaxf((float)x1, 0.0f), (float)x2);
+    const float cR = (float)c * Rf;
+    const float g = cR - detf * xc * xc;
+    const float gt = QUAD_MEET_REL * cR;
+    const float dhi = yhi - (float)y1, dlo = (float)y2 - ylo;      // >= 0: that end reaches the rectangle
+    const float grow = QUAD_MEET_GROW * Rf;
+    const bool near_hi = fabsf(dhi) * st <= fmaf(QUAD_MEET_ROW, st, grow);
+    const bool near_lo = fabsf(dlo) * sb <= fmaf(QUAD_MEET_ROW, sb, grow);
+    const bool in_x = (g > gt);
+    const bool out_y = (dhi < 0.0f && !near_hi) || (dlo < 0.0f && !near_lo);
+    // (a threshold below zero: the form is nowhere negative, the test drops whatever the rectangle)
+    if (T < 0.0 || g < -gt || (in_x && out_y)) return 0;
+    return (in_x && !near_hi && !near_lo) ? 1 : -1;
+}
+// [host-checked: end]
 
 // ---- exp() for the recurrence seeds -----------------------------------------------------------
 // exp(x) = 2^e * 2^(j/64) * exp(r), x = (64 e + j) ln2/64 + r, |r| <= ln2/128: a 64-entry table

@@ -714,11 +714,13 @@ k_render_hw(RenderArgs a) {
             c = make_comp_lc(lc, rec);
             double Tk = dropping ? Tdrop + (double)(__logf((float)fabs(c.A)) - log_eps) : 100.0;   // T + log(A / eps), no fp64 division
             if (dropping) {
-                double qmin = quad_min_rect(c.qa, c.qb, c.qc, xa - c.mx, xb - c.mx, ya - c.my, yb - c.my);
-                keep = (0.5 * qmin <= Tk);
-                // rows on which the component can matter on THIS tile's columns
+                // rows on which the component can matter on THIS tile's columns, and from the same ellipse the drop test: the
+                // minimum of the form over the rectangle (quad_min_rect, ~45 VALU) only for the few components per 10^5 whose
+                // ellipse ends within fp32 reach of the rectangle's edge -- the decision is that test's for every component
                 float ylo, yhi;
-                quad_rows_on_columns(c.qa, c.qb, c.qc, 2.0 * fmax(Tk, 0.0), xa - c.mx, xb - c.mx, ylo, yhi);
+                const int meet = quad_rows_and_meet(c.qa, c.qb, c.qc, Tk, xa - c.mx, xb - c.mx, ya - c.my, yb - c.my, ylo, yhi);
+                keep = (meet > 0);
+                if (meet < 0) keep = (0.5 * quad_min_rect(c.qa, c.qb, c.qc, xa - c.mx, xb - c.mx, ya - c.my, yb - c.my) <= Tk);
                 const float cy = (float)(c.my - (double)Y0);
                 // (the integer rows inside [cy + ylo, cy + yhi], a fiftieth of a row of margin for the fp32 ends: rounds 1-5 took
                 // floor and ceil + 1, a row more at either end of every component that ends inside the tile)
