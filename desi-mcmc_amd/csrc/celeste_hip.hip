@@ -253,7 +253,9 @@ struct cel_images : FieldState {
     bool star_one_segment = false;   // every band passes star_setup's test: k_render_stars may take star tiles
     hipEvent_t ev_step = nullptr; // marks a step's readback copy: the host waits for it, not for the sort queued behind it
     DevBuf<int64_t> d_tile_off;
-    unsigned long long *d_cursor = nullptr;   // fine cursor, fine overflow, coarse cursor, coarse overflow (inside d_llband)
+    unsigned long long *d_cursor = nullptr;   // fine cursor, fine overflow, coarse cursor, coarse overflow (inside d_llband), and the binning
+                                              // pass's saved and changed-at words behind them (BIN_WORDS, k_prep_bin.h)
+    unsigned long long bin_step = 0;          // renders that asked k_prep to compare its boxes so far: the step number of the next is + 1
     DevBuf<int> d_lists;
     int nsx = 0, nsy = 0;                     // 256 x 256 super-tiles of the coarse binning level
     DevBuf<int> d_sup_cnt;
@@ -713,9 +715,11 @@ int cel_images_create(cel_ctx *c, int B, int H, int W, const cel_band *bands, ce
     HIP_TRY(im->d_nelec.grow(npix, npix, st));
     HIP_TRY(im->d_lambda.grow(npix, npix, st));
     HIP_TRY(im->d_partials.grow(T, T, st));
-    // per-band sums and the binning cursors (4 x u64) share one buffer: they ride back to the host in one copy
-    HIP_TRY(im->d_llband.grow(MAX_BANDS + 4, MAX_BANDS + 4, st));
+    // per-band sums and the binning cursors (4 x u64) share one buffer: they ride back to the host in one copy; the
+    // binning pass's saved cursors and its changed-at word lie behind them
+    HIP_TRY(im->d_llband.grow(MAX_BANDS + BIN_WORDS, MAX_BANDS + BIN_WORDS, st));
     im->d_cursor = reinterpret_cast<unsigned long long *>(im->d_llband + MAX_BANDS);
+    HIP_TRY(hipMemsetAsync(im->d_cursor, 0, sizeof(unsigned long long) * BIN_WORDS, st));
     HIP_TRY(im->d_tile_cnt.grow(T, T, st));
     HIP_TRY(im->d_tile_nstar.grow(T, T, st));
     HIP_TRY(im->d_tile_work.grow(T, T, st));
@@ -981,7 +985,9 @@ static double rsq_galaxy() {
     return -2.0 * log1p(-q);         // scipy.stats.chi2.ppf(q, 2)
 }
 
-static int run_prep(cel_images *im, cel_sources *src, const int *d_live = nullptr, int nobox = 0) {
+// step != 0 (a render whose binning may be skipped, never with d_live or nobox): k_prep compares every (box, kind) with what
+// stands in the tables before it stores (k_prep_bin.h)
+static int run_prep(cel_images *im, cel_sources *src, const int *d_live = nullptr, int nobox = 0, unsigned long long step = 0) {
     cel_ctx *c = im->ctx;
     int64_t n = src->S * im->B;
     int rc = ensure_recs(im, n > 0 ? n : 1);
@@ -990,7 +996,7 @@ static int run_prep(cel_images *im, cel_sources *src, const int *d_live = nullpt
     int pi = prof_slot(c, CEL_K_PREP);
     LAUNCH_EV(k_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), c->stream, EV0(c, pi), EV1(c, pi), im->d_bands, im->B,
               im->full_H, im->W, im->win_y0, im->H, src->S, src->d_type, src->d_radec, src->d_counts, src->d_shape,
-              rsq_galaxy(), im->d_recs, im->d_boxes, im->d_kind, im->d_status, im->d_cursor, d_live, nobox);
+              rsq_galaxy(), im->d_recs, im->d_boxes, im->d_kind, im->d_status, im->d_cursor, (d_live || nobox) ? 0ull : step, d_live, nobox);
     HIP_TRY(hipGetLastError());
     im->records_written((d_live || nobox) ? 0 : src->gen, src->S);      // a partial table is nobody else's
     return CEL_OK;
@@ -1089,7 +1095,7 @@ static int render_small_stars(cel_images *im, cel_sources *src, int flags, bool 
     }
     unsigned long long cur0;
     memcpy(&cur0, im->h_small + nblk, sizeof(cur0));
-    if (cur0 == x.stamp) { im->small_off = true; return CEL_OK; }
+    if (cur0 == x.stamp) { im->small_off = true; im->records_written(0, S); return CEL_OK; }    // (it wrote a part of the tables)
     if (ll) {
         // a band's partials in a fixed order -- eight interleaved Kahan sums (index mod 8: independent chains for the host's
         // pipeline; one chain of 512 dependent adds per band was 13 us of the step), added in order: the same bits
@@ -1179,13 +1185,13 @@ static int plan_render(const cel_images *im, const cel_sources *src, int flags, 
 }
 
 // the fine binning kernel: the one-kernel form (first event e0) or the second half of the two-level form
-static void launch_bin_fine(cel_ctx *c, cel_images *im, int64_t S, int NS, bool one_level, hipEvent_t e0, hipEvent_t e1) {
+static void launch_bin_fine(cel_ctx *c, cel_images *im, int64_t S, int NS, bool one_level, hipEvent_t e0, hipEvent_t e1, const BinStep &bs) {
     auto go = [&](auto kernel, int waves) {
         LAUNCH_EV(kernel, dim3(NS), dim3(64 * waves), c->stream, e0, e1,
                   im->d_boxes, im->d_kind, S, im->ntx, im->nty, im->TH, im->TW,
                   im->nsx, im->nsy, im->d_sup_cnt, im->d_sup_off, im->d_clist, im->d_clist.cap, im->d_tile_cnt,
                   im->d_tile_nstar, im->d_tile_work, im->d_tile_off, im->d_cursor, im->d_lists, im->d_lists.cap,
-                  (int *)(im->d_cursor + 1), (int *)(im->d_cursor + 3));
+                  (int *)(im->d_cursor + 1), (int *)(im->d_cursor + 3), bs);
     };
     // (16-wave blocks while every super-tile gets a CU of its own, 8-wave blocks -- two to a CU -- beyond that: k_bin2.h)
     const bool small_blocks = NS > c->n_cu;
@@ -1276,8 +1282,9 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
     // (cel_sources_set_rows stamps them), only the tiles that the changed sources' boxes touch -- the boxes they had and the
     // boxes they have now -- are rendered again, each from its complete list: the same arithmetic in the same order as the full
     // render, so pixels, partials and log-likelihoods are the full render's bit for bit; every other tile's pixels and partial
-    // are still valid.  Source preparation and binning run in full (66 us at configs[2]); a render with nothing changed, or
-    // after a whole-catalogue upload, is a full render -- nothing is ever answered from a cache.
+    // are still valid.  Source preparation runs in full (27 us at configs[2]), the binning only when the move changed a box or
+    // a kind (below); a render with nothing changed, or after a whole-catalogue upload, renders every tile -- no pixel, partial
+    // or log-likelihood is ever answered from a cache.
     DeltaRows delta;
     delta.n = 0;
     bool incr = plan.incremental;
@@ -1298,10 +1305,17 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         HIP_TRY(hipMemsetAsync(im->d_dirty, 0, sizeof(int) * (size_t)T, st));
         mark_dirty();   // the tiles the changed sources' OLD boxes touch (before k_prep rewrites the boxes) ...
     }
+    // Binning only when a box or a kind changed.  The tile lists are a function of the (box, kind) table, the tiling and the
+    // source count alone -- no flux enters them.  When the host vouches that the lists stand for the table in d_boxes /
+    // d_kind (binning_of, asked BEFORE this render's k_prep fires records_written), k_prep compares what it is about to store
+    // with that table ON THE DEVICE, on every call, and the binning kernels return at once unless it found a difference.
+    // CEL_OPT_INCREMENTAL = 0: no comparison, the binning runs in full.
+    bool bins_stand = c->incremental && im->lists.binning_of(S);
     im->render_begins((flags & CEL_RENDER_LOGLIK) != 0, !lambda_out && !(flags & CEL_RENDER_NO_STORE));
-    rc = run_prep(im, src);
+    rc = run_prep(im, src, nullptr, 0, bins_stand ? ++im->bin_step : 0ull);
     if (rc) return rc;
     if (incr) mark_dirty();     // ... and the tiles their new boxes touch
+    const int64_t lists_cap0 = im->d_lists.cap, clist_cap0 = im->d_clist.cap;
     if (im->d_lists.cap == 0) {
         // first guess: every (band, source) touches ~6 tiles; grown on overflow below
         const int64_t n = (S * im->B) * 6 + 1024;
@@ -1316,7 +1330,10 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
     const int tile_order = plan.tile_order, parts = plan.parts;
     const bool bin_direct = plan.bin_direct, diag = plan.diag;
     if (bin_direct) HIP_TRY(im->d_lists.grow((int64_t)T * S, (int64_t)T * S, st));
+    if (im->d_lists.cap != lists_cap0 || im->d_clist.cap != clist_cap0) { im->lists_regrown(); bins_stand = false; }
     for (int attempt = 0; attempt < 8; attempt++) {
+        // (a retry bins: its cursor words were zeroed by hand, the attempt before it left half-built lists)
+        const BinStep bs = {im->d_cursor, im->bin_step, (bins_stand && attempt == 0) ? 0 : 1};
         // d_cursor: [0] fine cursor, [1] fine overflow, [2] coarse cursor, [3] coarse overflow;
         // zeroed by k_prep (no memset in the queue), by hand only when that did not run or on a retry
         if (attempt > 0 || S * im->B == 0) HIP_TRY(hipMemsetAsync(im->d_cursor, 0, sizeof(unsigned long long) * 4, st));
@@ -1330,13 +1347,13 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         // than BIN_CH candidates, the two-level form after that
         if (bin_direct) {
             LAUNCH_EV(k_bin_direct, dim3(T), dim3(64), st, EV0(c, pi), bin_ev1, im->d_boxes, im->d_kind, S, im->ntx, im->nty, im->TH, im->TW,
-                      im->d_tile_cnt, im->d_tile_nstar, im->d_tile_work, im->d_tile_off, im->d_cursor, im->d_lists);
+                      im->d_tile_cnt, im->d_tile_nstar, im->d_tile_work, im->d_tile_off, im->d_cursor, im->d_lists, bs);
         } else if (im->bin_two_level) {
             LAUNCH_EV(k_bin_coarse, dim3(NS), dim3(64 * COARSE_WAVES), st, EV0(c, pi), (hipEvent_t) nullptr, im->d_boxes, S, im->nsx, im->nsy,
-                      im->d_sup_cnt, im->d_sup_off, im->d_cursor + 2, im->d_clist, im->d_clist.cap, (int *)(im->d_cursor + 3));
-            launch_bin_fine(c, im, S, NS, false, (hipEvent_t) nullptr, bin_ev1);
+                      im->d_sup_cnt, im->d_sup_off, im->d_cursor + 2, im->d_clist, im->d_clist.cap, (int *)(im->d_cursor + 3), bs);
+            launch_bin_fine(c, im, S, NS, false, (hipEvent_t) nullptr, bin_ev1, bs);
         } else {
-            launch_bin_fine(c, im, S, NS, true, EV0(c, pi), bin_ev1);
+            launch_bin_fine(c, im, S, NS, true, EV0(c, pi), bin_ev1, bs);
         }
         if (tile_order && !order_ready)
             // heaviest first: by the durations the tiles had in the previous render when that was
@@ -1408,10 +1425,11 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         }
         im->render_overflowed();
         // rerun with room (a truncated coarse list also truncates the fine counts)
-        if (too_dense) { im->bin_two_level = true; continue; }
+        if (too_dense) { im->bin_two_level = true; im->bin_form_changed(); continue; }
         const int64_t nc = (int64_t)coarse[0] + (int64_t)coarse[0] / 4 + 1024, nf = (int64_t)fine[0] + (int64_t)fine[0] / 4 + 1024;
         if (!coarse_ok) HIP_TRY(im->d_clist.grow(nc, nc, st));
         if (!fine_ok) HIP_TRY(im->d_lists.grow(nf, nf, st));
+        im->lists_regrown();
         if (attempt == 7) return fail(CEL_ERR_HIP, "tile lists kept overflowing");
     }
     if (flags & CEL_RENDER_LOGLIK) ll_from_mailbox(c, im->B, ll_band, ll_total);

@@ -66,6 +66,12 @@ struct ListStamps {
     uint64_t lists_gen = 0;
     int64_t cost_S = -1;          // sources of the render whose tile durations d_tile_cost holds (-1: nothing measured yet)
     int64_t order_S = -1;         // d_order already holds the heaviest-first order of those costs (sorted behind that render's readback)
+    // the lists, per-tile counts, offsets, star counts, work estimates, super-tile arrays and the saved cursor words were built
+    // by a SUCCESSFUL binning of exactly the (box, kind) table that stands in d_boxes / d_kind now, for so many sources, in this
+    // window, by the same binning form, and nobody has re-allocated or written any of them since (-1: not so).  With it a
+    // render's binning kernels may return at once when k_prep found no box or kind to change (k_bin2.h); without it they bin
+    int64_t binned_S = -1;
+    bool binning_of(int64_t S) const { return S > 0 && binned_S == S; }
     bool costs_of(int64_t S) const { return cost_S == S; }
     bool order_ready(int64_t S) const { return order_S == S && cost_S == S; }
 };
@@ -154,15 +160,17 @@ struct FieldState {
     void new_sky_level() { model.lambda_gen = 0; model.partials_gen = 0; }
     // cel_images_set_window (another window than before): boxes are cut to the window, and the resident split's patches are
     // boxes of the old one
-    void new_window() { rec.recs_gen = rec.hbox_gen = 0; model.lambda_gen = lists.lists_gen = 0; split.drop(); }
-    void records_regrown() { rec.recs_gen = rec.hbox_gen = 0; }
-    // k_prep ran on S sources; gen = 0: a partial table or one without boxes is nobody's
-    void records_written(uint64_t gen, int64_t S) { rec.recs_gen = gen; rec.last_S = S; }
+    void new_window() { rec.recs_gen = rec.hbox_gen = 0; model.lambda_gen = lists.lists_gen = 0; lists.binned_S = -1; split.drop(); }
+    void records_regrown() { rec.recs_gen = rec.hbox_gen = 0; lists.binned_S = -1; }
+    // k_prep ran on S sources; gen = 0: a partial table or one without boxes is nobody's.  Whoever ran it, the table the
+    // lists were binned from may be gone (a partial k_prep, one without boxes, one that compared against another step's
+    // word): a render asks binning_of BEFORE its own k_prep and vouches again in render_succeeded
+    void records_written(uint64_t gen, int64_t S) { rec.recs_gen = gen; rec.last_S = S; lists.binned_S = -1; }
     void host_boxes_read(uint64_t gen) { rec.hbox_gen = gen; }
     // the one-launch render of a small star field wrote k_prep's records, no tile lists and no tile durations
     void small_star_render(uint64_t gen, int64_t S, bool stored) {
         rec.recs_gen = gen; rec.last_S = S;
-        lists.lists_gen = 0; lists.cost_S = lists.order_S = -1;
+        lists.lists_gen = 0; lists.cost_S = lists.order_S = -1; lists.binned_S = -1;
         if (stored) model.lambda_gen = 0;
     }
     // the general render: before anything is queued, a render that overwrites them vouches for nothing ...
@@ -178,14 +186,17 @@ struct FieldState {
     void render_succeeded(const SourceStamps &src, int64_t S, bool costs, bool ordered, bool vouches, double render_T, int parts,
                           bool partials, bool incremental) {
         lists.cost_S = costs ? S : -1; lists.order_S = ordered ? S : -1;
-        lists.lists_gen = src.gen;
+        lists.lists_gen = src.gen; lists.binned_S = S;
         if (vouches) {
             model.lambda_gen = src.gen; model.lambda_uid = src.uid; model.lambda_T = render_T; model.lambda_parts = parts;
             model.partials_gen = partials ? src.gen : 0;
         }
         if (incremental) model.last_dirty = -2;
     }
-    void render_overflowed() { lists.cost_S = lists.order_S = -1; }
+    void render_overflowed() { lists.cost_S = lists.order_S = -1; lists.binned_S = -1; }
+    // a list buffer (d_lists, d_clist) was re-allocated; the image set went over to the two-level binning form
+    void lists_regrown() { lists.binned_S = -1; }
+    void bin_form_changed() { lists.binned_S = -1; }
     // d_partials was written by someone else: a masked set's Poisson pass, the direct split's noise sums, the E-step's sky term
     void partials_overwritten() { model.partials_gen = 0; }
     // cel_photon_split: masses waiting for cel_stamp_mass_end share a scratch slot with it; the recurrence form rewrites

@@ -13,8 +13,13 @@
 // accumulation order in k_render, and with it every output bit, is reproducible.
 // List SEGMENTS are placed with one atomicAdd per list (segment order in the buffer is
 // arbitrary and irrelevant); no atomics touch list contents.
+//
+// Every kernel here takes a BinStep (k_prep_bin.h): when this render's k_prep found no (box, kind) to change and the host
+// vouches that the lists in front of it were binned from exactly this table, every block returns at its first instruction
+// and block 0 puts the cursor words of that binning back.  The launch (and its event pair) stays.
 #pragma once
 #include "device_common.h"
+#include "k_prep_bin.h"
 
 #define SUPER_W 256
 #define SUPER_H 256
@@ -29,7 +34,8 @@ __device__ inline bool box_hits(int4 q, int X0, int X1, int Y0, int Y1) {
 __global__ void __launch_bounds__(64 * COARSE_WAVES)
 k_bin_coarse(const int4 *__restrict__ boxes, int64_t S, int nsx, int nsy, int *__restrict__ sup_cnt,
              int64_t *__restrict__ sup_off, unsigned long long *cursor, int *__restrict__ clist,
-             int64_t capacity, int *overflow) {
+             int64_t capacity, int *overflow, BinStep bs) {
+    if (bin_unchanged(bs)) return;
     __shared__ int wcnt[COARSE_WAVES];
     __shared__ long long base_s;
     const int st = blockIdx.x;
@@ -99,7 +105,8 @@ k_bin_fine_blk(const int4 *__restrict__ boxes, const int *__restrict__ kind, int
                int TW, int nsx, int nsy, const int *__restrict__ sup_cnt, const int64_t *__restrict__ sup_off,
                const int *__restrict__ clist, int64_t ccap, int *__restrict__ tile_cnt, int *__restrict__ tile_nstar,
                int *__restrict__ tile_work, int64_t *__restrict__ tile_off, unsigned long long *cursor,
-               int *__restrict__ lists, int64_t capacity, int *overflow, int *coarse_overflow) {
+               int *__restrict__ lists, int64_t capacity, int *overflow, int *coarse_overflow, BinStep bs) {
+    if (bin_unchanged(bs)) return;
     constexpr int BIN_TPW = 32 / FINE_WAVES;      // max tiles per wave: (256/64) * (256/32) / FINE_WAVES
     __shared__ int4 sbox[BIN_CH];
     __shared__ int skind[BIN_CH];
@@ -269,7 +276,8 @@ k_bin_fine_blk(const int4 *__restrict__ boxes, const int *__restrict__ kind, int
 __global__ void __launch_bounds__(64)
 k_bin_direct(const int4 *__restrict__ boxes, const int *__restrict__ kind, int64_t S, int ntx, int nty, int TH, int TW,
              int *__restrict__ tile_cnt, int *__restrict__ tile_nstar, int *__restrict__ tile_work, int64_t *__restrict__ tile_off,
-             unsigned long long *cursor, int *__restrict__ lists) {
+             unsigned long long *cursor, int *__restrict__ lists, BinStep bs) {
+    if (bin_unchanged(bs)) return;
     const int tile = blockIdx.x, lane = threadIdx.x;
     const int per_band = ntx * nty;
     const int b = tile / per_band;

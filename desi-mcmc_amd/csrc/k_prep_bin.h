@@ -88,12 +88,11 @@ struct PrepArgs {
     SrcRec *recs; int4 *boxes; int *kind; int *status;      // recs == nullptr: nothing to do
     int nobox;
 };
-__device__ __forceinline__ void prep_one(const BandDev *__restrict__ bands, int b, int64_t s, int64_t i, int B, int H, int W, int win_y0, int win_h,
-                                         const int *__restrict__ type, double ra, double dec, const double *__restrict__ counts,
-                                         const double *__restrict__ shape, double rsq_gal, SrcRec *__restrict__ recs,
-                                         int4 *__restrict__ boxes, int *__restrict__ kind, int *__restrict__ status, int nobox) {
+// ... the record itself (prep_record), and the record stored (prep_one)
+__device__ __forceinline__ void prep_record(const BandDev *__restrict__ bands, int b, int64_t s, int B, int H, int W, int win_y0, int win_h,
+                                            const int *__restrict__ type, double ra, double dec, const double *__restrict__ counts,
+                                            const double *__restrict__ shape, double rsq_gal, int nobox, SrcRec &r) {
     const BandDev &bd = bands[b];
-    SrcRec r;
     memset(&r, 0, sizeof(r));
     int t = type[s];
     // equa2pixel (fits_image.py:166-174)
@@ -185,7 +184,43 @@ __device__ __forceinline__ void prep_one(const BandDev *__restrict__ bands, int 
         r.type = -1;
     }
     prep_window(r, py, win_y0, win_h);
+}
+__device__ __forceinline__ void prep_one(const BandDev *__restrict__ bands, int b, int64_t s, int64_t i, int B, int H, int W, int win_y0, int win_h,
+                                         const int *__restrict__ type, double ra, double dec, const double *__restrict__ counts,
+                                         const double *__restrict__ shape, double rsq_gal, SrcRec *__restrict__ recs,
+                                         int4 *__restrict__ boxes, int *__restrict__ kind, int *__restrict__ status, int nobox) {
+    SrcRec r;
+    prep_record(bands, b, s, B, H, W, win_y0, win_h, type, ra, dec, counts, shape, rsq_gal, nobox, r);
     prep_store(r, i, recs, boxes, kind, status);
+}
+
+// The binning pass's words behind its four cursor words (fine cursor, fine overflow, coarse cursor, coarse overflow):
+//   cursor[BIN_KEEP .. BIN_KEEP + 3]      the four as the last binning left them, saved by k_prep before it zeroes them
+//   cursor[BIN_CHANGED + BIN_LINE * k]    k < BIN_NCHANGED: the step number of the last k_prep in which a wave dealt to slot k
+//                                         found a (box, kind) to change
+// A binning kernel whose step stands in none of the BIN_NCHANGED words has the lists of exactly this table in front of it -- when
+// the host vouches for that (ListStamps::binning_of, field_state.h; force = 1 otherwise) -- and returns at once, its block 0
+// putting the saved words back: the mailbox copy then carries the totals and flags of the binning that built the lists.
+// (Why not ONE word: in a chain that moves every source, every wave of k_prep stores it, and stores to one cache line queue up
+// behind one another -- 782 of them cost the flagship's k_prep 21 us.  Dealt over 32 lines of their own they cost nothing.)
+#define BIN_KEEP 4
+#define BIN_LINE 16             // 64-bit words per 128-byte line
+#define BIN_CHANGED 16          // (the cursor words start a line of their own: the changed-at words follow on the next)
+#define BIN_NCHANGED 32
+#define BIN_WORDS (BIN_CHANGED + BIN_LINE * BIN_NCHANGED)
+struct BinStep {
+    unsigned long long *words;      // the BIN_WORDS words: cursors, saved cursors, changed-at words
+    unsigned long long step;        // this render's step number (never 0)
+    int force;                      // 1: bin whatever the words say
+};
+// true: nothing to do (every thread of the block gets the same answer)
+__device__ __forceinline__ bool bin_unchanged(const BinStep &bs) {
+    if (bs.force) return false;
+    int hit = 0;
+    if (threadIdx.x < BIN_NCHANGED) hit = bs.words[BIN_CHANGED + BIN_LINE * threadIdx.x] == bs.step;
+    if (__syncthreads_or(hit)) return false;        // (bs and the words are the same for every thread of every block)
+    if (blockIdx.x == 0 && threadIdx.x < 4) bs.words[threadIdx.x] = bs.words[BIN_KEEP + threadIdx.x];
+    return true;
 }
 
 __global__ void __launch_bounds__(256)
@@ -193,20 +228,38 @@ k_prep(const BandDev *__restrict__ bands, int B, int H, int W, int win_y0, int w
        const int *__restrict__ type, const double *__restrict__ radec,
        const double *__restrict__ counts, const double *__restrict__ shape, double rsq_gal,
        SrcRec *__restrict__ recs, int4 *__restrict__ boxes, int *__restrict__ kind, int *__restrict__ status,
-       unsigned long long *__restrict__ cursor /* the binning pass's 4 cursors / flags, zeroed here (a memset of
-                                                  its own cost 15 us of queue time per step), or nullptr */,
+       unsigned long long *cursor /* the binning pass's 4 cursors / flags, saved behind themselves (BIN_KEEP) and zeroed here
+                                     (a memset of its own cost 15 us of queue time per step), or nullptr */,
+       unsigned long long step /* != 0: a wave with a thread whose (box, kind) differs from what stands in the tables writes
+                                  this number into its changed-at word before it stores (every writer the same value, nothing
+                                  resets the words) */,
        const int *__restrict__ live /* [S] or nullptr: a source with live[s] < 0 is skipped (a retired slice chain:
                                        nothing reads its records this round) */,
        int nobox = 0 /* 1: the records feed conditional likelihoods on FIXED patch limits (the slice samplers' rounds): a
                         galaxy's own box -- the bounding radius over its 42 convolved components, most of this kernel's
                         arithmetic -- is not needed and is set to the whole window */) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < 4 && cursor) cursor[i] = 0ull;
+    if (i < 4 && cursor) { cursor[BIN_KEEP + i] = cursor[i]; cursor[i] = 0ull; }
     if (i >= S * B) return;
     int b = (int)(i / S);
     int64_t s = i - (int64_t)b * S;
     if (live && live[s] < 0) return;
-    prep_one(bands, b, s, i, B, H, W, win_y0, win_h, type, radec[2 * s], radec[2 * s + 1], counts, shape, rsq_gal, recs, boxes, kind, status, nobox);
+    if (!step) {
+        prep_one(bands, b, s, i, B, H, W, win_y0, win_h, type, radec[2 * s], radec[2 * s + 1], counts, shape, rsq_gal, recs, boxes, kind, status, nobox);
+        return;
+    }
+    // what the lists were binned from, asked for before the arithmetic that hides the load
+    const int4 was = boxes[i];
+    const int was_kind = kind[i];
+    SrcRec r;
+    prep_record(bands, b, s, B, H, W, win_y0, win_h, type, radec[2 * s], radec[2 * s + 1], counts, shape, rsq_gal, nobox, r);
+    const int now_kind = r.type < 0 ? 0 : (r.type == 0 ? K_PSF : K_GAL);
+    const bool changed = was.x != r.x0 || was.y != r.x1 || was.z != r.y0 || was.w != r.y1 || was_kind != now_kind;
+    // one store per wave, into the word of the wave's slot
+    const unsigned long long any = __ballot(changed);
+    if (any && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)any) - 1))
+        __hip_atomic_store(cursor + BIN_CHANGED + BIN_LINE * ((i >> 6) & (BIN_NCHANGED - 1)), step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    prep_store(r, i, recs, boxes, kind, status);
 }
 
 // Gibbs resamples the sky level (models.py:156-160): one scalar, passed as a kernel argument so
