@@ -492,11 +492,7 @@ int cel_ctx_create(int device, void *stream, cel_ctx **out) {
     for (int i = 0; i < 6; i++) { amp[i] = H_EXP_AMP[i] / se; var[i] = H_EXP_VAR[i]; }
     for (int i = 0; i < 8; i++) { amp[6 + i] = H_DEV_AMP[i] / sd; var[6 + i] = H_DEV_VAR[i]; }
     double ic[64], lc[64];
-    for (int j = 0; j < 64; j++) {
-        long double cj = 1.0L + ((long double)j + 0.5L) / 64.0L;
-        ic[j] = (double)(1.0L / cj);
-        lc[j] = (double)(-logl((long double)ic[j]));
-    }
+    log_tab_fill(ic, lc);
     if ((e = hipMemcpyToSymbol(HIP_SYMBOL(c_prof_amp), amp, sizeof(amp))) != hipSuccess ||
         (e = hipMemcpyToSymbol(HIP_SYMBOL(c_prof_var), var, sizeof(var))) != hipSuccess ||
         (e = hipMemcpyToSymbol(HIP_SYMBOL(c_log_ic), ic, sizeof(ic))) != hipSuccess ||

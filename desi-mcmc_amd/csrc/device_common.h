@@ -39,6 +39,17 @@ __constant__ double c_prof_var[K_PROF];
 // host, so that log(m) = lc[j] + log1p(m * ic[j] - 1) holds to the last bit for m in [1, 2).
 __constant__ double c_log_ic[64];
 __constant__ double c_log_lc[64];
+// [prim-checked: begin]
+// the host's values for the two (cel_ctx_create uploads them): ic[j] within half an ulp of 1/c_j, lc[j] within half an ulp
+// (+ 2^-11 ulp, long double's own rounding) of -log of THAT ic[j]
+inline void log_tab_fill(double ic[64], double lc[64]) {
+    for (int j = 0; j < 64; j++) {
+        long double cj = 1.0L + ((long double)j + 0.5L) / 64.0L;
+        ic[j] = (double)(1.0L / cj);
+        lc[j] = (double)(-logl((long double)ic[j]));
+    }
+}
+// [prim-checked: end]
 
 static const double H_EXP_AMP[6] = {2.34853813e-03, 3.07995260e-02, 2.23364214e-01,
                                     1.17949102e+00, 4.33873750e+00, 5.99820770e+00};

@@ -567,13 +567,7 @@ k_patch_ll_nz(const BandDev *__restrict__ bands, int B, int64_t P, const SrcRec 
     if (!done) {
         if (rec.type < 0) rec.type = (rec.type == -2) ? 1 : 0;
         rec.scale = 1.0;
-        {   // 2^(j/256), j = 4 lane + k: the 64-entry value times 2^(k/256)
-            const double e64 = exp2((double)lane * (1.0 / 64.0));
-            et[4 * lane + 0] = e64;
-            et[4 * lane + 1] = e64 * 1.0027112750502025;      // 2^(1/256)
-            et[4 * lane + 2] = e64 * 1.0054299011128027;      // 2^(2/256)
-            et[4 * lane + 3] = e64 * 1.0081558981184175;      // 2^(3/256)
-        }
+        exp_tab256_fill(et, lane, exp2((double)lane * (1.0 / 64.0)));      // 2^(j/256), j = 4 lane + k
         ltq[lane] = c_log_ic[lane];
         ltq[64 + lane] = c_log_lc[lane];
         const LaneConst lc = lane_consts(lane, bd);

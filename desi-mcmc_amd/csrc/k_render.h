@@ -121,10 +121,14 @@ __device__ inline int rec_fetch(const SrcRec *__restrict__ recs, int s, int lane
     return reinterpret_cast<const int *>(recs + s)[lane & 31];
 }
 
+// [prim-checked: begin]  (tests/test_primitives.py compiles the spans between these marks for the CPU and holds them, and the
+// same functions on the device, to the bounds stated here against long-double references)
 // 1/d and 1/sqrt(d) for the component tables: fp32 seed + two Newton steps (relative error ~1e-7 ->
 // 1e-14 -> rounding), a dozen independent-ish instructions against the ~35 of a correctly rounded
 // fp64 division followed by a correctly rounded square root, whose last bit nothing here needs.
 // d is a covariance determinant: positive, far inside fp32's range.
+// Bounds (seed within 1.5 fp32 ulp): 1/d to 0.5 ulp + 3e-11 ulp -- the last step's rounding; 1/sqrt(d) to 2 ulp (half an ulp
+// of the result after 1.5 u relative from the step's two inner roundings, u = 2^-53).  MEASURED: see rcp64 / rsqrt64.
 __device__ inline void rcp_rsqrt(double d, double &inv, double &rsq) {
     double y = (double)rcp_f32((float)d);
     y = fma(y, fma(-d, y, 1.0), y);
@@ -135,6 +139,9 @@ __device__ inline void rcp_rsqrt(double d, double &inv, double &rsq) {
 }
 
 // 1/d and 1/sqrt(d) alone, the same way (d positive and of moderate size: variances, determinants, 1 + t^2)
+// MEASURED: rcp64 0.5000 ulp on the CPU with the seed moved by -1, 0, +1 fp32 ulp and on the device; rsqrt64 1.97 ulp on the
+// CPU with the seed one ulp off (1.90 with the correctly rounded one), 1.90 ulp on the device (all 2^23 fp32 mantissas, odd and
+// even exponents, and doubles with random low bits).
 __device__ inline double rcp64(double d) {
     double y = (double)rcp_f32((float)d);
     y = fma(y, fma(-d, y, 1.0), y);
@@ -145,6 +152,7 @@ __device__ inline double rsqrt64(double d) {
     z = z * fma(-0.5 * d * z, z, 1.5);
     return z * fma(-0.5 * d * z, z, 1.5);
 }
+// [prim-checked: end]
 
 __device__ inline Comp make_comp_lc(const LaneConst &lc, const RecU &r) {
     double cxx, cxy, cyy, wt, mux, muy;
@@ -303,10 +311,14 @@ __device__ __forceinline__ int quad_rows_and_meet(double a, double b, double c, 
 }
 // [host-checked: end]
 
+// [prim-checked: begin]
 // ---- exp() for the recurrence seeds -----------------------------------------------------------
 // exp(x) = 2^e * 2^(j/64) * exp(r), x = (64 e + j) ln2/64 + r, |r| <= ln2/128: a 64-entry table
 // of 2^(j/64) in LDS and a degree-5 polynomial (truncation r^6/720 < 4e-17), ~9 fp64 ops against
-// ~17 + range checks for the library exp; error <= ~2 ulp.  The argument arrives already in units
+// ~17 + range checks for the library exp.  Error, for a normal result: <= 2.34 ulp + twice the table entry's own error in its
+// ulp -- 3.34 ulp on a correctly rounded table, 4.34 ulp on entries within 1 ulp (exp2 on the device); the terms are in
+// tests/test_primitives.py.  MEASURED: 2.30 ulp over 10^7 arguments on the CPU (correctly rounded table; 2.41 over 2 10^7 once),
+// 2.23 ulp over 10^6 on the device, whose entries are within 0.57 ulp.  The argument arrives already in units
 // of ln2/64 (t = x * 64/ln2: the table builder folds that factor into the quadratic-form
 // coefficients, which saves the scaling multiply and the two-step reduction per seed).
 // f = t - rint(t) is exact; the powers of ln2/64 are folded into the polynomial's coefficients.
@@ -328,10 +340,19 @@ __device__ inline double exp_tab64(double t, const double *__restrict__ et) {
     return ldexp(et[ni & 63] * p, ni >> 6);
 }
 
-// the same on a 256-entry table (t in units of ln2/256) with a cubic: |r| <= ln2/512, truncation r^4/24 < 1.4e-13 relative --
-// two fma less, for the evaluations at the photons (k_patch_ll_nz: 14 VALU per galaxy component and photon with it), whose
-// log-likelihood sums are tested to 1e-12
+// the same on a 256-entry table (t in units of ln2/256) with a cubic: |r| <= ln2/512, truncation r^4/24 e^|r| <= 1.4015e-13
+// relative -- two fma less, for the evaluations at the photons (k_patch_ll_nz: 14 VALU per galaxy component and photon with
+// it), whose log-likelihood sums are tested to 1e-12.  With the roundings (entries built as below from a 64-entry value within
+// 1 ulp): <= 1.4083e-13 relative for a normal result.  MEASURED: 1.4051e-13 on the CPU, 1.4048e-13 on the device.
 #define EXP_SCALE256 369.32993046757462703   // 256 / ln 2
+// entries 4 lane .. 4 lane + 3 of that table, 2^(j/256) for j = 4 lane + k: the 64-entry value e64 = 2^(lane/64) times 2^(k/256)
+// (each within (2 T + 2) u relative of the exact power for an e64 within T ulp, u = 2^-53)
+__device__ inline void exp_tab256_fill(double *et256, int lane, double e64) {
+    et256[4 * lane + 0] = e64;
+    et256[4 * lane + 1] = e64 * 1.0027112750502025;      // 2^(1/256)
+    et256[4 * lane + 2] = e64 * 1.0054299011128027;      // 2^(2/256)
+    et256[4 * lane + 3] = e64 * 1.0081558981184175;      // 2^(3/256)
+}
 __device__ inline double exp_tab256_p3(double t, const double *__restrict__ et256) {
     const double c1 = 2.7076061740622863e-03;     // (ln2/256)
     const double c2 = 3.6655655969101056e-06;     // (ln2/256)^2 / 2
@@ -349,8 +370,12 @@ __device__ inline double exp_tab256_p3(double t, const double *__restrict__ et25
 // log(x) = e ln2 + lc[j] + log1p(r), x = 2^e m, m in [1,2), j = floor(64 (m - 1)),
 // r = m * ic[j] - 1 with |r| <= 2^-7, log1p by its series to r^7 (truncation r^8/8 < 2e-18).
 // ~19 fp64-rate instructions against ~95 for the library log (which carries double-double
-// arithmetic for arguments this path never sees); error <= ~1.5 ulp.  x must be positive,
-// finite and normal: lambda >= eps > 0 here.  lt = 128 doubles in LDS: ic[64] then lc[64].
+// arithmetic for arguments this path never sees).  Error: <= 0.5 ulp of the result + 1.16e-16 ABSOLUTE (the rounding of
+// lc[j] and of the sum lc[j] + ..., each up to 2^-54, and 4.4e-18 from r, the series and e * LN2_LO; derived in
+// tests/test_primitives.py).  That is <= 1.5 ulp where |log x| >= 0.5, and an absolute error near x = 1, where it is many
+// ulp of a small result (e ln2 cancels against lc[j] just below 1).  MEASURED: 1.11e-16 beyond the half ulp on the CPU and
+// on the device; 0.99 ulp where |log x| >= 0.5; 6.6e-17 absolute on [1 - 1/128, 1 + 1/64).  Other arguments (0, negative,
+// denormal, inf, NaN) go to the library log.  lt = 128 doubles in LDS: ic[64] then lc[64] (log_tab_fill, device_common.h).
 __device__ inline double log_tab(double x, const double *__restrict__ lt) {
     const double LN2_HI = 0x1.62e42fee00000p-1;      // ln 2, upper 32 bits (e * HI is exact)
     const double LN2_LO = 0x1.a39ef35793c76p-33;     // ln 2 - HI
@@ -370,6 +395,7 @@ __device__ inline double log_tab(double x, const double *__restrict__ lt) {
     double e = (double)ex;
     return fma(e, LN2_HI, lt[64 + j] + fma(e, LN2_LO, p));
 }
+// [prim-checked: end]
 
 // ---- direct evaluator: sum over components of A exp(-q/2) at (x, y) -------------------------
 // qscale = 1 for a table holding the inverse covariance itself (stamps), 1/EXP_SCALE for the

@@ -32,6 +32,8 @@
 #endif
 #include "hw_source.h"
 
+// [prim-checked: begin]  (tests/test_primitives.py: the published Philox4x32-10 known answers, the order and formula of
+// philox_double, philox_word's half-words, fast_rcp's bound)
 #ifndef PHILOX_ROUNDS
 #define PHILOX_ROUNDS 10      // Philox4x32-10 (Salmon et al. 2011); lower values only for timing experiments
 #endif
@@ -75,18 +77,25 @@ __device__ inline double philox_double(Philox &g) {
     g.have -= 2;
     return ((double)a * 67108864.0 + (double)b) * (1.0 / 9007199254740992.0);
 }
+// [prim-checked: end]
 
 // Stirling-series tail used by BTPE's final acceptance test (btpe_st_r below).  The leading constant is randomkit's 13680
 // (deps/randomkit/distributions.c:362-365, the sampler the reference's split calls); Kachitvichyanukul & Schmeiser print
 // 13860 = 166320/12.  Kept as the reference's dependency has it: the term is a 1e-3 relative change of a 1/(12 x)
 // correction inside an accept/reject bound, far below anything the pmf tests resolve.
 
-// 1/x to ~4e-15 relative for x of fp32 range: v_rcp_f32 (1 ulp) + one Newton step in fp64 (5 instructions with the two
-// conversions, against ~15 for an IEEE fp64 division).  Used where a probability or a pmf ratio is formed.
+// [prim-checked: begin]
+// 1/x for x of fp32 range: v_rcp_f32 + one Newton step in fp64 (5 instructions with the two conversions, against ~15 for an
+// IEEE fp64 division).  Used where a probability or a pmf ratio is formed.  The step squares the seed's error e0 and adds one
+// rounding: <= e0^2 + 1.01 * 2^-53 relative, e0 <= 2^-24 (the conversion of x) + the instruction's own -- 5.70e-14 for an
+// instruction within 1.5 fp32 ulp (what tests/test_primitives.py assumes and asserts), 3.2e-14 for one within 1 ulp.
+// MEASURED: 4.34e-14 on the CPU with the seed a whole ulp off its correctly rounded value, 7.96e-15 with that value itself;
+// 1.45e-14 on the device (not the 4e-15 these comments used to quote).
 __device__ inline double fast_rcp(double x) {
     double y = (double)rcp_f32((float)x);
     return fma(y, fma(-x, y, 1.0), y);
 }
+// [prim-checked: end]
 
 // Binomial(n, r) for r <= 1/2, n r <= 30: sequential inversion (BINV).
 // P(X = 0) = (1 - r)^n >= 1 - n r, so a uniform at or below 1 - n r returns 0 before anything
@@ -102,7 +111,7 @@ __device__ inline long long binom_inversion(long long n, double r, double U /* t
     const double qn = exp_tab64(nd * log_tab(q, lt) * EXP_SCALE, et);
     if (U <= qn) return 0;
     // p(X) = p(X-1) (n - X + 1)/X r/q: one division for r/q, 1/X from an fp32 reciprocal and
-    // one Newton step (4e-15; the recurrence needs no more)
+    // one Newton step (<= 5.7e-14, fast_rcp above; the recurrence needs no more)
     const double s = r / q;
     const double bound = fmin(nd, np + 10.0 * sqrt(np * q + 1.0));
     double X = 0.0, px = qn;
@@ -119,10 +128,10 @@ __device__ inline long long binom_inversion(long long n, double r, double U /* t
 }
 
 // Binomial(n, r) for r <= 1/2, n r > 30: BTPE (triangle / parallelogram / exponential tails).
-// Round 6: no IEEE fp64 division and no library log in it -- quotients by fast_rcp (4e-15 relative: fp32 reciprocal + a Newton
+// Round 6: no IEEE fp64 division and no library log in it -- quotients by fast_rcp (<= 5.7e-14 relative: fp32 reciprocal + a Newton
 // step, 4 instructions against ~15), logarithms by the table log of k_render.h (the sampler's LDS table, to the last bits); the
 // square root that sizes the triangle stays exact (the envelope's constants assume that p1).  These touch the algorithm at accept/reject
-// boundaries only, 1e-14 wide; the pmf tests (chi^2 against the exact pmf, moments) are unchanged.  A trip of 64 queued draws
+// boundaries only, 1e-13 wide; the pmf tests (chi^2 against the exact pmf, moments) are unchanged.  A trip of 64 queued draws
 // holding one BTPE lane costs every lane this code: ~1 500 instructions before, ~600 now (tools/ablate_split.py).
 __device__ inline double btpe_st_r(double x, double rx /* ~1/x */) {
     const double r2 = rx * rx;
@@ -235,11 +244,13 @@ __device__ inline long long binomial_draw(long long n, double p, Philox &g, cons
 __device__ inline double split_tf(long long n, double pr) {         // floor((1 - n p) 2^16): V < tf passes; <= 0: nobody does
     return floor((1.0 - (double)n * pr) * SPLIT_WORD_SCALE);
 }
+// [prim-checked: begin]
 __device__ inline unsigned philox_word(const Philox &g, int w /* 0..7 */) {
     // (shifts, not a selection among the four words: the compiler turns a chain of selects on an index into a table in scratch)
     const unsigned long long lo = ((unsigned long long)g.out[1] << 32) | g.out[0], hi = ((unsigned long long)g.out[3] << 32) | g.out[2];
     return (unsigned)(((w & 4) ? hi : lo) >> ((w & 3) * 16)) & 0xffffu;
 }
+// [prim-checked: end]
 // the whole draw for one (pixel, source): what k_photon_split_hw does in two passes
 __device__ inline long long split_draw(long long n, double pr, unsigned long long seed, unsigned long long group_key, int word,
                                        unsigned long long pixel_key, unsigned s, const double *__restrict__ et,
@@ -925,7 +936,7 @@ __device__ __forceinline__ void photon_split_hw_body(SplitArgs a) {
         if (a.massfx) {                  // this half-tile's share of the source's stamp mass (cel_stamp_mass's short cut)
             fsum = wave_sum_lane63(fsum);
             if (lane == 63 && fsum > 0.0 && rec.scale > 0.0)
-                atomicAdd(a.massfx + ((int64_t)s * a.B + b), (unsigned long long)__double2ull_rn(fsum * fast_rcp(rec.scale) * MASS_FX));   // 1 / scale to 4e-15
+                atomicAdd(a.massfx + ((int64_t)s * a.B + b), (unsigned long long)__double2ull_rn(fsum * fast_rcp(rec.scale) * MASS_FX));   // 1 / scale to 5.7e-14
         }
         if (a.nz && __ballot(zhi >= 0)) {
             // the patch's photon rectangle (what the conditional likelihoods will evaluate): one

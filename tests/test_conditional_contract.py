@@ -32,7 +32,9 @@ The dense kernels, host-buffer form.  The value is linear in the patch data, so 
      * C_R = 1e-12, the evaluator's relative rounding per term (test_drop_contract.py: seeds, the 64-row recurrence, the
        accumulator's adds); every weight is positive, so sum |t| = m and the relative error of m is C_R, which is its log's
        absolute error; counts * m and + eps / + bg add 2 ulp relative: 2e-16, inside the rounding of 1e-12;
-     * log_tab: <= 1.5 ulp of its result (k_render.h); the direct kernel's log(): 1 ulp;
+     * log_tab: <= 0.5 ulp of its result + 1.16e-16 absolute (k_render.h; derived and asserted in test_primitives.py, measured
+       0.5 ulp + 1.11e-16) -- not "1.5 ulp of its result", which holds only where |log v| >= 0.5: the 2 ulp(|log v|) below
+       take the half ulp, and the absolute part is 1.2e-4 of C_R, so tol covers it unchanged; the direct kernel's log(): 1 ulp;
      * the two sums: ll_A and ll_B are formed by the same fixed tree, and differ in the lane that holds p.  On the path from
        that lane to the result there are the lane's own adds (<= 2), six wave_sum steps (eight tree steps in k_patch_ll), the
        chunk class's add, the mass term, three class adds and the band loop: <= 14 roundings of half an ulp each per sum,
@@ -62,7 +64,8 @@ shifts of 1e-3, 0.3 and 5 px, one change of each shape coordinate) are scored wi
 2 (k_patch_ll_hw<0> on the photon rectangle) against the exact  sum z log(counts m) - counts sum w  on the fetched data.
    tol of a value = sum over photons of z (rel + 2 ulp(|log v|)) + 16 ulp(S_abs), S_abs = sum z |log v| + counts sum w, and
    rel = sum_k t_k err_k / m,  err_k = 1.5e-13 + 6 ulp kappa_k q_abs_k / 2   for the photon kernel:
-     1.4e-13 exp_tab256_p3's truncation (k_render.h) + its table and three fma; the exponent is five fma (one multiply and one
+     1.4015e-13 exp_tab256_p3's truncation (k_render.h) + 6.7e-16 for its table and three fma = 1.4083e-13 (derived and
+     asserted in test_primitives.py; measured 1.405e-13): inside the 1.5e-13; the exponent is five fma (one multiply and one
      fma on two squares in the rotated form) of products whose sizes add up to q_abs_k / 2: <= 6 roundings of that size;
      kappa_k = cond(W) cond(P_k) for the rotated basis -- the Cholesky pivot w11 - l21^2 cancels by cond(W), the entries of
      L^-1 P_k L^-T by cond(P_k) on top, and the Jacobi angle's own error only moves the form by (l1 - l2) d(angle), which the
