@@ -200,13 +200,60 @@ def galaxy_source_like(th, Z_s, images, check_overlap=True, unconstrained=True, 
     return float(_source_like_batch(np.asarray(th, dtype=np.float64)[None, :], Z_s, images, limits)[0])
 
 
-def galaxy_source_like_grad(th, Z_s, images, check_overlap=True, unconstrained=False, limits=None):
+def _source_like_grad_analytic(th, Z_s, images, limits=None):
+    """the true gradient of galaxy_source_like in th: one gradient-form launch per image (mode 2, a type-2 proposal as
+    _source_like_batch builds it), then the host chain from (W00, W01, W11) to (sigma, phi, rho) and from counts to fluxes"""
+    theta_s, sig_s, phi_s, rho_s = th[0:4]
+    grad = np.zeros(11)
+    typ = np.full(1, 2, dtype=np.int32)
+    for n, img in enumerate(images):
+        box, Z = _patch_limits(Z_s[n], img, None if limits is None else limits[n])
+        iset, pos = _celeste._image_subset((img,))
+        k = pos[0]
+        R = gen_galaxy_transformation(sig_s, rho_s, phi_s, img.Ups_n)                # constant CD: W has no location term
+        counts = np.zeros((1, iset.B))
+        ratio = img.kappa / img.calib
+        counts[0, k] = (th[6 + BANDS.index(img.band)] / img.calib) * img.kappa
+        boxes = np.zeros((iset.B, 4), dtype=np.int32)
+        boxes[k] = box
+        patches = [None] * iset.B
+        patches[k] = Z
+        sset = iset._sources(typ, th[None, 4:6], counts, np.array([_prof_shape(theta_s, R)]))
+        _, g_u, g_c, g_sh = iset.patch_loglik_grad(sset, boxes, patches, mode=2)
+        gW = g_sh[0, 1:4]                                                           # d / d (W00, W01, W11); W01 counts both places
+        # R = Ups^-1 G(sigma, phi, rho) (gen_galaxy_ra_dec_basis), W = R R^T: dW = dR R^T + R dR^T
+        D = np.linalg.inv(img.Ups_n)
+        phi = (90. - phi_s) * np.pi / 180.
+        re_deg = max(1. / 30, sig_s) / 3600.
+        cp, sp = np.cos(phi), np.sin(phi)
+        dR = [R / sig_s if sig_s > 1. / 30 else np.zeros((2, 2)),                   # the floor max(1/30, sigma)
+              np.dot(D, re_deg * np.array([[-sp, cp * rho_s], [-cp, -sp * rho_s]])) * (-np.pi / 180.),
+              np.dot(D, re_deg * np.array([[0., sp], [0., cp]]))]
+        grad[0] += g_sh[0, 0]
+        for i, d in enumerate(dR):
+            dW = np.dot(d, R.T) + np.dot(R, d.T)
+            grad[1 + i] += gW[0] * dW[0, 0] + gW[1] * dW[0, 1] + gW[2] * dW[1, 1]
+        grad[4:6] += g_u[0]
+        grad[6 + BANDS.index(img.band)] += g_c[0, k] * ratio
+    return grad
+
+
+def galaxy_source_like_grad(th, Z_s, images, check_overlap=True, unconstrained=False, limits=None, analytic=False):
     """gradient of galaxy_source_like in th  -- celeste_galaxy_conditionals.py:44-88: analytic in theta
     and the fluxes, central differences (step 1e-5) in sigma, phi, rho, ra, dec.  The analytic terms
     are the reference's as written (:63-67: they use the flux in nanomaggies where the image flux in
     counts belongs; documented quirk).  The ten finite-difference likelihoods of an
-    image are ONE device launch."""
+    image are ONE device launch.
+
+    analytic=True: the TRUE gradient of galaxy_source_like in th = [theta, sigma, phi, rho, ra, dec, b_u .. b_z], from the
+    device's gradient form (cel_patch_loglik, mode 8 + 2; k_patch_grad.h): one launch per image, no differences.  The chain
+    from W to (sigma, phi, rho) goes through gen_galaxy_transformation(sig, rho, phi, img.Ups_n) -- the constant-CD route, so W
+    has no location term -- with d / d sigma = 0 under the floor max(1/30, sigma); counts to fluxes is kappa / calib, summed
+    over the images of a band.  This form does NOT reproduce Q12: its theta and flux entries are the derivatives of the value,
+    not the reference's mis-scaled terms."""
     th = np.asarray(th, dtype=np.float64)
+    if analytic:
+        return _source_like_grad_analytic(th, Z_s, images, limits)
     theta_s, sig_s, phi_s, rho_s = th[0:4]
     u_s = th[4:6]
     bs = dict(zip(BANDS, th[-5:]))

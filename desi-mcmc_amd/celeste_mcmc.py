@@ -603,6 +603,31 @@ class ModelGibbs(object):
                 ll += self._exact_terms(f, idx, pc)
         return ll
 
+    def location_loglik_grad(self, idx, U, typ=None, shape=None):
+        """location_loglik with its analytic gradient in (ra, dec), per degree, summed over fields (the gradient form of
+        cel_patch_loglik_multi against the resident patches) -> (ll[P], g[P, 2]); ll is location_loglik's value, bit for bit.
+        The exact conditional's mass term has no derivative here: conditional="exact" raises."""
+        from . import field as _field
+        if self.conditional == "exact":
+            raise ValueError("location_loglik_grad: the exact conditional's stamp-mass term has no analytic derivative yet "
+                             "(conditional='reference' only)")
+        idx = np.asarray(idx, dtype=np.int64)
+        P = idx.shape[0]
+        ll, g = np.zeros(P), np.zeros((P, 2))
+        typ = self.typ[idx] if typ is None else np.ascontiguousarray(typ, dtype=np.int32)
+        shape = self.shape[idx] if shape is None else np.asarray(shape, dtype=np.float64).reshape(P, 4)
+        owner = idx.astype(np.int32)
+        for f in self.fields:
+            if f.prop is None or f.prop.capacity < P:
+                f.prop = _field.SourceSet(f.iset.ctx, max(2 * self.S, P, 16), f.iset.B)
+            cts = getattr(f, "_counts", None)
+            pc = self.counts(f, idx=idx) if cts is None else cts[idx]
+            f.prop.set(typ, U, pc, shape)
+            l, gr, _, _ = f.iset.patch_loglik_resident_grad(f.prop, owner)
+            ll += l
+            g += gr
+        return ll, g
+
     def _exact_terms(self, f, sel, pc):
         """what turns Source.log_likelihood's value for the proposals in f.prop (chains `sel`, expected photons `pc`) into the
         exact conditional: -counts * (the proposal's stamp mass on its own box) in place of -counts * sum(psf weights) where

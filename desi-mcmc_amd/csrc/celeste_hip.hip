@@ -99,6 +99,7 @@ static int fail(int code, const char *fmt, ...) {
 #include "k_type_move.h"
 #include "k_estep.h"
 #include "k_grad.h"
+#include "k_patch_grad.h"
 #include "k_split.h"
 #include "k_slice.h"
 
@@ -125,8 +126,8 @@ enum ScratchSlot {
     SCR_OFFSETS,      // cel_patch_loglik_multi, cel_photon_split: a caller's patch offsets
     SCR_VALUES,       // cel_patch_loglik_multi: the jobs' sums; cel_photon_split: the noise partials; cel_stamp_mass_begin: the masses (PENDING)
     SCR_PATCH_DATA,   // cel_patch_loglik_multi, cel_photon_split: a caller's patch pixels, staged; cel_samples_fetch: sums the split did not form
-    SCR_TMP_A,        // cel_render_stamps: jobs; cel_estep_stats: xtilde; cel_loglik_grad: sums; cel_mog_loglike: components; cel_galaxy_mixture_params: inputs
-    SCR_TMP_B,        // cel_render_stamps: boxes; cel_estep_stats: masses; cel_loglik_grad: staged gradients; cel_mog_loglike: points; cel_galaxy_mixture_params: outputs
+    SCR_TMP_A,        // cel_render_stamps: jobs; cel_estep_stats: xtilde; cel_loglik_grad: sums; cel_patch_loglik_multi (gradient form): the parts' sums; cel_mog_loglike: components; cel_galaxy_mixture_params: inputs
+    SCR_TMP_B,        // cel_render_stamps: boxes; cel_estep_stats: masses; cel_loglik_grad: staged gradients; cel_patch_loglik_multi (gradient form): the 7 + B rows; cel_mog_loglike: points; cel_galaxy_mixture_params: outputs
     SCR_TMP_C,        // cel_render_stamps: offsets; cel_estep_stats: per-entry sums; cel_mog_loglike: outputs; cel_flux_conditionals, cel_gamma_streams: inputs + outputs
     SCR_HOST_IO,      // cel_sources_set_rows: the staged rows; cel_render_stamps: the stamps on their way to the host
     SCR_COUNT
@@ -1600,13 +1601,18 @@ int cel_render_stamps(cel_images *im, cel_sources *src, int band, int scaled, co
 }
 
 // ---- per-source conditional log-likelihoods ---------------------------------------------------
+static const int CEL_PLL_GRAD = 8;      // mode = CEL_PLL_GRAD + m: the gradient form (celeste_hip.h names it in cel_patch_loglik's comment)
 int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owner, int64_t NB,
-                           const int32_t *boxes, const int64_t *offsets, const double *data, int mem, int mode,
+                           const int32_t *boxes, const int64_t *offsets, const double *data, int mem, int mode_arg,
                            double *ll_out) {
     if (!im || !src || !ll_out) return fail(CEL_ERR_INVALID, "cel_patch_loglik: null argument");
     if (src->B != im->B || src->ctx != im->ctx) return fail(CEL_ERR_INVALID, "sources do not match images");
+    // the gradient form CEL_PLL_GRAD + m, m in {0, 1, 2}: every check below is mode m's, the value in slot 0 is mode m's path
+    const bool grad = (mode_arg >= CEL_PLL_GRAD && mode_arg <= CEL_PLL_GRAD + 2);
+    const int mode = grad ? mode_arg - CEL_PLL_GRAD : mode_arg;
     if (mode != 0 && mode != 1 && mode != 2 && mode != 4)
-        return fail(CEL_ERR_INVALID, "mode must be 0 (conditional), 1 (isolated), 2 (patch Poisson) or 4 (Poisson on a background plane)");
+        return fail(CEL_ERR_INVALID, "mode must be 0 (conditional), 1 (isolated), 2 (patch Poisson), 4 (Poisson on a background plane) "
+                                     "or 8 + (0, 1, 2) (the gradient form)");
     // resident form: boxes == offsets == data == NULL -> the patches of the last resident photon
     // split (mode 0) or the observed image on those boxes (mode 1); NB must be that split's S
     const bool resident = (!boxes && !offsets && !data);
@@ -1620,6 +1626,8 @@ int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owne
                     (long long)NB, (long long)im->split.samp_S);
     if (NB < 1 || (NB > 1 && !owner)) return fail(CEL_ERR_INVALID, "cel_patch_loglik: NB patch sets need an owner array");
     if (resident && mode == 1 && !im->have_nelec) return fail(CEL_ERR_INVALID, "the isolated form needs cel_images_set_nelec");
+    if (grad && (im->win_y0 != 0 || im->full_H != im->H))
+        return fail(CEL_ERR_INVALID, "cel_patch_loglik (gradient form): an image set with a row window (cel_images_set_window) is not supported");
     cel_ctx *c = im->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const int B = im->B;
@@ -1653,7 +1661,7 @@ int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owne
     const bool nzl = resident && mode == 0 && c->variant != 0 && im->split.nz_valid;
     const int nsplit = (c->variant != 0 && mode == 0 && P * B <= 8192) ? PLL_PARTS : 1;
     const int nparts = nzl ? PLL_PARTS : nsplit;
-    std::vector<double> hout((size_t)(P * B * nparts));
+    std::vector<double> hout((size_t)(P * B * nparts)), val((size_t)(grad ? P : 0));
     int4 *d_nz = nullptr;
     // one block: a caller's boxes, their photon rectangles, the owners
     auto carve = [&](char *base) {
@@ -1740,8 +1748,39 @@ int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owne
             for (int k = 1; k < nparts; k++) x += q[k];     // a job's parts first, in order (as k_slice_step does)
             s += x;
         }
-        ll_out[p] = s;
+        if (grad) val[(size_t)p] = s;                       // slot 0 of the gradient form, written once its sums are in
+        else ll_out[p] = s;
     }
+    if (!grad) return CEL_OK;
+    // ---- the gradient form (k_patch_grad.h): the same records, boxes, offsets, owners and staged data, still in their slots
+    double *d_sums = nullptr, *d_grad = nullptr;
+    const size_t ng = (size_t)P * (7 + B);
+    if ((rc = scratch_get(c, SCR_TMP_A, sizeof(double) * GRAD_NS * PGRAD_PARTS * (size_t)(P * B), (void **)&d_sums)) ||
+        (rc = scratch_get(c, SCR_TMP_B, sizeof(double) * ng, (void **)&d_grad)))
+        return rc;
+    {
+        int pi = prof_begin(c, CEL_K_PATCH_LL);
+        const dim3 grid((unsigned)(P * B * PGRAD_PARTS));
+        const int *i_data = (resident && mode == 0) ? (const int *)im->d_samp : nullptr;
+#define PGRAD_LAUNCH(M, TZ, DATA)                                                                                              \
+        hipLaunchKernelGGL((k_patch_grad<M, TZ>), grid, dim3(64), 0, c->stream, im->d_bands, B, P, im->d_recs, (const int *)d_owner, \
+                           (const int4 *)d_box, (const int64_t *)d_off, (const TZ *)(DATA), (const double *)im->d_nelec, im->H, im->W, d_sums)
+        if (i_data) PGRAD_LAUNCH(0, int, i_data);
+        else if (mode == 0) PGRAD_LAUNCH(0, double, d_data);
+        else if (mode == 1) PGRAD_LAUNCH(1, double, d_data);
+        else PGRAD_LAUNCH(2, double, d_data);
+#undef PGRAD_LAUNCH
+        hipLaunchKernelGGL(k_patch_grad_chain, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, c->stream, im->d_bands, B, P, im->d_recs,
+                           (const int *)d_owner, (const int4 *)d_box, (const int *)src->d_type, (const double *)src->d_shape,
+                           (const double *)src->d_counts, (const double *)d_sums, mode, d_grad);
+        prof_end(c, pi);
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<double> hg(ng);
+    HIP_TRY(hipMemcpyAsync(hg.data(), d_grad, sizeof(double) * ng, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int64_t p = 0; p < P; p++) hg[(size_t)p * (7 + B)] = val[(size_t)p];
+    memcpy(ll_out, hg.data(), sizeof(double) * ng);
     return CEL_OK;
 }
 

@@ -664,6 +664,66 @@ class ImageSet(object):
                                                data.ctypes.data, L.CEL_HOST, 1 if isolated else 0, L.dptr(out)))
         return out
 
+    # ---- the gradient form of the conditional log-likelihoods: cel_patch_loglik[_multi](mode = CEL_PLL_GRAD + m) --------
+    def _split_grad(self, flat, P):
+        """the P * (7 + B) doubles of the gradient form -> (ll[P], g_radec[P,2], g_counts[P,B], g_shape[P,4])"""
+        g = flat.reshape(P, 7 + self.B)
+        return g[:, 0].copy(), g[:, 1:3].copy(), g[:, 7:].copy(), g[:, 3:7].copy()
+
+    def patch_loglik_multi_grad(self, sources, owner, boxes, patches, isolated=False, mode=None):
+        """patch_loglik_multi and its analytic gradient on the FIXED patch limits (k_patch_grad.h): mode 0 (conditional), 1
+        (isolated) or 2 (patch Poisson); `isolated` means mode 1 when no mode is given.
+        -> (ll[P], g_radec[P,2] per degree, g_counts[P,B], g_shape[P,4]) in loglik_grad's units and conventions; ll is the plain
+        call's value, bit for bit.  Nothing is dropped in the gradient whatever the tail options say."""
+        m = (1 if isolated else 0) if mode is None else int(mode)
+        if m == 1:
+            self._refuse_masked("patch_loglik_multi(isolated=True)")
+        boxes = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, self.B, 4)
+        NB = boxes.shape[0]
+        owner = np.ascontiguousarray(owner, dtype=np.int32)
+        if owner.shape != (sources.S,):
+            raise ValueError("owner must have one entry per proposal")
+        offs = np.zeros(NB * self.B + 1, dtype=np.int64)
+        flat = []
+        for o in range(NB):
+            for b in range(self.B):
+                y0, y1, x0, x1 = boxes[o, b]
+                n = int(y1 - y0) * int(x1 - x0) if (y1 > y0 and x1 > x0) else 0
+                if n:
+                    p = L.f64(patches[o][b])
+                    if p.shape != (y1 - y0, x1 - x0):
+                        raise ValueError("set %d band %d: patch shape %s does not match its box" % (o, b, p.shape))
+                    flat.append(p.ravel())
+                offs[o * self.B + b + 1] = offs[o * self.B + b] + n
+        data = np.concatenate(flat) if flat else np.zeros(1)
+        out = np.zeros(sources.S * (7 + self.B))
+        L.check(L.lib().cel_patch_loglik_multi(self._h, sources._h, owner.ctypes.data_as(L.c_int32_p), NB,
+                                               boxes.ctypes.data_as(L.c_int32_p), offs.ctypes.data_as(L.c_int64_p),
+                                               data.ctypes.data, L.CEL_HOST, L.CEL_PLL_GRAD + m, L.dptr(out)))
+        return self._split_grad(out, sources.S)
+
+    def patch_loglik_grad(self, sources, boxes, patches, mode=0):
+        """patch_loglik(mode=...) of each of the P proposals in `sources` on ONE source's fixed patches, with its analytic
+        gradient (cel_patch_loglik, mode = CEL_PLL_GRAD + mode; mode 0, 1 or 2).  boxes (B,4) y0,y1,x0,x1; patches: B arrays or None.
+        -> (ll[P], g_radec[P,2], g_counts[P,B], g_shape[P,4])"""
+        boxes = np.ascontiguousarray(boxes, dtype=np.int32).reshape(1, self.B, 4)
+        return self.patch_loglik_multi_grad(sources, np.zeros(sources.S, dtype=np.int32), boxes, [patches], mode=mode)
+
+    def patch_loglik_resident_grad(self, proposals, owner, isolated=False):
+        """patch_loglik_resident and its analytic gradient: against the resident sample patches (isolated=True: against the
+        observed image on the same boxes).  -> (ll[P], g_radec[P,2], g_counts[P,B], g_shape[P,4])"""
+        if isolated:
+            self._refuse_masked("patch_loglik_resident(isolated=True)")
+        owner = np.ascontiguousarray(owner, dtype=np.int32)
+        if owner.shape != (proposals.S,):
+            raise ValueError("owner must have one entry per proposal")
+        S, tot = C.c_int64(0), C.c_int64(0)
+        L.check(L.lib().cel_samples_info(self._h, C.byref(S), C.byref(tot)))
+        out = np.zeros(proposals.S * (7 + self.B))
+        L.check(L.lib().cel_patch_loglik_multi(self._h, proposals._h, owner.ctypes.data_as(L.c_int32_p), S.value, None, None, None,
+                                               L.CEL_DEVICE, L.CEL_PLL_GRAD + (1 if isolated else 0), L.dptr(out)))
+        return self._split_grad(out, proposals.S)
+
     def stamp_boxes(self, sources, band):
         S = sources.S
         boxes = np.zeros((S, 4), dtype=np.int32)

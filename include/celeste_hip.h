@@ -402,7 +402,36 @@ int cel_render_stamps(cel_images *img, cel_sources *src, int band, int scaled, c
  *            against background + model, the image_like closure of the star <-> galaxy move
  *            (CelestePy/sources.py:6-12,277-291).  Each band's patch data is TWO planes, z then bg
  *            (offsets[b+1]-offsets[b] = 2 x box area); a NaN z marks a masked pixel (invvar == 0); negative counts are data
- *   ll_out   P doubles (host) */
+ *   ll_out   P doubles (host)
+ *
+ *   mode 8 + m, m in {0, 1, 2}  -- CEL_PLL_GRAD = 8, a value of `mode` and no enumerator: THE GRADIENT FORM of mode m.  Boxes,
+ *            offsets (ONE plane per band, as in
+ *            mode m: offsets sized for 7 + B planes are refused), data, mem, owner, NB and the resident form (m = 0 or 1)
+ *            keep their meaning; ONLY THE SIZE OF ll_out CHANGES:
+ *   ll_out   P * (7 + B) doubles (host).  Per proposal p, at ll_out + p * (7 + B):
+ *              0        the value the same call with mode = m returns, bit for bit (that path is run)
+ *              1, 2     d / d ra, d / d dec, per degree
+ *              3 .. 6   type 1: d / d (theta, sigma [arcsec], phi [degrees], rho); type 2: d / d (theta, W00, W01, W11);
+ *                       stars: zeros
+ *              7 + b    d / d counts[p][b]
+ *            Slots 1 .. 6 are summed over the bands in band order.  The gradient is that of the value documented for mode m
+ *            on the FIXED patch limits (no integer box of the source enters).  With u the unit stamp, m(pix) = counts_b u(pix)
+ *            and dq = d u / d q, a location or shape entry is sum_b counts_b sum_pix r dq and the counts entry sum_pix r u, with
+ *              m = 0:  r = z / m where m > 0, else 0; the counts entry gets a further - sum(psf weights_b)
+ *              m = 1:  r = z / (m + eps_b) - 1
+ *              m = 2:  r = z / m - 1 where m > 0, else 0
+ *            (a pixel with m == 0 adds nothing: no 0 / 0, every output finite whenever the value is).  Conventions are
+ *            cel_loglik_grad's: ra / dec act through equa2pixel and, for type 1, through cd_at_pixel's cos(dec) term in W;
+ *            d / d sigma is 0 where the floor max(1/30, sigma) holds; d / d theta keeps both profiles.  A band with an empty
+ *            patch contributes nothing; a source whose own box is empty still renders its kind, and its derivatives, on the
+ *            imposed limits; an overlap-test miss contributes only - sum(psf weights_b) to its counts entry for m = 0 and
+ *            renders as a star for m = 1, 2, as the value does.
+ *            Slot 0 and slots 1 .. differ by the drop rule: slot 0 carries whatever rule mode m applies under
+ *            CEL_OPT_TAIL_LOG[_SOURCE] and CEL_OPT_KERNEL; the gradient kernel (k_patch_grad.h) reads neither option, drops
+ *            nothing (every component at every pixel) and gives the same bits under CEL_OPT_KERNEL 0 and 1 and on every call.
+ *            Refused with CEL_ERR_INVALID before anything is launched or written: whatever mode m refuses for the same
+ *            arguments; 8 + 3, 8 + 4 and any other value; an image set with a row window (cel_images_set_window), as
+ *            cel_loglik_grad refuses it.  The launches are timed under CEL_K_PATCH_LL. */
 int cel_patch_loglik(cel_images *img, cel_sources *src, const int32_t *boxes, const int64_t *offsets,
                      const double *data, int mem, int mode, double *ll_out);
 /* The same for proposals of MANY sources in one launch (a whole sweep of per-source updates):
