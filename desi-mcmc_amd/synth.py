@@ -63,9 +63,10 @@ def make_sources(S, H, W, bands, frac_gal=0.5, seed=42):
 class SyntheticField(object):
     """A device-resident synthetic field: .images (ImageSet), .sources (SourceSet), .src (host dict)."""
 
-    def __init__(self, ctx, S, B, H, W, frac_gal=0.5, seed=42, with_nelec=True):
+    def __init__(self, ctx, S, B, H, W, frac_gal=0.5, seed=42, with_nelec=True, bands=None):
         self.S, self.B, self.H, self.W = S, B, H, W
-        self.bands = make_bands(H, W, B)
+        # bands: the caller's own (B, 37) records (another WCS, say) in place of make_bands'
+        self.bands = make_bands(H, W, B) if bands is None else np.array(bands, dtype=np.float64).reshape(B, -1)
         self.src = make_sources(S, H, W, self.bands, frac_gal, seed)
         self.images = _field.ImageSet(ctx, self.bands, H, W)
         self.sources = _field.SourceSet(ctx, max(S, 1), B).set(self.src["type"], self.src["radec"],

@@ -32,6 +32,11 @@ real_fields.npz    configs 1 / 4 on EVERY real field the reference ships (data/s
                    data/galaxy_stamps 25, data/real 1 = 100 fields, 500 images, 221 catalogue sources): FitsImage
                    records + nelec, the catalogue as util/misc/init_utils.py:42-60 loads it, gen_model_image,
                    celeste_likelihood[_multi_image], every source's box, star stamps and gen_galaxy_psf_image patches
+general_wcs.npz    the rotated, sheared, per-band WCS of tests/_general_wcs.py (CRPIX off the frame, dec 87) on a virtual
+                   96x112 frame, 3 bands: FitsImage records, equa2pixel / pixel2equa / cd_at_pixel samples,
+                   gen_galaxy_transformation, star and galaxy patches + boxes (edges, overlap test, sigma floor, a thin galaxy
+                   at 45 degrees to the rotated axes), a 14-source mixed field (`python make_golden.py general_wcs` writes
+                   this file alone)
 """
 import os
 import sys
@@ -85,12 +90,14 @@ def stack_bands(imgs):
     return {k: np.array([r[k] for r in recs], dtype=np.float64) for k in recs[0]}
 
 
-def virtual_images(name, H, W, nelec=None, field=FIELD):
+def virtual_images(name, H, W, nelec=None, field=FIELD, wcs=None):
     """Reference FitsImage objects for a synthetic H x W frame per band.
 
     Header = the real stamp's header with NAXIS/CRPIX moved to the frame centre
     (SURVEY 8d); pixel data chosen so that the reference's own
     ``round((img/CALIB + SKY) * GAIN)`` reproduces ``nelec`` exactly.
+    wcs: optional per-band dicts of header cards (CD*_*, CRPIX*, CRVAL*) that
+    replace the stamp's; nelec may then hold fewer than five bands (the rest: zeros).
     """
     imgs = []
     for bi, b in enumerate(BANDS):
@@ -98,7 +105,10 @@ def virtual_images(name, H, W, nelec=None, field=FIELD):
         hdr = dict(hdr)
         hdr["NAXIS1"], hdr["NAXIS2"] = W, H
         hdr["CRPIX1"], hdr["CRPIX2"] = W / 2.0 + 1.0, H / 2.0 + 1.0
-        ne = np.zeros((H, W)) if nelec is None else nelec[bi]
+        if wcs is not None:
+            assert set(wcs[bi]) <= {"CD1_1", "CD1_2", "CD2_1", "CD2_2", "CRPIX1", "CRPIX2", "CRVAL1", "CRVAL2"}
+            hdr.update(wcs[bi])
+        ne = np.zeros((H, W)) if nelec is None or bi >= len(nelec) else nelec[bi]
         pix = (ne / hdr["GAIN"] - hdr["SKY"]) * hdr["CALIB"]
         _refload.VIRTUAL_FITS["virt:%s-%s" % (name, b)] = (hdr, pix)
     tmpl = "virt:" + name + "-%s"
@@ -106,7 +116,7 @@ def virtual_images(name, H, W, nelec=None, field=FIELD):
         im = ref_fits.FitsImage(b, fits_file_template=tmpl)
         imgs.append(im)
     if nelec is not None:
-        for bi, im in enumerate(imgs):
+        for bi, im in enumerate(imgs[:len(nelec)]):
             assert np.array_equal(im.nelec, nelec[bi]), "nelec round trip failed"
     return imgs
 
@@ -703,7 +713,117 @@ def gen_src_bound(imgs):
          pixel_grid=grid, grid_HW=np.array([H, W]))
 
 
+def gen_general_wcs():
+    """general_wcs.npz: the reference on a 96 x 112 frame, 3 bands, under the rotated, sheared, per-band WCS of
+    tests/_general_wcs.py (CRPIX off the frame, dec 87): WCS samples, gen_galaxy_transformation, star and galaxy patches with
+    their boxes, and a 14-source mixed field.  Patches and model images are stored subsampled (every `stride`-th pixel both
+    ways) with their full sums / log-likelihoods, to stay small."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import _general_wcs as gw
+    H, W, NB = gw.FIX_H, gw.FIX_W, gw.FIX_B
+    hdrs = [gw.general_header(H, W, b) for b in range(5)]
+    imgs = virtual_images("gwcs0", H, W, wcs=hdrs)[:NB]
+    out = stack_bands(imgs)
+    out.update(H=np.array(H), W=np.array(W))
+    # -- WCS samples: 15 points, some off the frame
+    rs = np.random.RandomState(17)
+    pix = np.vstack([np.column_stack([rs.uniform(-25, W + 25, 12), rs.uniform(-25, H + 25, 12)]),
+                     [[0.0, 0.0], [W - 1.0, H - 1.0], [55.5, 47.5]]])
+    out["w_pix"] = pix
+    out["w_equa"] = np.array([[im.pixel2equa(p) for p in pix] for im in imgs])
+    out["w_pix_back"] = np.array([[im.equa2pixel(u) for u in row] for im, row in zip(imgs, out["w_equa"])])
+    out["w_cd"] = np.array([[im.cd_at_pixel(p[0], p[1]) for p in pix] for im in imgs])
+    # -- gen_galaxy_transformation: 6 shapes at 3 positions, every band
+    t_shapes = np.vstack([GAL_SHAPES[:6], [[0.5, 2.0, 102.0, 0.15]]])[[0, 1, 2, 3, 5, 6]]
+    t_pix = np.array([[50.3, 40.7], [3.5, 90.0], [130.0, -12.5]])
+    out["t_shapes"], out["t_pix"] = t_shapes, t_pix
+    out["t_tinv"] = np.array([[[ref_gal.gen_galaxy_transformation(th[1], th[3], th[2], im.cd_at_pixel(p[0], p[1]))
+                                for th in t_shapes] for p in t_pix] for im in imgs])
+    # -- stars: interior, every frame edge, both sides of the overlap test (celeste.py:130-132), positions named in band 0
+    s_pix = np.array([[50.3, 40.7], [20.5, 70.2], [1.2, 48.0], [110.6, 30.3], [60.0, 0.4], [55.5, 95.2],
+                      [-46.0, 40.0], [-55.0, 40.0], [-50.8, 40.0], [30.0, -46.0], [30.0, -55.0], [189.0, 50.0], [196.0, 50.0]])
+    s_u = np.array([imgs[0].pixel2equa(p) for p in s_pix])
+    st_stride = 2
+    st_band, st_idx, st_none, st_box, st_patch, st_sum = [], [], [], [], [], []
+    for bi, im in enumerate(imgs):
+        for i, u in enumerate(s_u):
+            patch, yl, xl = ref_cel.gen_point_source_psf_image(u, im)
+            st_band.append(bi); st_idx.append(i); st_none.append(int(patch is None))
+            if patch is None:
+                st_box.append([0, 0, 0, 0]); st_patch.append(np.zeros((0, 0))); st_sum.append(0.0)
+            else:
+                st_box.append([yl[0], yl[1], xl[0], xl[1]]); st_patch.append(patch[::st_stride, ::st_stride]); st_sum.append(patch.sum())
+    flat, offs, shapes = pack_ragged(st_patch)
+    out.update(s_pix=s_pix, s_u=s_u, st_band=np.array(st_band), st_idx=np.array(st_idx), st_none=np.array(st_none, dtype=np.int8),
+               st_box=np.array(st_box, dtype=np.int64), st_flat=flat, st_offs=offs, st_shapes=shapes, st_sum=np.array(st_sum),
+               st_stride=np.array(st_stride))
+    assert 0 < sum(st_none) < len(st_none)
+    # -- galaxies: 6 in each band; one under the sigma floor, a thin one at 45 degrees to the rotated axes, one cut by a corner
+    g_th = np.array([[0.40, 1.5, 30.0, 0.60], [0.05, 0.5, 0.0, 0.30], [0.95, 1.0, 90.0, 0.90], [0.30, 0.01, 10.0, 0.50],
+                     [0.50, 2.0, 102.0, 0.15], [0.70, 2.5, 45.0, 0.20]])
+    g_pix = np.array([[50.3, 40.7], [20.5, 70.2], [90.1, 20.6], [70.7, 60.3], [40.2, 30.9], [104.5, 88.0]])
+    g_u = np.array([imgs[0].pixel2equa(p) for p in g_pix])
+    ga_stride = 3
+    ga_band, ga_idx, ga_box, ga_patch, ga_sum, ga_tinv, ga_pxy = [], [], [], [], [], [], []
+    for bi, im in enumerate(imgs):
+        for i, (th, u) in enumerate(zip(g_th, g_u)):
+            patch, yl, xl = ref_gal.gen_galaxy_psf_image(th, u, im)
+            px, py, Tinv, _ = galaxy_cmix(th, u, im)
+            ga_band.append(bi); ga_idx.append(i); ga_box.append([yl[0], yl[1], xl[0], xl[1]])
+            ga_patch.append(patch[::ga_stride, ::ga_stride]); ga_sum.append(patch.sum()); ga_tinv.append(Tinv); ga_pxy.append([px, py])
+    flat, offs, shapes = pack_ragged(ga_patch)
+    out.update(g_th=g_th, g_pix=g_pix, g_u=g_u, ga_band=np.array(ga_band), ga_idx=np.array(ga_idx),
+               ga_box=np.array(ga_box, dtype=np.float64), ga_flat=flat, ga_offs=offs, ga_shapes=shapes, ga_sum=np.array(ga_sum),
+               ga_tinv=np.array(ga_tinv), ga_pxy=np.array(ga_pxy), ga_stride=np.array(ga_stride))
+    # -- a 14-source mixed field.  gen_model_image cannot place a galaxy (gen_galaxy_psf_image ignores return_patch): as in
+    #    mini_field.npz the mixed image is the scatter-add of gen_src_image_with_fluxes' own patches (Q3 extension), and the
+    #    star-only catalogue goes through the reference's own gen_model_image / celeste_likelihood
+    rs = np.random.RandomState(29)
+    S = 14
+    f_pix = np.column_stack([rs.uniform(-4, W + 4, S), rs.uniform(-4, H + 4, S)])
+    is_gal = (np.arange(S) % 2 == 1).astype(np.int64)
+    flux = np.exp(rs.uniform(np.log(1.0), np.log(100.0), size=(S, 5)))
+    f_shape = np.column_stack([rs.uniform(0.05, 0.95, S), np.exp(rs.uniform(np.log(0.4), np.log(2.5), S)),
+                               rs.uniform(0.0, 180.0, S), rs.uniform(0.2, 0.95, S)])
+    radec = np.array([imgs[0].pixel2equa(p) for p in f_pix])
+    srcs = [SrcParams(u=radec[s], a=int(is_gal[s]), fluxes=flux[s], theta=f_shape[s, 0], sigma=f_shape[s, 1],
+                      phi=f_shape[s, 2], rho=f_shape[s, 3]) for s in range(S)]
+
+    def render(images):
+        lam, boxes = [], []
+        for img in images:
+            f = np.zeros(img.nelec.shape)
+            for src in srcs:
+                p, yl, xl = ref_cel.gen_src_image_with_fluxes(src, img)
+                y0, y1, x0, x1 = int(yl[0]), int(yl[1]), int(xl[0]), int(xl[1])
+                f[y0:y1, x0:x1] += p
+                boxes.append([y0, y1, x0, x1])
+            lam.append(img.epsilon + f)
+        return np.array(lam), np.array(boxes, dtype=np.int64).reshape(len(images), S, 4)
+
+    lam_true, _ = render(imgs)
+    nelec = np.random.RandomState(31).poisson(lam_true).astype(np.float64)
+    fimgs = virtual_images("gwcs1", H, W, nelec=nelec, wcs=hdrs)[:NB]
+    lam, f_box = render(fimgs)
+    assert np.array_equal(lam, lam_true)
+    ll_band = np.array([np.sum(im.nelec * np.log(l) - l) for im, l in zip(fimgs, lam)])
+    stars = [SrcParams(u=radec[s], a=0, fluxes=dict(zip(BANDS, flux[s]))) for s in range(S) if not is_gal[s]]
+    star_lam = np.array([ref_cel.gen_model_image(stars, im) for im in fimgs])
+    star_ll = np.array([ref_cel.celeste_likelihood(stars, im) for im in fimgs])
+    f_stride = 2
+    assert np.abs(nelec).max() < 2 ** 31
+    out.update(f_pix=f_pix, f_radec=radec, f_is_gal=is_gal, f_flux=flux[:, :NB], f_shape=f_shape, f_nelec=nelec.astype(np.int32),
+               f_lam=lam[:, ::f_stride, ::f_stride], f_ll_band=ll_band, f_box=f_box, f_star_lam=star_lam[:, ::f_stride, ::f_stride],
+               f_star_ll=star_ll, f_stride=np.array(f_stride))
+    save("general_wcs.npz", **out)
+    size, cap = os.path.getsize(os.path.join(HERE, "general_wcs.npz")), os.path.getsize(os.path.join(HERE, "star_stamps.npz"))
+    assert size < cap, (size, cap)
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["general_wcs"]:
+        gen_general_wcs()
+        sys.exit(0)
     if sys.argv[1:] == ["src_bound"]:
         gen_src_bound(ref_images())
         sys.exit(0)
@@ -726,3 +846,4 @@ if __name__ == "__main__":
     gen_slicesample()
     gen_src_bound(imgs)
     gen_real_fields()
+    gen_general_wcs()

@@ -146,6 +146,24 @@ def test_fitsimage_mirror_host_logic(built):
     assert np.array_equal(im.nelec, rec["nelec"][2])
     np.testing.assert_allclose(im.epsilon, rec["eps"][2], rtol=1e-15)
     np.testing.assert_allclose(im.covars, rec["covars"][2], rtol=1e-15)
+    # the same round trip with CD1_2, CD2_1 != 0: the rotated, sheared records of general_wcs.npz (tests/_general_wcs.py), CRPIX
+    # off the frame -- rho, phi, Ups_n, its inverse and the WCS helpers against what the reference made of the same header
+    gg = load_golden("general_wcs.npz")
+    for b in range(len(gg["eps"])):
+        ups = gg["ups"][b]
+        assert ups[0, 1] != 0.0 and ups[1, 0] != 0.0 and ups[0, 1] != ups[1, 0]
+        gh = dict(hdr, CRPIX1=gg["rho"][b][0] + 1.0, CRPIX2=gg["rho"][b][1] + 1.0, CRVAL1=gg["phi"][b][0], CRVAL2=gg["phi"][b][1],
+                  CD1_1=ups[0, 0], CD1_2=ups[0, 1], CD2_1=ups[1, 0], CD2_2=ups[1, 1])
+        im = built.FitsImage.from_header("ugriz"[b], gh, pix)
+        assert np.array_equal(im.Ups_n, ups) and np.array_equal(im.phi_n, gg["phi"][b])
+        np.testing.assert_allclose(im.rho_n, gg["rho"][b], rtol=1e-15)
+        np.testing.assert_allclose(im.Ups_n_inv, gg["ups_inv"][b], rtol=1e-14)
+        np.testing.assert_allclose(im.band_record()[24:36], np.concatenate([gg["rho"][b], gg["phi"][b], ups.ravel(), gg["ups_inv"][b].ravel()]),
+                                   rtol=1e-14)
+        for p, e, pb, cd in zip(gg["w_pix"], gg["w_equa"][b], gg["w_pix_back"][b], gg["w_cd"][b]):
+            np.testing.assert_allclose(im.pixel2equa(p), e, rtol=1e-15)
+            np.testing.assert_allclose(im.equa2pixel(e), pb, rtol=1e-12, atol=1e-10)
+            np.testing.assert_allclose(im.cd_at_pixel(p[0], p[1]), cd, rtol=1e-9, atol=1e-18)
 
 
 def test_flux_conventions_q2(built):

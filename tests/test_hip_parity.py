@@ -790,7 +790,7 @@ def _row_strips_body(cel, ctx, f, H, W, world, frac_gal, rt):
     assert ctx.profile_get("small_stars")[1] == (1 if frac_gal == 0.0 else 0)
     ctx.profile(False)
     lam = f.images.model_images()
-    parts = np.zeros(2)
+    parts = np.zeros(len(llb))
     for r in range(world):
         y0, y1 = dist.strip_rows(H, world, r)
         if y1 <= y0:

@@ -117,12 +117,10 @@ def _param_map(band, typ, radec, shape, orc):
     return np.array([p[0], p[1], 0.0, 0.0, 0.0])
 
 
-def _scene(cel, ctx, seed=7, S=48):
-    """~48 stars and galaxies over 3 bands at 192 x 256: one galaxy below the sigma floor, two of type 2 (theta 0.35 and
-    1); nelec drawn from a catalogue perturbed away from the one the gradient is taken at"""
+def _catalogue(bands, seed=7, S=48):
+    """the scene's catalogue (no device work) and the generator, left where the perturbed catalogue's draws begin"""
     from desi_mcmc_amd import synth
     rs = np.random.RandomState(seed)
-    bands = synth.make_bands(H, W, B)
     pix = np.column_stack([rs.uniform(12, W - 12, S), rs.uniform(12, H - 12, S)])
     typ = (rs.rand(S) < 0.55).astype(np.int32)
     typ[:3] = [1, 2, 2]
@@ -134,6 +132,18 @@ def _scene(cel, ctx, seed=7, S=48):
     shape[(typ == 0)] = 0.0
     counts = np.exp(rs.uniform(np.log(300.0), np.log(3e4), size=(S, B)))
     radec = synth.pixel2equa(bands[0], pix)
+    return dict(pix=pix, typ=typ, shape=shape, counts=counts, radec=radec), rs
+
+
+def _scene(cel, ctx, seed=7, S=48, bands=None):
+    """~48 stars and galaxies over 3 bands at 192 x 256: one galaxy below the sigma floor, two of type 2 (theta 0.35 and
+    1); nelec drawn from a catalogue perturbed away from the one the gradient is taken at.  bands: the band records
+    (synth.make_bands' unless given)"""
+    from desi_mcmc_amd import synth
+    if bands is None:
+        bands = synth.make_bands(H, W, B)
+    cat, rs = _catalogue(bands, seed, S)
+    pix, typ, shape, counts, radec = cat["pix"], cat["typ"], cat["shape"], cat["counts"], cat["radec"]
     # the observed image: a render of the catalogue moved by ~0.3 px and 5 % in counts, with Poisson noise
     radec_t = synth.pixel2equa(bands[0], pix + rs.normal(0, 0.3, (S, 2)))
     iset = cel.ImageSet(ctx, bands, H, W)

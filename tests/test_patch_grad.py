@@ -226,6 +226,10 @@ def _compared(p, col):
 
 @pytest.fixture(scope="module")
 def fd(orc, scene):
+    return _fd_pairs(orc, scene)
+
+
+def _fd_pairs(orc, scene):
     """per mode: (fd_h, fd_h/2) of the oracle's value, (P, 6 + B) each; a coordinate a source does not have stays 0.
     A pair of quotients that disagrees by more than a tenth of test 3's bar, or whose step does not keep the value's last bit
     below that tenth -- both judged from the yardstick alone -- is formed again
@@ -251,7 +255,7 @@ def fd(orc, scene):
                 if _compared(p, col) and (abs(q1[p, col] - q2[p, col]) > 1e-7 * top[col] or last_bit > 1e-7 * top[col]):
                     q1[p, col] = _quotient(orc, scene, mode, p, kind, i, h, True)
                     q2[p, col] = _quotient(orc, scene, mode, p, kind, i, 0.5 * h, True)
-                    again.append((NAMES[p], COORDS[col]))
+                    again.append((scene.get("names", NAMES)[p], COORDS[col]))
         print("mode %d: %d quotient pairs formed in extended precision: %s" % (mode, len(again), again))
         out[mode] = (q1, q2)
     return out

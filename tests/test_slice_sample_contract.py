@@ -103,10 +103,10 @@ def clump_pixels(boxes, pix, sep):
 class Scene(object):
     """a synthetic field with a resident split, the one-row scorer over it and the oracle's runs, each computed once"""
 
-    def __init__(self, cel, B=3, H=128, W=128, clump_sep=None):
+    def __init__(self, cel, B=3, H=128, W=128, clump_sep=None, bands=None):
         from desi_mcmc_amd import synth
         self.cel, self.ctx, self.B = cel, cel.default_context(0), B
-        f = self.f = synth.SyntheticField(self.ctx, S, B, H, W, frac_gal=0.5, with_nelec=clump_sep is None)
+        f = self.f = synth.SyntheticField(self.ctx, S, B, H, W, frac_gal=0.5, with_nelec=clump_sep is None, bands=bands)
         self.src = f.src
         self.clumps = {}
         if clump_sep is not None:

@@ -47,10 +47,11 @@ def orc():
     return oracle
 
 
-def _scene(cel, ctx, seed=7, S=S_BASE):
+def _scene(cel, ctx, seed=7, S=S_BASE, bands=None):
     from desi_mcmc_amd import synth
     rs = np.random.RandomState(seed)
-    bands = synth.make_bands(H, W, B)
+    if bands is None:
+        bands = synth.make_bands(H, W, B)
     pix = np.column_stack([rs.uniform(12, W - 12, S), rs.uniform(12, H - 12, S)])
     typ = (rs.rand(S) < 0.55).astype(np.int32)
     typ[:3] = [1, 2, 2]
@@ -88,6 +89,10 @@ def scene(cel, ctx):
 
 @pytest.fixture(scope="module")
 def jac(ctx, scene):
+    return _jac(ctx, scene)
+
+
+def _jac(ctx, scene):
     """the calls every test shares: the gradient and lambda with nothing dropped, and per band the scaled = 3 and scaled = 2
     planes on the sources' own boxes"""
     iset, sset = scene["iset"], scene["sset"]
