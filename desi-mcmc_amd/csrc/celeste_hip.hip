@@ -450,6 +450,45 @@ static int copy_out(void *dst, const void *src, size_t bytes, int mem, hipStream
     return CEL_OK;
 }
 
+// One launch of k_patch_ll_hw<MODE, TZ>: a field per kernel parameter (k_patch_ll.h describes them) behind bands, B, H and W, which
+// launch_patch_ll takes from the image set.  The defaults are the plain launch's: one block per job, in job order, one value per job.
+template <typename TZ> struct PatchLlJob {
+    int64_t P = 0;
+    const SrcRec *recs = nullptr;
+    const int *owner = nullptr;
+    const int4 *pbox = nullptr;
+    const int64_t *offsets = nullptr;
+    const TZ *data = nullptr;
+    const double *nelec = nullptr;
+    const int4 *nzbox = nullptr;
+    double Tdrop = 0.0, *out = nullptr;
+    const int *job_order = nullptr;
+    int nsplit = 1;
+    const int *job_count = nullptr, *nzmode = nullptr;
+    int encoded = 0, ostride = 0;
+};
+// the usual job: P proposals on the patches their owners name, against the observed image
+template <typename TZ> static PatchLlJob<TZ> patch_ll_job(const cel_ctx *c, const cel_images *im, int64_t P, const int *owner, double *out,
+                                                          const int4 *pbox, const int64_t *offsets, const TZ *data) {
+    PatchLlJob<TZ> j;
+    j.P = P; j.recs = im->d_recs; j.owner = owner; j.pbox = pbox; j.offsets = offsets; j.data = data; j.nelec = im->d_nelec;
+    j.Tdrop = c->tail_T; j.out = out;
+    return j;
+}
+// `pi`: a profile slot (prof_slot) whose event pair rides on the dispatch, or -1
+template <int MODE, typename TZ>
+static void launch_patch_ll(cel_ctx *c, const cel_images *im, const PatchLlJob<TZ> &j, int64_t blocks, hipStream_t st, int pi = -1) {
+    LAUNCH_EV((k_patch_ll_hw<MODE, TZ>), dim3((unsigned)blocks), dim3(64), st, EV0(c, pi), EV1(c, pi), (const BandDev *)im->d_bands, im->B,
+              j.P, j.recs, j.owner, j.pbox, j.offsets, j.data, j.nelec, im->H, im->W, j.nzbox, j.Tdrop, j.out, j.job_order, j.nsplit,
+              j.job_count, j.nzmode, j.encoded, j.ostride);
+}
+// the stamp-mass form (MODE 3): P sources' unit stamps summed over their own boxes, a block per (source, band) job or entry of `jobs`
+static void launch_stamp_mass(cel_ctx *c, const cel_images *im, int64_t P, const int *owner, double *out, int64_t blocks, const int *jobs = nullptr) {
+    PatchLlJob<double> j;
+    j.P = P; j.recs = im->d_recs; j.owner = owner; j.Tdrop = c->tail_T; j.out = out; j.job_order = jobs;
+    launch_patch_ll<3>(c, im, j, blocks, c->stream);
+}
+
 extern "C" {
 
 int cel_abi_version(void) { return CEL_ABI_VERSION; }
@@ -1602,20 +1641,34 @@ int cel_render_stamps(cel_images *im, cel_sources *src, int band, int scaled, co
 
 // ---- per-source conditional log-likelihoods ---------------------------------------------------
 static const int CEL_PLL_GRAD = 8;      // mode = CEL_PLL_GRAD + m: the gradient form (celeste_hip.h names it in cel_patch_loglik's comment)
-int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owner, int64_t NB,
-                           const int32_t *boxes, const int64_t *offsets, const double *data, int mem, int mode_arg,
-                           double *ll_out) {
+// cel_patch_loglik_multi in steps.  What its checks settle, then where its staging puts things:
+struct PllCall {
+    int mode = 0;                                   // 0, 1, 2 or 4
+    bool grad = false;                              // the gradient form CEL_PLL_GRAD + mode
+    bool resident = false, nzl = false;             // the resident split's patches, not a caller's; their photon lists take part
+    int64_t P = 0, nb = 0;                          // proposals; (patch set, band) boxes
+    std::vector<int4> hbox;                         // a caller's boxes as the kernels read them: x0, x1, y0, y1
+    int nsplit = 1, nparts = 1;                     // blocks per dense job; slots per job in d_out
+    int4 *d_box = nullptr, *d_nz = nullptr;
+    int64_t *d_off = nullptr;
+    int *d_owner = nullptr;
+    double *d_data = nullptr, *d_out = nullptr;
+    const int *i_data = nullptr;                    // the resident split's int32 photon counts (mode 0); everything else is double
+};
+// step 1: the argument checks and the boxes.  k.P == 0 with CEL_OK: nothing to score.
+static int pll_check(cel_images *im, cel_sources *src, const int32_t *owner, int64_t NB, const int32_t *boxes,
+                     const int64_t *offsets, const double *data, int mode_arg, const double *ll_out, PllCall &k) {
     if (!im || !src || !ll_out) return fail(CEL_ERR_INVALID, "cel_patch_loglik: null argument");
     if (src->B != im->B || src->ctx != im->ctx) return fail(CEL_ERR_INVALID, "sources do not match images");
     // the gradient form CEL_PLL_GRAD + m, m in {0, 1, 2}: every check below is mode m's, the value in slot 0 is mode m's path
-    const bool grad = (mode_arg >= CEL_PLL_GRAD && mode_arg <= CEL_PLL_GRAD + 2);
-    const int mode = grad ? mode_arg - CEL_PLL_GRAD : mode_arg;
+    const bool grad = k.grad = (mode_arg >= CEL_PLL_GRAD && mode_arg <= CEL_PLL_GRAD + 2);
+    const int mode = k.mode = grad ? mode_arg - CEL_PLL_GRAD : mode_arg;
     if (mode != 0 && mode != 1 && mode != 2 && mode != 4)
         return fail(CEL_ERR_INVALID, "mode must be 0 (conditional), 1 (isolated), 2 (patch Poisson), 4 (Poisson on a background plane) "
                                      "or 8 + (0, 1, 2) (the gradient form)");
     // resident form: boxes == offsets == data == NULL -> the patches of the last resident photon
     // split (mode 0) or the observed image on those boxes (mode 1); NB must be that split's S
-    const bool resident = (!boxes && !offsets && !data);
+    const bool resident = k.resident = (!boxes && !offsets && !data);
     if (!resident && (!boxes || !offsets)) return fail(CEL_ERR_INVALID, "cel_patch_loglik: null boxes / offsets");
     if (resident && mode > 1) return fail(CEL_ERR_INVALID, "the resident form scores mode 0 or 1");
     const int nplanes = (mode == 4) ? 2 : 1;               // mode 4: data plane, then background plane
@@ -1628,13 +1681,12 @@ int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owne
     if (resident && mode == 1 && !im->have_nelec) return fail(CEL_ERR_INVALID, "the isolated form needs cel_images_set_nelec");
     if (grad && (im->win_y0 != 0 || im->full_H != im->H))
         return fail(CEL_ERR_INVALID, "cel_patch_loglik (gradient form): an image set with a row window (cel_images_set_window) is not supported");
-    cel_ctx *c = im->ctx;
-    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(im->ctx->device));
     const int B = im->B;
-    const int64_t P = src->S, nb = NB * B;
+    const int64_t P = k.P = src->S, nb = k.nb = NB * B;
     if (P == 0) return CEL_OK;
     if (!resident && offsets[0] != 0) return fail(CEL_ERR_INVALID, "cel_patch_loglik: offsets[0] must be 0");
-    std::vector<int4> hbox((size_t)(resident ? 0 : nb));
+    k.hbox.resize((size_t)(resident ? 0 : nb));
     for (int64_t i = 0; i < (resident ? 0 : nb); i++) {
         int y0 = boxes[4 * i], y1 = boxes[4 * i + 1], x0 = boxes[4 * i + 2], x1 = boxes[4 * i + 3];
         int64_t area = (y1 > y0 && x1 > x0) ? (int64_t)(y1 - y0) * (x1 - x0) : 0;
@@ -1643,138 +1695,131 @@ int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owne
                         (long long)(i / B), (int)(i % B), (long long)(offsets[i + 1] - offsets[i]), (long long)area, nplanes);
         if (area > 0 && (y0 < 0 || x0 < 0 || y1 > im->H || x1 > im->W))
             return fail(CEL_ERR_INVALID, "patch set %lld band %d: patch limits outside the image", (long long)(i / B), (int)(i % B));
-        hbox[(size_t)i] = make_int4(x0, x1, y0, y1);
+        k.hbox[(size_t)i] = make_int4(x0, x1, y0, y1);
     }
     if (owner)
         for (int64_t p = 0; p < P; p++)
             if (owner[p] < 0 || owner[p] >= NB) return fail(CEL_ERR_INVALID, "owner[%lld] = %d out of range", (long long)p, owner[p]);
     if (!resident && offsets[nb] > 0 && !data) return fail(CEL_ERR_INVALID, "cel_patch_loglik: null data");
-    int rc = run_prep(im, src);
-    if (rc) return rc;
-    int4 *d_box = nullptr;
-    int64_t *d_off = nullptr;
-    int *d_owner = nullptr;
-    double *d_data = nullptr, *d_out = nullptr;
+    return CEL_OK;
+}
+
+// step 2: the scratch slots, the carved block and the uploads -- k's device pointers are set, the copies queued
+static int pll_stage(cel_images *im, const int32_t *owner, const int64_t *offsets, const double *data, int mem, PllCall &k) {
+    cel_ctx *c = im->ctx;
+    const int B = im->B;
+    const int64_t P = k.P, nb = k.nb;
+    const bool resident = k.resident;
     // a call with few proposals is a handful of one-wave jobs as long as their longest: each is dealt to PLL_PARTS blocks
     // (the values do not depend on it: the kernel sums its chunks in PLL_PARTS classes either way)
     // (with photon lists a job always owns PLL_PARTS slots: the kernel that scores at the photons writes its four class sums)
-    const bool nzl = resident && mode == 0 && c->variant != 0 && im->split.nz_valid;
-    const int nsplit = (c->variant != 0 && mode == 0 && P * B <= 8192) ? PLL_PARTS : 1;
-    const int nparts = nzl ? PLL_PARTS : nsplit;
-    std::vector<double> hout((size_t)(P * B * nparts)), val((size_t)(grad ? P : 0));
-    int4 *d_nz = nullptr;
+    k.nzl = resident && k.mode == 0 && c->variant != 0 && im->split.nz_valid;
+    k.nsplit = (c->variant != 0 && k.mode == 0 && P * B <= 8192) ? PLL_PARTS : 1;
+    k.nparts = k.nzl ? PLL_PARTS : k.nsplit;
     // one block: a caller's boxes, their photon rectangles, the owners
     auto carve = [&](char *base) {
-        Carver k{base};
-        d_box = k.take<int4>(resident ? 0 : nb);
-        d_nz = k.take<int4>(resident ? 0 : nb);
-        d_owner = owner ? k.take<int>(P) : nullptr;
-        return k.off;
+        Carver cv{base};
+        k.d_box = cv.take<int4>(resident ? 0 : nb);
+        k.d_nz = cv.take<int4>(resident ? 0 : nb);
+        k.d_owner = owner ? cv.take<int>(P) : nullptr;
+        return cv.off;
     };
     char *d_blk = nullptr;
+    int rc;
     if ((rc = scratch_get(c, SCR_PLL_BOXES, carve(nullptr), (void **)&d_blk)) ||
-        (rc = scratch_get(c, SCR_OFFSETS, sizeof(int64_t) * (nb + 1), (void **)&d_off)) ||
-        (rc = scratch_get(c, SCR_VALUES, sizeof(double) * P * B * nparts, (void **)&d_out)))
+        (rc = scratch_get(c, SCR_OFFSETS, sizeof(int64_t) * (nb + 1), (void **)&k.d_off)) ||
+        (rc = scratch_get(c, SCR_VALUES, sizeof(double) * P * B * k.nparts, (void **)&k.d_out)))
         return rc;
     carve(d_blk);
-    if (owner) HIP_TRY(hipMemcpyAsync(d_owner, owner, sizeof(int) * P, hipMemcpyHostToDevice, c->stream));
+    if (owner) HIP_TRY(hipMemcpyAsync(k.d_owner, owner, sizeof(int) * P, hipMemcpyHostToDevice, c->stream));
     if (resident) {
-        d_nz = im->d_snz;
-        d_box = im->d_sbox;
-        d_off = im->d_soff;
-        d_data = nullptr;                                 // mode 0: the int32 patches (below); mode 1 reads nelec on the boxes
-    } else {
-        HIP_TRY(hipMemcpyAsync(d_box, hbox.data(), sizeof(int4) * nb, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_off, offsets, sizeof(int64_t) * (nb + 1), hipMemcpyHostToDevice, c->stream));
+        k.d_nz = im->d_snz; k.d_box = im->d_sbox; k.d_off = im->d_soff;
+        if (k.mode == 0) k.i_data = im->d_samp;           // mode 0: the int32 patches; mode 1 reads nelec on the boxes
+        return CEL_OK;
     }
-    if (resident) {
-    } else if (mem == CEL_DEVICE) {
-        d_data = const_cast<double *>(data);
-    } else {
-        if ((rc = scratch_get(c, SCR_PATCH_DATA, sizeof(double) * (offsets[nb] > 0 ? offsets[nb] : 1), (void **)&d_data))) return rc;   // (copies are queued: scratch_get fails through HIP_TRY, which drains the device)
-        if (offsets[nb] > 0)
-            HIP_TRY(hipMemcpyAsync(d_data, data, sizeof(double) * offsets[nb], hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(k.d_box, k.hbox.data(), sizeof(int4) * nb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(k.d_off, offsets, sizeof(int64_t) * (nb + 1), hipMemcpyHostToDevice, c->stream));
+    if (mem == CEL_DEVICE) { k.d_data = const_cast<double *>(data); return CEL_OK; }
+    if ((rc = scratch_get(c, SCR_PATCH_DATA, sizeof(double) * (offsets[nb] > 0 ? offsets[nb] : 1), (void **)&k.d_data))) return rc;   // (copies are queued: scratch_get fails through HIP_TRY, which drains the device)
+    if (offsets[nb] > 0) HIP_TRY(hipMemcpyAsync(k.d_data, data, sizeof(double) * offsets[nb], hipMemcpyHostToDevice, c->stream));
+    return CEL_OK;
+}
+
+// step 3: the values, P * B * k.nparts of them in k.d_out
+static void pll_launch_values(cel_images *im, const PllCall &k) {
+    cel_ctx *c = im->ctx;
+    const int B = im->B;
+    const int64_t P = k.P;
+    hipStream_t st = c->stream;
+    if (c->variant == 0) {           // the direct kernel: every mode, one block and one value per job
+        auto direct = [&](auto kernel, auto *z) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)(P * B)), dim3(256), 0, st, im->d_bands, B, P, im->d_recs, k.d_owner, k.d_box,
+                               k.d_off, z, im->d_nelec, im->H, im->W, k.mode, k.d_out);
+        };
+        if (k.i_data) direct(k_patch_ll<int>, k.i_data); else direct(k_patch_ll<double>, (const double *)k.d_data);
+        return;
     }
-    {
-        int pi = prof_begin(c, CEL_K_PATCH_LL);
-        // the resident split's patches are int32 photon counts (mode 0); everything a caller hands over, and the observed
-        // image the resident mode 1 reads, is double
-        const int *i_data = (resident && mode == 0) ? im->d_samp : nullptr;
-        if (c->variant == 0) {
-            if (i_data)
-                hipLaunchKernelGGL(k_patch_ll<int>, dim3((unsigned)(P * B)), dim3(256), 0, c->stream, im->d_bands, B, P, im->d_recs,
-                                   d_owner, d_box, d_off, i_data, im->d_nelec, im->H, im->W, mode, d_out);
-            else
-                hipLaunchKernelGGL(k_patch_ll<double>, dim3((unsigned)(P * B)), dim3(256), 0, c->stream, im->d_bands, B, P, im->d_recs,
-                                   d_owner, d_box, d_off, (const double *)d_data, im->d_nelec, im->H, im->W, mode, d_out);
-        } else if (mode == 0) {
-            if (!resident)
-                hipLaunchKernelGGL(k_patch_nzbox<double>, dim3((unsigned)nb), dim3(64), 0, c->stream, d_box, d_off, (const double *)d_data, d_nz);
-            if (i_data) {
-                hipLaunchKernelGGL((k_patch_ll_hw<0, int>), dim3((unsigned)(P * B * nsplit)), dim3(64), 0, c->stream, im->d_bands, B, P, im->d_recs,
-                                   d_owner, d_box, d_off, i_data, im->d_nelec, im->H, im->W, d_nz, c->tail_T, d_out,
-                                   (const int *)nullptr, nsplit, (const int *)nullptr, (const int *)(nzl ? im->d_nzmode : nullptr), 0, nparts);
-                if (nzl)                    // ... and the proposals whose patch is scored at its photons (the others return at once)
-                    hipLaunchKernelGGL(k_patch_ll_nz<false>, dim3((unsigned)(P * B)), dim3(64), 0, c->stream, im->d_bands, B, P, im->d_recs,
-                                       (const int *)d_owner, (const int4 *)d_box, (const int4 *)d_nz, (const int *)im->d_nzmode,
-                                       (const int64_t *)im->d_nzoff, (const NzEntry *)im->d_nzlist, d_out, (const int *)nullptr,
-                                       (const int *)nullptr, (const SliceFuse *)nullptr);
-            } else
-                hipLaunchKernelGGL((k_patch_ll_hw<0, double>), dim3((unsigned)(P * B * nparts)), dim3(64), 0, c->stream, im->d_bands, B, P, im->d_recs,
-                                   d_owner, d_box, d_off, (const double *)d_data, im->d_nelec, im->H, im->W, d_nz, c->tail_T, d_out,
-                                   (const int *)nullptr, nparts, (const int *)nullptr);
-        } else if (mode == 2)
-            hipLaunchKernelGGL((k_patch_ll_hw<2, double>), dim3((unsigned)(P * B)), dim3(64), 0, c->stream, im->d_bands, B, P, im->d_recs,
-                               d_owner, d_box, d_off, (const double *)d_data, im->d_nelec, im->H, im->W, (const int4 *)nullptr, c->tail_T, d_out,
-                               (const int *)nullptr, 1, (const int *)nullptr);
-        else if (mode == 4)
-            hipLaunchKernelGGL((k_patch_ll_hw<4, double>), dim3((unsigned)(P * B)), dim3(64), 0, c->stream, im->d_bands, B, P, im->d_recs,
-                               d_owner, d_box, d_off, (const double *)d_data, im->d_nelec, im->H, im->W, (const int4 *)nullptr, c->tail_T, d_out,
-                               (const int *)nullptr, 1, (const int *)nullptr);
-        else
-            hipLaunchKernelGGL((k_patch_ll_hw<1, double>), dim3((unsigned)(P * B)), dim3(64), 0, c->stream, im->d_bands, B, P, im->d_recs,
-                               d_owner, d_box, d_off, (const double *)d_data, im->d_nelec, im->H, im->W, (const int4 *)nullptr, c->tail_T, d_out,
-                               (const int *)nullptr, 1, (const int *)nullptr);
-        prof_end(c, pi);
+    PatchLlJob<double> jd = patch_ll_job(c, im, P, k.d_owner, k.d_out, k.d_box, k.d_off, (const double *)k.d_data);     // (no data: mode 1 on the resident boxes)
+    if (k.mode == 1) launch_patch_ll<1>(c, im, jd, P * B, st);           // modes 1, 2 and 4: one block per job over the whole patch
+    else if (k.mode == 2) launch_patch_ll<2>(c, im, jd, P * B, st);
+    else if (k.mode == 4) launch_patch_ll<4>(c, im, jd, P * B, st);
+    else if (k.i_data) {             // mode 0 on the resident split's patches
+        PatchLlJob<int> j = patch_ll_job(c, im, P, k.d_owner, k.d_out, k.d_box, k.d_off, k.i_data);
+        j.nzbox = k.d_nz; j.nsplit = k.nsplit; j.nzmode = k.nzl ? (const int *)im->d_nzmode : nullptr; j.ostride = k.nparts;
+        launch_patch_ll<0>(c, im, j, P * B * k.nsplit, st);
+        if (k.nzl)                   // ... and the proposals whose patch is scored at its photons (the others return at once)
+            hipLaunchKernelGGL(k_patch_ll_nz<false>, dim3((unsigned)(P * B)), dim3(64), 0, st, im->d_bands, B, P, im->d_recs,
+                               (const int *)k.d_owner, (const int4 *)k.d_box, (const int4 *)k.d_nz, (const int *)im->d_nzmode,
+                               (const int64_t *)im->d_nzoff, (const NzEntry *)im->d_nzlist, k.d_out, (const int *)nullptr,
+                               (const int *)nullptr, (const SliceFuse *)nullptr);
+    } else {                         // mode 0 on a caller's patches: on their photon rectangles
+        if (!k.resident)
+            hipLaunchKernelGGL(k_patch_nzbox<double>, dim3((unsigned)k.nb), dim3(64), 0, st, k.d_box, k.d_off, (const double *)k.d_data, k.d_nz);
+        jd.nzbox = k.d_nz; jd.nsplit = k.nparts;
+        launch_patch_ll<0>(c, im, jd, P * B * k.nparts, st);
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(hout.data(), d_out, sizeof(double) * P * B * nparts, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+}
+
+// step 4: a proposal's value -- a job's parts first, in order (as k_slice_step does), then the bands, in order (the reference's image loop)
+static void pll_sum(const std::vector<double> &hout, int64_t P, int B, int nparts, double *ll) {
     for (int64_t p = 0; p < P; p++) {
         double s = 0.0;
-        for (int b = 0; b < B; b++) {                       // band order, like the reference's image loop
+        for (int b = 0; b < B; b++) {
             const double *q = hout.data() + (size_t)(p * B + b) * nparts;
             double x = q[0];
-            for (int k = 1; k < nparts; k++) x += q[k];     // a job's parts first, in order (as k_slice_step does)
+            for (int i = 1; i < nparts; i++) x += q[i];
             s += x;
         }
-        if (grad) val[(size_t)p] = s;                       // slot 0 of the gradient form, written once its sums are in
-        else ll_out[p] = s;
+        ll[p] = s;
     }
-    if (!grad) return CEL_OK;
-    // ---- the gradient form (k_patch_grad.h): the same records, boxes, offsets, owners and staged data, still in their slots
+}
+
+// step 5, the gradient form (k_patch_grad.h): the same records, boxes, offsets, owners and staged data, still in their slots;
+// `val` is mode m's value per proposal, slot 0 of its row
+static int pll_gradient(cel_images *im, cel_sources *src, const PllCall &k, const std::vector<double> &val, double *ll_out) {
+    cel_ctx *c = im->ctx;
+    const int B = im->B, mode = k.mode;
+    const int64_t P = k.P;
     double *d_sums = nullptr, *d_grad = nullptr;
     const size_t ng = (size_t)P * (7 + B);
+    int rc;
     if ((rc = scratch_get(c, SCR_TMP_A, sizeof(double) * GRAD_NS * PGRAD_PARTS * (size_t)(P * B), (void **)&d_sums)) ||
         (rc = scratch_get(c, SCR_TMP_B, sizeof(double) * ng, (void **)&d_grad)))
         return rc;
-    {
-        int pi = prof_begin(c, CEL_K_PATCH_LL);
-        const dim3 grid((unsigned)(P * B * PGRAD_PARTS));
-        const int *i_data = (resident && mode == 0) ? (const int *)im->d_samp : nullptr;
+    int pi = prof_begin(c, CEL_K_PATCH_LL);
+    const dim3 grid((unsigned)(P * B * PGRAD_PARTS));
 #define PGRAD_LAUNCH(M, TZ, DATA)                                                                                              \
-        hipLaunchKernelGGL((k_patch_grad<M, TZ>), grid, dim3(64), 0, c->stream, im->d_bands, B, P, im->d_recs, (const int *)d_owner, \
-                           (const int4 *)d_box, (const int64_t *)d_off, (const TZ *)(DATA), (const double *)im->d_nelec, im->H, im->W, d_sums)
-        if (i_data) PGRAD_LAUNCH(0, int, i_data);
-        else if (mode == 0) PGRAD_LAUNCH(0, double, d_data);
-        else if (mode == 1) PGRAD_LAUNCH(1, double, d_data);
-        else PGRAD_LAUNCH(2, double, d_data);
+    hipLaunchKernelGGL((k_patch_grad<M, TZ>), grid, dim3(64), 0, c->stream, im->d_bands, B, P, im->d_recs, (const int *)k.d_owner, \
+                       (const int4 *)k.d_box, (const int64_t *)k.d_off, (const TZ *)(DATA), (const double *)im->d_nelec, im->H, im->W, d_sums)
+    if (k.i_data) PGRAD_LAUNCH(0, int, k.i_data);
+    else if (mode == 0) PGRAD_LAUNCH(0, double, k.d_data);
+    else if (mode == 1) PGRAD_LAUNCH(1, double, k.d_data);
+    else PGRAD_LAUNCH(2, double, k.d_data);
 #undef PGRAD_LAUNCH
-        hipLaunchKernelGGL(k_patch_grad_chain, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, c->stream, im->d_bands, B, P, im->d_recs,
-                           (const int *)d_owner, (const int4 *)d_box, (const int *)src->d_type, (const double *)src->d_shape,
-                           (const double *)src->d_counts, (const double *)d_sums, mode, d_grad);
-        prof_end(c, pi);
-    }
+    hipLaunchKernelGGL(k_patch_grad_chain, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, c->stream, im->d_bands, B, P, im->d_recs,
+                       (const int *)k.d_owner, (const int4 *)k.d_box, (const int *)src->d_type, (const double *)src->d_shape,
+                       (const double *)src->d_counts, (const double *)d_sums, mode, d_grad);
+    prof_end(c, pi);
     HIP_TRY(hipGetLastError());
     std::vector<double> hg(ng);
     HIP_TRY(hipMemcpyAsync(hg.data(), d_grad, sizeof(double) * ng, hipMemcpyDeviceToHost, c->stream));
@@ -1782,6 +1827,26 @@ int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owne
     for (int64_t p = 0; p < P; p++) hg[(size_t)p * (7 + B)] = val[(size_t)p];
     memcpy(ll_out, hg.data(), sizeof(double) * ng);
     return CEL_OK;
+}
+
+int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owner, int64_t NB,
+                           const int32_t *boxes, const int64_t *offsets, const double *data, int mem, int mode_arg,
+                           double *ll_out) {
+    PllCall k;
+    int rc = pll_check(im, src, owner, NB, boxes, offsets, data, mode_arg, ll_out, k);
+    if (rc || k.P == 0) return rc;
+    if ((rc = run_prep(im, src)) || (rc = pll_stage(im, owner, offsets, data, mem, k))) return rc;
+    cel_ctx *c = im->ctx;
+    const int pi = prof_begin(c, CEL_K_PATCH_LL);
+    pll_launch_values(im, k);
+    prof_end(c, pi);
+    HIP_TRY(hipGetLastError());
+    std::vector<double> hout((size_t)(k.P * im->B * k.nparts)), val((size_t)(k.grad ? k.P : 0));
+    HIP_TRY(hipMemcpyAsync(hout.data(), k.d_out, sizeof(double) * hout.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    // (slot 0 of the gradient form is written once its sums are in)
+    pll_sum(hout, k.P, im->B, k.nparts, k.grad ? val.data() : ll_out);
+    return k.grad ? pll_gradient(im, src, k, val, ll_out) : CEL_OK;
 }
 
 int cel_patch_loglik(cel_images *im, cel_sources *src, const int32_t *boxes, const int64_t *offsets,
@@ -1845,9 +1910,7 @@ int cel_stamp_mass_begin(cel_images *im, cel_sources *src) {
         hipLaunchKernelGGL(k_stamp_mass_masked, dim3((unsigned)(S * B)), dim3(64), 0, c->stream, im->d_bands, B, im->H, im->W, S,
                            im->d_recs, (const double *)im->d_nelec, c->tail_T, d_out, (const int *)nullptr);
     } else {
-        hipLaunchKernelGGL((k_patch_ll_hw<3, double>), dim3((unsigned)(S * B)), dim3(64), 0, c->stream, im->d_bands, B, S, im->d_recs,
-                           (const int *)nullptr, (const int4 *)nullptr, (const int64_t *)nullptr, (const double *)nullptr,
-                           (const double *)nullptr, im->H, im->W, (const int4 *)nullptr, c->tail_T, d_out);
+        launch_stamp_mass(c, im, S, nullptr, d_out, S * B);
     }
     prof_end(c, pi);
     HIP_TRY(hipGetLastError());
@@ -1878,10 +1941,7 @@ static int mass_finish(cel_images *im, int64_t *n_out) {
             // catalogue, or a photon split that re-allocated its buffers, is caught here instead of scoring stale records:
             if (im->mass.todo_ptr != im->d_mass_todo || !im->mass.intact(im->rec, im->split))
                 return fail(CEL_ERR_INVALID, "cel_stamp_mass_end: the source records or the photon split were rebuilt since cel_stamp_mass_begin");
-            hipLaunchKernelGGL((k_patch_ll_hw<3, double>), dim3((unsigned)ntodo), dim3(64), 0, c->stream, im->d_bands, im->B, S_todo, im->d_recs,
-                               (const int *)nullptr, (const int4 *)nullptr, (const int64_t *)nullptr, (const double *)nullptr,
-                               (const double *)nullptr, im->H, im->W, (const int4 *)nullptr, c->tail_T, im->mass.values,
-                               (const int *)im->d_mass_todo);
+            launch_stamp_mass(c, im, S_todo, nullptr, im->mass.values, ntodo, im->d_mass_todo);
             HIP_TRY(hipGetLastError());
         }
     }
@@ -1982,16 +2042,23 @@ int cel_stamp_mass(cel_images *im, cel_sources *src, double *mass) {
 // their jobs densely (k_patch_ll_hw<0>), those of `nz` at their photons (k_patch_ll_nz; `fuse`: the block that finishes a
 // chain's last job steps the chain).  A list names the blocks of a round; `count` is its length where only the device knows
 // it (the launch is sized by an upper bound and the kernels stop there).  Every job fills its PLL_PARTS slots of d_ll.
+// CEL_OPT_KERNEL = 0 knows no lists: the direct kernel scores every (proposal, band) job in one launch, one slot per job.  -> launches
 struct LlBlocks { int64_t n; const int *list, *count; };
-static void launch_resident_ll(cel_ctx *c, cel_images *im, int64_t P, const int *d_owner, double *d_ll, bool use_nz,
-                               LlBlocks dense, LlBlocks nz, const SliceFuse *fuse) {
+static int launch_resident_ll(cel_ctx *c, cel_images *im, int64_t P, const int *d_owner, double *d_ll, bool use_nz,
+                              LlBlocks dense, LlBlocks nz, const SliceFuse *fuse) {
     const int B = im->B;
     hipStream_t st = c->stream;
-    if (dense.n > 0) {
+    if (c->variant == 0) {
         int pi = prof_slot(c, CEL_K_PATCH_LL);
-        LAUNCH_EV((k_patch_ll_hw<0, int>), dim3((unsigned)dense.n), dim3(64), st, EV0(c, pi), EV1(c, pi), im->d_bands, B, P, im->d_recs,
-                  d_owner, im->d_sbox, im->d_soff, (const int *)im->d_samp, im->d_nelec, im->H, im->W, im->d_snz, c->tail_T, d_ll,
-                  dense.list, 1, dense.count, (const int *)(use_nz ? im->d_nzmode : nullptr), 1, PLL_PARTS);
+        LAUNCH_EV(k_patch_ll<int>, dim3((unsigned)(P * B)), dim3(256), st, EV0(c, pi), EV1(c, pi), im->d_bands, B, P, im->d_recs,
+                  d_owner, im->d_sbox, im->d_soff, (const int *)im->d_samp, im->d_nelec, im->H, im->W, 0, d_ll);
+        return 1;
+    }
+    if (dense.n > 0) {
+        PatchLlJob<int> j = patch_ll_job(c, im, P, d_owner, d_ll, im->d_sbox, im->d_soff, (const int *)im->d_samp);
+        j.nzbox = im->d_snz; j.job_order = dense.list; j.job_count = dense.count; j.nzmode = use_nz ? (const int *)im->d_nzmode : nullptr;
+        j.encoded = 1; j.ostride = PLL_PARTS;
+        launch_patch_ll<0>(c, im, j, dense.n, st, prof_slot(c, CEL_K_PATCH_LL));
     }
     if (nz.n > 0) {
         int pi = prof_slot(c, CEL_K_PATCH_LL);
@@ -2002,6 +2069,32 @@ static void launch_resident_ll(cel_ctx *c, cel_images *im, int64_t P, const int 
         };
         if (fuse) go(k_patch_ll_nz<true>); else go(k_patch_ll_nz<false>);
     }
+    return (dense.n > 0) + (nz.n > 0);
+}
+
+// The exact conditional's pair (k_slice_gen.h) for the P slots of `prop`: the mass kernel proper, cel_stamp_mass_begin's plain
+// branch, on the running chains' jobs (a slot that is not scored retires by its owner; a launch of P B blocks that find
+// nothing to do costs 0.15 ms, see there), then the term per slot
+static void launch_exact_terms(cel_ctx *c, cel_images *im, const cel_sources *prop, int64_t P, const int *d_owner, int64_t n_mass,
+                               const int *d_list_mass, double *d_mass, double *d_exact) {
+    if (n_mass > 0) launch_stamp_mass(c, im, P, d_owner, d_mass, n_mass, d_list_mass);
+    hipLaunchKernelGGL(k_sg_exact_terms, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, c->stream, P, im->B, d_owner, (const BandDev *)im->d_bands,
+                       (const double *)prop->d_counts, (const double *)d_mass, (const int64_t *)im->d_soff, d_exact);
+}
+
+// a sampler's proposal set of n rows in `own`, built anew with room to spare when the one there is too small
+static int ensure_proposals(cel_ctx *c, std::unique_ptr<cel_sources, SourcesDeleter> &own, int64_t n, int B) {
+    if (own && own->cap >= n) return CEL_OK;
+    own.reset();
+    cel_sources *np = nullptr;
+    int rc = cel_sources_create(c, n + n / 4 + 16, B, &np);
+    if (!rc) own.reset(np);
+    return rc;
+}
+
+// chains with a negative id are another rank's: they never run here
+static int64_t chains_here(const int32_t *chain_ids, int64_t S) {
+    return chain_ids ? (int64_t)std::count_if(chain_ids, chain_ids + S, [](int32_t id) { return id >= 0; }) : S;
 }
 
 int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_ids, double sigma, uint64_t seed,
@@ -2067,13 +2160,7 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
     const size_t need = carve(nullptr);
     HIP_TRY(im->d_slice.grow(need, need + need / 4, st));
     carve(im->d_slice);
-    if (!im->slice_prop || im->slice_prop->cap < S) {
-        im->slice_prop.reset();
-        cel_sources *np = nullptr;
-        int rc0 = cel_sources_create(c, S + S / 4 + 16, B, &np);
-        if (rc0) return rc0;
-        im->slice_prop.reset(np);
-    }
+    { int rp = ensure_proposals(c, im->slice_prop, S, B); if (rp) return rp; }
     cel_sources *prop = im->slice_prop.get();
     // the proposal set: this catalogue with the locations rewritten every round
     HIP_TRY(hipMemcpyAsync(prop->d_type, src->d_type, sizeof(int) * S, hipMemcpyDeviceToDevice, st));
@@ -2125,12 +2212,8 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
     // likelihood launch and the round gains under 10 us.  c->slice_fuse = N: rounds of at most N blocks are fused (1: every round).
     const bool fuse_ok = use_nz && c->slice_fuse && n_dense == 0 && n_nz > 0;
     bool fused = false;                               // of the batch being queued
-    int64_t rounds = 0, evals = 0, queued = 0, live = S;
-    if (chain_ids) {                    // chains with a negative id are another rank's: they never run here
-        live = 0;
-        for (int64_t s = 0; s < S; s++) live += chain_ids[s] >= 0;
-        if (live < 1) live = 1;         // a launch needs a block; k_slice_live_jobs finds nothing to run
-    }
+    int64_t rounds = 0, evals = 0, queued = 0, live = chains_here(chain_ids, S);
+    if (chain_ids && live < 1) live = 1;    // a launch needs a block; k_slice_live_jobs finds nothing to run
     int rc = CEL_OK;
     // The chains advance on the device alone (propose -> records -> likelihoods -> consume), so rounds are queued SLICE_BATCH
     // at a time and the flags read once per batch -- and TWO batches are kept in flight: batch k + 1 is queued before the
@@ -2187,15 +2270,9 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
                 prop->all_rows_changed(true);
                 // the first round's records; every later round's were written by the step kernel that named its points
                 if (queued == 0 && (rc = run_prep(im, prop, d_owner, 1))) return rc;      // the patch limits are fixed: no boxes
-                if (c->variant == 0) {
-                    int pi = prof_slot(c, CEL_K_PATCH_LL);
-                    LAUNCH_EV(k_patch_ll<int>, dim3((unsigned)(S * B)), dim3(256), st, EV0(c, pi), EV1(c, pi), im->d_bands, B, S, im->d_recs,
-                              d_owner, im->d_sbox, im->d_soff, (const int *)im->d_samp, im->d_nelec, im->H, im->W, 0, d_ll);
-                } else {
-                    launch_resident_ll(c, im, S, d_owner, d_ll, use_nz, {gd, use_live ? d_live : d_jobs, use_live ? d_flags + 4 : nullptr},
-                                       {gn, use_live ? d_live_nz : d_jobs_nz, use_live ? d_flags + 5 : nullptr},
-                                       fused ? d_fz + (use_live ? 1 : 0) : nullptr);
-                }
+                launch_resident_ll(c, im, S, d_owner, d_ll, use_nz, {gd, use_live ? d_live : d_jobs, use_live ? d_flags + 4 : nullptr},
+                                   {gn, use_live ? d_live_nz : d_jobs_nz, use_live ? d_flags + 5 : nullptr},
+                                   fused ? d_fz + (use_live ? 1 : 0) : nullptr);
                 if (!fused)
                 hipLaunchKernelGGL(k_slice_step, dim3((unsigned)((S + 63) / 64)), dim3(64 * B), 0, st, ss, S, B, ostr, d_ll, sigma, d_flags, (int)queued, prop->d_radec, d_owner,
                                    (k == nb - 1 && c->variant != 0 && !fuse_ok) ? 1 : 0, pa);
@@ -2309,13 +2386,7 @@ static int slice_type_move(cel_images *im, cel_sources *src, const int32_t *chai
     const size_t need = carve(nullptr);
     HIP_TRY(im->d_sgen.grow(need, need + need / 4, st));
     carve(im->d_sgen);
-    if (!im->sgen_prop || im->sgen_prop->cap < 2 * S) {
-        im->sgen_prop.reset();
-        cel_sources *np = nullptr;
-        int rc0 = cel_sources_create(c, 2 * S + S / 2 + 16, B, &np);
-        if (rc0) return rc0;
-        im->sgen_prop.reset(np);
-    }
+    { int rp = ensure_proposals(c, im->sgen_prop, 2 * S, B); if (rp) return rp; }
     cel_sources *prop = im->sgen_prop.get();
     const int64_t P = 2 * S;
     if (S == 0) {
@@ -2337,8 +2408,7 @@ static int slice_type_move(cel_images *im, cel_sources *src, const int32_t *chai
     int64_t n_dense = P * B, n_nz = 0, n_mass = 0;
     int *h_flags = c->mail->sh.slice_flags;
     if (lists || exact) {
-        int64_t live = S;
-        if (chain_ids) { live = 0; for (int64_t s = 0; s < S; s++) live += chain_ids[s] >= 0; }
+        const int64_t live = chains_here(chain_ids, S);
         hipLaunchKernelGGL(k_tm_jobs, dim3(j256), dim3(256), 0, st, tm, S, B, (const int *)(use_nz ? im->d_nzmode : nullptr),
                            (const int *)im->d_nnz, (const int4 *)im->d_snz, (live * 2 * B <= 8192) ? 1 : 0,
                            lists ? d_list : (int *)nullptr, d_flags + 4, d_list_nz, d_flags + 5, d_list_mass, d_flags + 6);
@@ -2354,26 +2424,8 @@ static int slice_type_move(cel_images *im, cel_sources *src, const int32_t *chai
     if (exact)
         hipLaunchKernelGGL(k_sg_cover, dim3(p256), dim3(256), 0, st, P, B, d_owner, tm.pri, (const int4 *)im->d_boxes,
                            (const int *)im->d_status, (const int4 *)im->d_snz);
-    int64_t launches = 0;
-    if (c->variant == 0) {
-        int pi = prof_slot(c, CEL_K_PATCH_LL);
-        LAUNCH_EV(k_patch_ll<int>, dim3((unsigned)(P * B)), dim3(256), st, EV0(c, pi), EV1(c, pi), im->d_bands, B, P, im->d_recs,
-                  (const int *)d_owner, im->d_sbox, im->d_soff, (const int *)im->d_samp, im->d_nelec, im->H, im->W, 0, d_ll);
-        launches = 1;
-    } else {
-        launch_resident_ll(c, im, P, d_owner, d_ll, use_nz, {n_dense, d_list, nullptr}, {n_nz, d_list_nz, nullptr}, nullptr);
-        launches = (n_dense > 0) + (n_nz > 0);
-    }
-    if (exact) {
-        if (n_mass > 0)
-            hipLaunchKernelGGL((k_patch_ll_hw<3, double>), dim3((unsigned)n_mass), dim3(64), 0, st, im->d_bands, B, P, im->d_recs,
-                               (const int *)d_owner, (const int4 *)nullptr, (const int64_t *)nullptr, (const double *)nullptr,
-                               (const double *)nullptr, im->H, im->W, (const int4 *)nullptr, c->tail_T, d_mass,
-                               (const int *)d_list_mass);
-        hipLaunchKernelGGL(k_sg_exact_terms, dim3(p256), dim3(256), 0, st, P, B, (const int *)d_owner,
-                           (const BandDev *)im->d_bands, (const double *)prop->d_counts, (const double *)d_mass,
-                           (const int64_t *)im->d_soff, d_exact);
-    }
+    const int64_t launches = launch_resident_ll(c, im, P, d_owner, d_ll, use_nz, {n_dense, d_list, nullptr}, {n_nz, d_list_nz, nullptr}, nullptr);
+    if (exact) launch_exact_terms(c, im, prop, P, d_owner, n_mass, d_list_mass, d_mass, d_exact);
     hipLaunchKernelGGL(k_tm_decide, dim3(g256), dim3(256), 0, st, tm, S, B, ostr, (const double *)d_ll, (const double *)d_exact,
                        (const double *)prop->d_shape, (int *)src->d_type, (double *)src->d_shape, d_out, d_flag, d_flags + 1);
     HIP_TRY(hipGetLastError());
@@ -2476,13 +2528,7 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
     const size_t need = carve(nullptr);
     HIP_TRY(im->d_sgen.grow(need, need + need / 4, st));
     carve(im->d_sgen);
-    if (!im->sgen_prop || im->sgen_prop->cap < 2 * S) {
-        im->sgen_prop.reset();
-        cel_sources *np = nullptr;
-        int rc0 = cel_sources_create(c, 2 * S + S / 2 + 16, B, &np);
-        if (rc0) return rc0;
-        im->sgen_prop.reset(np);
-    }
+    { int rp = ensure_proposals(c, im->sgen_prop, 2 * S, B); if (rp) return rp; }
     cel_sources *prop = im->sgen_prop.get();
     g.D = D; g.ndir = ndir; g.compwise = compwise; g.step_out = step_out ? 1 : 0; g.max_steps_out = max_steps_out; g.param = param;
     g.sigma = sigma; g.phi_max = param ? phi_max : 0.0; g.dirs = compwise ? nullptr : d_dirs;
@@ -2533,24 +2579,9 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
             if (exact)
                 hipLaunchKernelGGL(k_sg_cover, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, P, B, d_owner, g.pri,
                                    (const int4 *)im->d_boxes, (const int *)im->d_status, (const int4 *)im->d_snz);
-            if (c->variant == 0) {
-                int pi = prof_slot(c, CEL_K_PATCH_LL);
-                LAUNCH_EV(k_patch_ll<int>, dim3((unsigned)(P * B)), dim3(256), st, EV0(c, pi), EV1(c, pi), im->d_bands, B, P, im->d_recs,
-                          (const int *)d_owner, im->d_sbox, im->d_soff, (const int *)im->d_samp, im->d_nelec, im->H, im->W, 0, d_ll);
-            } else {
-                launch_resident_ll(c, im, P, d_owner, d_ll, use_nz, {n_dense, d_list, nullptr}, {n_nz, d_list_nz, nullptr}, nullptr);
-            }
+            launch_resident_ll(c, im, P, d_owner, d_ll, use_nz, {n_dense, d_list, nullptr}, {n_nz, d_list_nz, nullptr}, nullptr);
             if (exact) {
-                // the mass kernel proper, cel_stamp_mass_begin's plain branch, on the running chains' jobs (a slot that is not
-                // scored retires by its owner; a launch of 2 S B blocks that find nothing to do costs 0.15 ms, see there)
-                if (n_mass > 0)
-                    hipLaunchKernelGGL((k_patch_ll_hw<3, double>), dim3((unsigned)n_mass), dim3(64), 0, st, im->d_bands, B, P, im->d_recs,
-                                       (const int *)d_owner, (const int4 *)nullptr, (const int64_t *)nullptr, (const double *)nullptr,
-                                       (const double *)nullptr, im->H, im->W, (const int4 *)nullptr, c->tail_T, d_mass,
-                                       (const int *)d_list_mass);
-                hipLaunchKernelGGL(k_sg_exact_terms, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, P, B, (const int *)d_owner,
-                                   (const BandDev *)im->d_bands, (const double *)prop->d_counts, (const double *)d_mass,
-                                   (const int64_t *)im->d_soff, d_exact);
+                launch_exact_terms(c, im, prop, P, d_owner, n_mass, d_list_mass, d_mass, d_exact);
                 hipLaunchKernelGGL(k_sg_consume_exact, dim3(g256), dim3(256), 0, st, g, rs, S, B, ostr, (const double *)d_ll, d_flags,
                                    (const double *)d_exact);
             } else

@@ -192,18 +192,18 @@ k_patch_ll_hw(const BandDev *__restrict__ bands, int B, int64_t P, const SrcRec 
               const TZ *__restrict__ data, const double *__restrict__ nelec, int H, int W,
               const int4 *__restrict__ nzbox /* NB*B from k_patch_nzbox, or nullptr: evaluate the whole patch */,
               double Tdrop, double *__restrict__ out /* P*B*nsplit */,
-              const int *__restrict__ job_order = nullptr /* P*B: launch order of the (proposal, band) jobs, heaviest first */,
-              int nsplit = 1 /* 1 or PLL_PARTS blocks per job: block (job, part) takes the job's chunks c with
+              const int *__restrict__ job_order /* P*B: launch order of the (proposal, band) jobs, heaviest first */,
+              int nsplit /* 1 or PLL_PARTS blocks per job: block (job, part) takes the job's chunks c with
                                 c % PLL_PARTS == part and writes out[job * PLL_PARTS + part]; part 0 carries the terms that
                                 are not sums over pixels.  A round of few, long one-wave jobs (the late rounds of the slice
                                 sampler, a caller with a handful of proposals) otherwise lasts as long as its longest job
                                 while most of the GPU idles.  MODE 0 sums its chunks in PLL_PARTS classes either way and
                                 whoever adds the parts adds them in order, so a value does not depend on nsplit */,
-              const int *__restrict__ job_count = nullptr /* with job_order: only its first *job_count entries are jobs */,
-              const int *__restrict__ nzmode = nullptr /* MODE 0, resident patches: per patch 1 = scored at its photons by k_patch_ll_nz, not here */,
-              int encoded = 0 /* job_order holds (job << 3 | part << 1 | split) per BLOCK: a list may deal some jobs (the long ones) to
+              const int *__restrict__ job_count /* with job_order: only its first *job_count entries are jobs */,
+              const int *__restrict__ nzmode /* MODE 0, resident patches: per patch 1 = scored at its photons by k_patch_ll_nz, not here */,
+              int encoded /* job_order holds (job << 3 | part << 1 | split) per BLOCK: a list may deal some jobs (the long ones) to
                                  PLL_PARTS blocks and leave the others whole -- what the slice sampler launches in every round */,
-              int ostride = 0 /* doubles per job in `out` (0: PLL_PARTS when nsplit > 1, else 1).  A job that is not dealt writes its
+              int ostride /* doubles per job in `out` (0: PLL_PARTS when nsplit > 1, else 1).  A job that is not dealt writes its
                                  value to slot 0 and zeros behind it, so that whoever adds a job's slots in order gets the same bits
                                  whether the job was dealt or not */) {
     __shared__ double acc[HW_TH * HW_TW];
@@ -707,40 +707,7 @@ k_job_work(const int *__restrict__ type, const int4 *__restrict__ nzbox, int64_t
 
 // k_order (k_prep_bin.h) for the (job, part) entries of k_job_work: the members (work >= 0) come first, heaviest first,
 // each written as the kernels' block descriptor job << 3 | part << 1 | dealt (= 2 i + the work's low bit); *nmember
-// receives their number.  One block.
-__global__ void __launch_bounds__(1024)
-k_order_members(const int *__restrict__ work, int T, int *__restrict__ order, int *__restrict__ nmember) {
-    __shared__ int hist[257];
-    __shared__ int red[1024];
-    const int tid = threadIdx.x;
-    int mx = 0;
-    for (int i = tid; i < T; i += 1024) mx = max(mx, work[i] >> 1);
-    red[tid] = mx;
-    if (tid < 257) hist[tid] = 0;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if (tid < o) red[tid] = max(red[tid], red[tid + o]);
-        __syncthreads();
-    }
-    const long long wmax = red[0] > 0 ? red[0] : 1;
-    for (int i = tid; i < T; i += 1024) {
-        const int w = work[i];
-        atomicAdd(&hist[w < 0 ? 256 : 255 - (int)(((long long)(w >> 1) * 255) / wmax)], 1);
-    }
-    __syncthreads();
-    if (tid == 0) {   // exclusive scan, bucket 0 = heaviest, bucket 256 = the non-members
-        int run = 0;
-        for (int k = 0; k < 257; k++) { int c = hist[k]; hist[k] = run; run += c; }
-        *nmember = hist[256];
-    }
-    __syncthreads();
-    for (int i = tid; i < T; i += 1024) {
-        const int w = work[i];
-        order[atomicAdd(&hist[w < 0 ? 256 : 255 - (int)(((long long)(w >> 1) * 255) / wmax)], 1)] = 2 * i + (w < 0 ? 0 : (w & 1));
-    }
-}
-
-// The same in two steps, 4 x faster (three quarters of the (job, part) entries are not members): the members first
+// receives their number.  Two steps (three quarters of the (job, part) entries are not members): the members first
 // compacted by the whole GPU (one atomic per wave), then ordered by one block.
 __global__ void __launch_bounds__(256)
 k_list_members(const int *__restrict__ work, int T, int *__restrict__ work_c, int *__restrict__ desc_c, int *__restrict__ nmember) {

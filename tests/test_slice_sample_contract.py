@@ -365,6 +365,25 @@ def test_the_direct_evaluator_backs_the_samplers(cel):
 
 
 @gpu
+def test_the_direct_evaluator_backs_the_location_step(cel):
+    """CEL_OPT_KERNEL = 0 under cel_slice_locations (its rounds score through the same launch as cel_slice_sample's): the
+    oracle's run on the scorer taken under the same option, bit for bit as under the recurrence kernels"""
+    from desi_mcmc_amd import _lib
+    ctx = cel.default_context(0)
+    before = ctx.get_option(_lib.CEL_OPT_KERNEL)
+    ctx.set_kernel("direct")
+    try:
+        scene = Scene(cel)
+        seed = SEEDS[1]
+        ids = chain_ids(seed)
+        want = scene.oracle(0, ids, seed, sigma=1e-3, step_out=False)
+        scene.reset()
+        scene.check(scene.f.images.slice_locations(scene.f.sources, 1e-3, seed, chain_ids=ids), want, 0, ("direct", "slice_locations"))
+    finally:
+        ctx.set_option(_lib.CEL_OPT_KERNEL, before)
+
+
+@gpu
 def test_failures_come_back_as_the_reference_raises_them(cel, scene_a):
     """a NaN log-likelihood (a NaN among one row's expected counts) and too few rounds come back as the reference's plain
     Exception("Slice sampler got a NaN") / as ValueError, from both samplers; the image set is as good as new afterwards.
