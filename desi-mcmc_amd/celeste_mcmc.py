@@ -19,7 +19,7 @@ _M64 = (1 << 64) - 1
 # one tag per randomised step of a sweep: no two steps share a stream key for any seed (with seed = 0 the plain
 # `seed * prime + sweep` forms all collapsed to `sweep`, and a source's location, shape and flux draws were one sequence)
 STEP_TAGS = dict(split=0x53504C4954000001, flux=0x464C555800000002, location=0x4C4F434154000003, shape=0x5348415045000004,
-                 type=0x5459504500000005)
+                 type=0x5459504500000005, hmc=0x484D430000000006)
 
 
 def _mix64(z):
@@ -31,7 +31,7 @@ def _mix64(z):
 
 
 def step_seed(seed, step, sweep, k=0):
-    """the stream seed of one step (`split`, `flux`, `location`, `shape`, `type`) of sweep number `sweep` (of field k): a hash of
+    """the stream seed of one step (`split`, `flux`, `location`, `shape`, `type`, `hmc`) of sweep number `sweep` (of field k): a hash of
     all of them, so that the Gibbs blocks draw from unrelated streams whatever the chain's seed is"""
     return _mix64((_mix64(_mix64(int(seed) & _M64) ^ STEP_TAGS[step]) + int(sweep)) & _M64 ^ (int(k) * 0xD6E8FEB86659FD93 & _M64))
 
@@ -308,7 +308,8 @@ class ModelGibbs(object):
         self.engine = engine
         self.sweeps = 0
         self.timing = dict(split=0.0, flux=0.0, location=0.0, rounds=0, evals=0, shape=0.0, shape_rounds=0, shape_evals=0,
-                           type=0.0, type_evals=0, type_accepted=0)
+                           type=0.0, type_evals=0, type_accepted=0, hmc=0.0, hmc_evals=0, hmc_accepted=0)
+        self._hmc_p = None                      # the HMC step's momentum, kept from call to call (resample_hmc)
         # ONE chain over several GPUs: `deal` (dist.SourceDeal) names the sources this rank
         # updates.  Every rank runs the same photon split (counter-based draws: the replicas are bitwise equal) and
         # the same host draws (same seed), updates the fluxes and locations of ITS sources only, and the ranks
@@ -603,9 +604,10 @@ class ModelGibbs(object):
                 ll += self._exact_terms(f, idx, pc)
         return ll
 
-    def location_loglik_grad(self, idx, U, typ=None, shape=None):
+    def location_loglik_grad(self, idx, U, typ=None, shape=None, shape_grad=False):
         """location_loglik with its analytic gradient in (ra, dec), per degree, summed over fields (the gradient form of
         cel_patch_loglik_multi against the resident patches) -> (ll[P], g[P, 2]); ll is location_loglik's value, bit for bit.
+        shape_grad=True: the six coordinates (ra, dec, theta, sigma, phi, rho) -> (ll[P], g[P, 6]) (a star's last four: 0).
         The exact conditional's mass term has no derivative here: conditional="exact" raises."""
         from . import field as _field
         if self.conditional == "exact":
@@ -613,7 +615,7 @@ class ModelGibbs(object):
                              "(conditional='reference' only)")
         idx = np.asarray(idx, dtype=np.int64)
         P = idx.shape[0]
-        ll, g = np.zeros(P), np.zeros((P, 2))
+        ll, g = np.zeros(P), np.zeros((P, 6 if shape_grad else 2))
         typ = self.typ[idx] if typ is None else np.ascontiguousarray(typ, dtype=np.int32)
         shape = self.shape[idx] if shape is None else np.asarray(shape, dtype=np.float64).reshape(P, 4)
         owner = idx.astype(np.int32)
@@ -623,9 +625,9 @@ class ModelGibbs(object):
             cts = getattr(f, "_counts", None)
             pc = self.counts(f, idx=idx) if cts is None else cts[idx]
             f.prop.set(typ, U, pc, shape)
-            l, gr, _, _ = f.iset.patch_loglik_resident_grad(f.prop, owner)
+            l, gr, _, gs = f.iset.patch_loglik_resident_grad(f.prop, owner)
             ll += l
-            g += gr
+            g += np.concatenate([gr, gs], axis=1) if shape_grad else gr
         return ll, g
 
     def _exact_terms(self, f, sel, pc):
@@ -912,6 +914,150 @@ class ModelGibbs(object):
         self.timing["type"] += time.perf_counter() - t0
         return self.typ
 
+    # -- hmc_sample_galaxy_params: celeste_mcmc.py:281-331, all sources at once ------------------------------------
+    #: the reference's call: step 1e-5, 50 leapfrog steps, mass (.1, .1, 1, .1 | .001, .001) for (theta, sigma, phi, rho | u),
+    #: refresh_alpha .9 -- here in the order of q = (ra, dec, theta, sigma, phi, rho)
+    HMC_REFERENCE = dict(eps=1e-5, steps=50, mass=(.001, .001, .1, .1, 1., .1), refresh=.9)
+
+    @classmethod
+    def hmc_preset(cls, name):
+        """"reference" -> the keyword arguments of resample_hmc that make hmc_sample_galaxy_params' call
+        (celeste_mcmc.py:287-314): dict(eps, steps, imass, refresh)"""
+        if name != "reference":
+            raise ValueError("hmc preset must be 'reference'")
+        r = cls.HMC_REFERENCE
+        return dict(eps=r["eps"], steps=r["steps"], imass=1.0 / np.array(r["mass"], dtype=np.float64), refresh=r["refresh"])
+
+    def hmc_default_imass(self):
+        """the library's scale-free inverse mass (S, 6): (one pixel in degrees)^2 / N for ra and dec and 1 / N for the shape,
+        N = the chain's photons in the current split (at least 1) -- the order of a posterior variance when the PSF is about a
+        pixel wide.  Nobody has tuned it."""
+        N = np.zeros(self.S)
+        for f in self.fields:
+            N = N + np.asarray(f.sums, dtype=np.float64).sum(axis=1)
+        N = np.maximum(N, 1.0)
+        ups = np.asarray(self.fields[0].iset.band(0), dtype=np.float64)[28:32]
+        pix2 = abs(ups[0] * ups[3] - ups[1] * ups[2])
+        im = np.empty((self.S, 6))
+        im[:, :2] = (pix2 / N)[:, None]
+        im[:, 2:] = (1.0 / N)[:, None]
+        return im
+
+    def _hmc_engine_on_device(self):
+        """the device runs the HMC step (cel_slice_sample, param 3) where it runs the type step under the reference's
+        conditional: one field of unmasked frames"""
+        ok = len(self.fields) == 1 and self.mask != "honour"
+        if self.engine == "device" and not ok:
+            raise ValueError("the device HMC step runs one field of whole, unmasked frames")
+        return ok and self.engine != "host"
+
+    def resample_hmc(self, eps=None, steps=None, imass=None, refresh=0.0):
+        """hmc_sample_galaxy_params (celeste_mcmc.py:281-331) for every source at once: one HMC update of
+        q = (ra, dec, theta, sigma, phi, rho) per galaxy and of (ra, dec) per star against the current photon split, the counts
+        held fixed (the flux step samples their Gamma conditional exactly).  Given the split a source's conditional involves
+        no other source, so the update of all sources at once is exact.  The target is the location and shape steps'
+        conditional with the built-in shape prior; `steps` leapfrog steps of size eps (util/infer/hmc.py), accepted iff
+        log u < log alpha with u the first uniform of the chain's stream of step_seed("hmc").
+        The momentum is kept from call to call and refreshed as  refresh * p + sqrt(1 - refresh^2) * sqrt(mass) * z  with z
+        the normals of the streams of step_seed("hmc", 1) (refresh=0: a fresh momentum every call); a coordinate with
+        imass = 0 is frozen and its momentum is 0.  imass: (6,) or (S, 6), default hmc_default_imass(); eps default 0.5, steps
+        default 8.  hmc_preset("reference") holds the reference's numbers.  phi is wrapped afterwards, as resample_shapes wraps it.
+        The exact conditional's mass term has no derivative yet: conditional="exact" raises."""
+        import time
+        from .util.infer.slicesample import ChainStreams
+        from .util.infer.hmc import hmc_lockstep
+        if self.conditional == "exact":
+            raise ValueError("resample_hmc: the exact conditional's stamp-mass term has no analytic derivative yet "
+                             "(conditional='reference' only)")
+        if not self._default_shape_prior:
+            raise ValueError("resample_hmc: a custom shape prior (shape_logprior=) has no derivative here")
+        on_device = self._hmc_engine_on_device()
+        t0 = time.perf_counter()
+        S = self.S
+        eps = 0.5 if eps is None else float(eps)
+        steps = 8 if steps is None else int(steps)
+        refresh = float(refresh)
+        if not (eps > 0.0) or not (1 <= steps <= 1024) or not (0.0 <= refresh <= 1.0):
+            raise ValueError("resample_hmc: eps > 0, 1 <= steps <= 1024 and 0 <= refresh <= 1")
+        im = self.hmc_default_imass() if imass is None else np.array(np.broadcast_to(np.asarray(imass, dtype=np.float64), (S, 6)))
+        if not np.all(np.isfinite(im) & (im >= 0.0)):
+            raise ValueError("resample_hmc: imass must be finite and >= 0")
+        mine = self.active if self.deal is None else (self.active & self.deal.mask)
+        runs = mine & ((self.typ == 0) | (self.typ == 1))
+        im[self.typ != 1, 2:] = 0.0                     # a star moves in (ra, dec) only
+        im[~runs] = 0.0
+        # the momentum: every chain's own normals, in coordinate order
+        ids_all = np.arange(S)
+        if self._hmc_p is None or self._hmc_p.shape != (S, 6):
+            self._hmc_p = np.zeros((S, 6))
+        cs = ChainStreams(self.step_seed("hmc", 1), ids_all)
+        z = np.stack([cs.normal(ids_all) for _ in range(6)], axis=1)
+        moves = im > 0.0
+        sd = np.sqrt(1.0 / np.where(moves, im, 1.0))    # sqrt(mass)
+        p = refresh * self._hmc_p + np.sqrt(1.0 - refresh * refresh) * sd * z
+        p = np.where(moves, p, 0.0)
+        p = np.where(runs[:, None], p, self._hmc_p)
+        seed = self.step_seed("hmc")
+        q0 = np.concatenate([self.u, self.shape], axis=1)
+        if on_device:
+            f = self.fields[0]
+            sset = self._sources(f)
+            ids = np.where(runs, ids_all, -1).astype(np.int32)
+            q, pn, _, st = f.iset.hmc_step(sset, p, im, eps, steps, seed, phi_max=self.phi_period, chain_ids=ids)
+            evals, accepted = st["evals"], st["accepted"]
+        else:
+            q, pn = q0.copy(), p.copy()
+            act = np.nonzero(runs)[0]
+            evals = accepted = 0
+            if act.size:
+                from .celeste_galaxy_conditionals import galaxy_shape_prior_constrained as prior
+                period = self.phi_period
+                for f in self.fields:
+                    f._counts = self.counts(f)
+
+                def value_fn(i, Q):
+                    idx = act[i]
+                    ll = self.location_loglik(idx, Q[:, :2], shape=Q[:, 2:])
+                    gal = self.typ[idx] == 1
+                    pri = np.zeros(idx.size)
+                    pri[gal] = prior(Q[gal, 2], Q[gal, 3], Q[gal, 4], Q[gal, 5], period)
+                    return ll + pri
+
+                def grad_fn(i, Q):
+                    idx = act[i]
+                    _, g = self.location_loglik_grad(idx, Q[:, :2], shape=Q[:, 2:], shape_grad=True)
+                    gal = self.typ[idx] == 1
+                    g[~gal, 2:] = 0.0
+                    s = Q[gal, 3]
+                    g[gal, 3] = g[gal, 3] + (2.0 / ((s * s) * s) - 4.0 / s)
+                    return g
+
+                def support_fn(i, Q):
+                    gal = self.typ[act[i]] == 1
+                    inside = ((Q[:, 2] > 0.) & (Q[:, 2] < 1.) & (Q[:, 3] > 0.) & (Q[:, 5] > 0.) & (Q[:, 5] < 1.) &
+                              (Q[:, 4] > 0.) & (Q[:, 4] < period))
+                    return ~gal | inside
+
+                st = {}
+                log_u = np.log(ChainStreams(seed, act).uniform(np.arange(act.size)))
+                try:
+                    qa, pa, _, _ = hmc_lockstep(q0[act], p[act], im[act], eps, steps, value_fn, grad_fn, log_u, support_fn, stats=st)
+                finally:
+                    for f in self.fields:
+                        f._counts = None
+                q[act], pn[act] = qa, pa
+                evals, accepted = st["evals"], st["accepted"]
+        wrap = runs & (self.typ == 1)
+        q[:, 4] = np.where(wrap, (q[:, 4] + self.phi_period) % self.phi_period, q[:, 4])
+        self.u, self.shape = np.ascontiguousarray(q[:, :2]), np.ascontiguousarray(q[:, 2:])
+        self._hmc_p = pn
+        if on_device:
+            self.fields[0]._uploaded = None            # (the device holds the unwrapped angles)
+        self.timing["hmc_evals"] += evals
+        self.timing["hmc_accepted"] += accepted
+        self.timing["hmc"] += time.perf_counter() - t0
+        return self.u, self.shape
+
     def _check_types(self, types):
         if types and not self._default_shape_prior:
             raise ValueError("sweep(types=True) draws a star's galaxy shape from the built-in shape prior: with a custom shape prior "
@@ -920,11 +1066,12 @@ class ModelGibbs(object):
             raise ValueError("sweep(types=True) runs on whole frames (a replicated deal or one rank): a source that changes its "
                              "type changes its box, and a strip's window was cut for the boxes it was dealt")
 
-    def sweep(self, shapes=False, types=False):
+    def sweep(self, shapes=False, types=False, hmc=False):
         """CelesteBase.resample_model: every field's photons, then every source (fluxes, location) -- and, with
         shapes=True, the galaxies' shapes as sample_galaxy_params does (celeste_mcmc.py:166-243;
         Source.resample_shape is a stub in the reference, sources.py:321-325, so it is off by default); with types=True the
-        star <-> galaxy move last (resample_types)"""
+        star <-> galaxy move last (resample_types); with hmc=True one HMC update of every source's location and shape
+        (resample_hmc with its defaults) right after the location step"""
         self._check_types(types)
         solo = self.deal is not None and getattr(self.deal, "solo", False) and self.deal.world > 1
         if solo:        # one rank of an N-rank chain played alone (bench.py --as-rank): the other ranks' rows keep their values
@@ -932,6 +1079,8 @@ class ModelGibbs(object):
         self.resample_photons()
         self.resample_fluxes()
         self.resample_locations()
+        if hmc:
+            self.resample_hmc()
         if shapes:
             self.resample_shapes()
         if types:
@@ -944,9 +1093,10 @@ class ModelGibbs(object):
                 self.typ[other] = before[3][other]
         self.sweeps += 1
 
-    def sweep_reversed(self, shapes=False, types=False):
+    def sweep_reversed(self, shapes=False, types=False, hmc=False):
         """The sweep's blocks in REVERSE order -- (shapes,) locations, fluxes, sky levels, photons -- on the augmented state (sources, sky
-        levels, the current photon split): the time reversal of sweep() (types=True: the type move first).  Every block is reversible with respect to its
+        levels, the current photon split): the time reversal of sweep() (types=True: the type move first; hmc=True: the HMC
+        update between the shapes and the locations, reversible for a momentum refreshed in full, resample_hmc's default).  Every block is reversible with respect to its
         conditional (Gibbs draws; slice updates whose axis order is shuffled per call), so a chain run backwards from a state
         is a chain run with this.  It needs a photon split of the current state to start from (_split_photons()).  Used by the
         calibration test (tests/test_calibration.py) to put the true parameters at a random position of a stationary chain;
@@ -960,6 +1110,8 @@ class ModelGibbs(object):
             self.resample_types()
         if shapes:
             self.resample_shapes()
+        if hmc:
+            self.resample_hmc()
         self.resample_locations()
         self.resample_fluxes()
         self._resample_sky()

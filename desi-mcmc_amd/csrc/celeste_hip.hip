@@ -97,6 +97,7 @@ static int fail(int code, const char *fmt, ...) {
 #include "k_patch_ll.h"
 #include "k_slice_gen.h"
 #include "k_type_move.h"
+#include "k_hmc.h"
 #include "k_estep.h"
 #include "k_grad.h"
 #include "k_patch_grad.h"
@@ -2454,6 +2455,163 @@ static int slice_type_move(cel_images *im, cel_sources *src, const int32_t *chai
     return CEL_OK;
 }
 
+// The HMC step (k_hmc.h): cel_slice_sample's param 3, after its refusals.  Every running chain's trajectory is queued on the
+// stream -- per leapfrog step the gradient form's two launches on the proposal set (one slot per chain) and one k_hmc_step --,
+// then q0 and qL are scored as the type move scores its two slots; one synchronisation for the job counts, one readback.
+static int slice_hmc(cel_images *im, cel_sources *src, const int32_t *chain_ids, const double *dirs, int numdir, double eps,
+                     double phi_max, uint64_t seed, int L, double *x_out, double *llh_out, int64_t *stats) {
+    if (!dirs || numdir != 2 * HMC_D)
+        return fail(CEL_ERR_INVALID, "cel_slice_sample: the HMC step (param 3) needs dirs = S rows of (momentum[6], inverse mass[6]) and numdir = 12");
+    cel_ctx *c = im->ctx;
+    if (c->slice_conditional == 1)
+        return fail(CEL_ERR_INVALID, "cel_slice_sample: the HMC step (param 3): the exact conditional's stamp-mass term has no analytic derivative yet "
+                                     "(CEL_OPT_SLICE_CONDITIONAL = 0 only)");
+    if (im->win_y0 != 0 || im->full_H != im->H)
+        return fail(CEL_ERR_INVALID, "cel_slice_sample: the HMC step (param 3) is not supported on an image set with a row window "
+                                     "(cel_images_set_window): the gradient form refuses it");
+    if (L > 1024) return fail(CEL_ERR_INVALID, "cel_slice_sample: the HMC step (param 3) takes 1 <= max_rounds <= 1024 leapfrog steps");
+    if (!std::isfinite(eps)) return fail(CEL_ERR_INVALID, "cel_slice_sample: the HMC step's eps (sigma) must be finite");
+    const int B = im->B;
+    const int64_t S = src->S;
+    // a running chain's momentum and inverse mass (the entries it reads: a star's are 0, 1; where the host does not know the
+    // types, all six)
+    const bool types = (int64_t)src->h_type.size() == S;
+    for (int64_t s = 0; s < S; s++) {
+        if (chain_ids && chain_ids[s] < 0) continue;
+        const int t = types ? src->h_type[(size_t)s] : 1;
+        if (t != 0 && t != 1) continue;
+        for (int i = 0; i < (t == 1 ? HMC_D : 2); i++) {
+            const double p0 = dirs[2 * HMC_D * s + i], m = dirs[2 * HMC_D * s + HMC_D + i];
+            if (!std::isfinite(p0)) return fail(CEL_ERR_INVALID, "cel_slice_sample: the HMC step's momentum %d of chain %lld is not finite", i, (long long)s);
+            if (!std::isfinite(m) || m < 0.0)
+                return fail(CEL_ERR_INVALID, "cel_slice_sample: the HMC step's inverse mass %d of chain %lld is negative or not finite", i, (long long)s);
+        }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const int ostr = (c->variant != 0) ? PLL_PARTS : 1;
+    const bool lists = c->variant != 0;
+    // one allocation, carved (Carver: once for the size, once for the pointers)
+    Hmc hm;
+    double *d_dirs, *d_ll, *d_sums, *d_grad, *d_out;
+    int *d_owner, *d_owner2, *d_ids, *d_list, *d_list_nz, *d_flags, *d_flag;
+    auto carve = [&](char *base) {
+        Carver k{base};
+        const size_t n = (size_t)S;
+        hm.q = k.take<double>(HMC_D * n);
+        hm.p = k.take<double>(HMC_D * n);
+        hm.p0 = k.take<double>(HMC_D * n);
+        hm.im = k.take<double>(HMC_D * n);
+        hm.log_u = k.take<double>(n);
+        hm.k0 = k.take<double>(n);
+        hm.pri = k.take<double>(2 * n);
+        d_dirs = k.take<double>(2 * HMC_D * n);
+        d_ll = k.take<double>(2 * n * B * ostr);
+        d_sums = k.take<double>((size_t)GRAD_NS * PGRAD_PARTS * n * B);      // k_patch_grad's sums per (chain, band, part)
+        d_grad = k.take<double>(n * (7 + B));                                // the mode-8 rows
+        d_out = k.take<double>((2 * HMC_D + 1) * n);          // q and the momentum per chain, then log alpha per chain
+        d_flag = k.take<int>(n);                              // right behind d_out, and the evaluations behind it: one readback
+        hm.nev = k.take<int>(n);
+        hm.run = k.take<int>(n);
+        hm.dead = k.take<int>(n);
+        d_owner = k.take<int>(n);
+        d_owner2 = k.take<int>(2 * n);
+        d_ids = k.take<int>(n);
+        d_list = k.take<int>(lists ? 2 * n * B * PLL_PARTS : 0);
+        d_list_nz = k.take<int>(lists ? 2 * n * B * PLL_PARTS : 0);
+        d_flags = k.take<int>(8, 16);                         // [1] error bits, [4] / [5] dense / photon-list blocks
+        return k.off;
+    };
+    const size_t need = carve(nullptr);
+    HIP_TRY(im->d_sgen.grow(need, need + need / 4, st));
+    carve(im->d_sgen);
+    { int rp = ensure_proposals(c, im->sgen_prop, 2 * S, B); if (rp) return rp; }
+    cel_sources *prop = im->sgen_prop.get();
+    const int64_t P = 2 * S;
+    if (S == 0) {
+        if (stats) { stats[0] = L; stats[1] = 0; stats[2] = 0; stats[3] = 0; }
+        return CEL_OK;
+    }
+    { int rr = ensure_recs(im, P * B); if (rr) return rr; }  // (the records of both proposal sets: nothing grows between the launches)
+    HIP_TRY(hipMemcpyAsync(d_dirs, dirs, sizeof(double) * 2 * HMC_D * S, hipMemcpyHostToDevice, st));
+    if (chain_ids) HIP_TRY(hipMemcpyAsync(d_ids, chain_ids, sizeof(int) * S, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));                        // pageable sources must stay valid
+    HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(int) * 8, st));
+    const unsigned g256 = (unsigned)((S + 255) / 256), j256 = (unsigned)((S * B + 255) / 256);
+    hipLaunchKernelGGL(k_hmc_fill, dim3(g256), dim3(256), 0, st, hm, S, B, phi_max, (const int *)src->d_type, (const double *)src->d_radec,
+                       (const double *)src->d_counts, (const double *)src->d_shape, (const double *)d_dirs,
+                       chain_ids ? (const int *)d_ids : (const int *)nullptr, (const int64_t *)im->d_soff, (unsigned long long)seed,
+                       prop->d_type, prop->d_radec, prop->d_counts, prop->d_shape, d_owner, d_flags + 1);
+    int64_t launches = 1;
+    const bool use_nz = im->split.nz_valid && c->variant != 0;
+    int64_t n_dense = P * B, n_nz = 0;
+    int *h_flags = c->mail->sh.slice_flags;
+    if (lists) {                                              // the two slots' blocks of every running chain (k_tm_jobs on this step's `run`)
+        TypeMove view{nullptr, nullptr, nullptr, hm.run};
+        const int64_t live = chains_here(chain_ids, S);
+        hipLaunchKernelGGL(k_tm_jobs, dim3(j256), dim3(256), 0, st, view, S, B, (const int *)(use_nz ? im->d_nzmode : nullptr),
+                           (const int *)im->d_nnz, (const int4 *)im->d_snz, (live * 2 * B <= 8192) ? 1 : 0, d_list, d_flags + 4,
+                           d_list_nz, d_flags + 5, (int *)nullptr, (int *)nullptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * 6, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        n_dense = h_flags[4]; n_nz = h_flags[5];
+        launches++;
+    }
+    // L + 1 gradients, a step behind each but the last: nothing here depends on what the device finds
+    int rc = CEL_OK;
+    for (int l = 0; l <= L; l++) {
+        prop->S = S;
+        prop->all_rows_changed(true);
+        if ((rc = run_prep(im, prop, d_owner, 1))) return rc; // the patch limits are fixed: no boxes
+        const int pi = prof_begin(c, CEL_K_PATCH_LL);
+        hipLaunchKernelGGL((k_patch_grad<0, int>), dim3((unsigned)(S * B * PGRAD_PARTS)), dim3(64), 0, st, im->d_bands, B, S, im->d_recs,
+                           (const int *)d_owner, (const int4 *)im->d_sbox, (const int64_t *)im->d_soff, (const int *)im->d_samp,
+                           (const double *)im->d_nelec, im->H, im->W, d_sums);
+        hipLaunchKernelGGL(k_patch_grad_chain, dim3(g256), dim3(256), 0, st, im->d_bands, B, S, im->d_recs, (const int *)d_owner,
+                           (const int4 *)im->d_sbox, (const int *)prop->d_type, (const double *)prop->d_shape,
+                           (const double *)prop->d_counts, (const double *)d_sums, 0, d_grad);
+        prof_end(c, pi);
+        launches += 3;
+        if (l < L) {
+            hipLaunchKernelGGL(k_hmc_step, dim3(g256), dim3(256), 0, st, hm, S, B, l == 0 ? 1 : 0, eps, phi_max, (const int *)src->d_type,
+                               (const double *)d_grad, prop->d_radec, prop->d_shape, d_owner);
+            launches++;
+        }
+    }
+    hipLaunchKernelGGL(k_hmc_slots, dim3(g256), dim3(256), 0, st, hm, S, B, eps, phi_max, (const int *)src->d_type, (const double *)src->d_radec,
+                       (const double *)src->d_counts, (const double *)src->d_shape, (const double *)d_grad, prop->d_type, prop->d_radec,
+                       prop->d_counts, prop->d_shape, d_owner2);
+    prop->S = P;
+    prop->all_rows_changed(true);
+    if ((rc = run_prep(im, prop, d_owner2, 1))) return rc;
+    launches += 2 + launch_resident_ll(c, im, P, d_owner2, d_ll, use_nz, {n_dense, d_list, nullptr}, {n_nz, d_list_nz, nullptr}, nullptr);
+    hipLaunchKernelGGL(k_hmc_decide, dim3(g256), dim3(256), 0, st, hm, S, B, ostr, (const double *)d_ll, (const int *)src->d_type,
+                       (double *)src->d_radec, (double *)src->d_shape, d_out, d_flag, d_flags + 1);
+    launches++;
+    HIP_TRY(hipGetLastError());
+    src->all_rows_changed(false);         // the catalogue on the device has new locations and shapes; the types stand
+    // one readback: the rows, log alpha, the flags and the evaluations lie one behind the other
+    static_assert(sizeof(double) == 2 * sizeof(int), "the readback's layout");
+    const int64_t nd = (2 * HMC_D + 1) * S;
+    std::vector<double> back((size_t)(nd + S));
+    HIP_TRY(hipMemcpyAsync(back.data(), d_out, sizeof(double) * nd + sizeof(int) * 2 * S, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int *hf = reinterpret_cast<const int *>(back.data() + nd), *hn = hf + S;
+    int64_t evals = 0, accepted = 0;
+    for (int64_t s = 0; s < S; s++) {
+        evals += hn[s];
+        accepted += hf[s] == 1;
+    }
+    if (x_out) memcpy(x_out, back.data(), sizeof(double) * 2 * HMC_D * S);
+    if (llh_out) memcpy(llh_out, back.data() + 2 * HMC_D * S, sizeof(double) * S);
+    if (stats) { stats[0] = L; stats[1] = evals; stats[2] = accepted; stats[3] = launches; }
+    if (h_flags[1] & 1)
+        return fail(CEL_ERR_INVALID, "cel_slice_sample: the HMC step found a state outside its own conditional (its current row scores -inf)");
+    return CEL_OK;
+}
+
 // The general slice sampler (k_slice_gen.h): random directions, stepping out by doubling, D = 2 or 4.
 int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t *chain_ids, const double *dirs, int numdir,
                      int step_out, int max_steps_out, double sigma, double phi_max, uint64_t seed, int max_rounds,
@@ -2468,9 +2626,10 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
                                      "with a row window (cel_images_set_window): its cover test is not window-relative");
     if (src->B != im->B || src->ctx != im->ctx) return fail(CEL_ERR_INVALID, "sources do not match images");
     { int rs = need_resident_split(im, src, "cel_slice_sample"); if (rs) return rs; }
-    if (param != 0 && param != 1 && param != 2) return fail(CEL_ERR_INVALID, "cel_slice_sample: param must be 0 (location), 1 (shape) or 2 (type)");
+    if (param < 0 || param > 3) return fail(CEL_ERR_INVALID, "cel_slice_sample: param must be 0 (location), 1 (shape), 2 (type) or 3 (HMC)");
     if (!(sigma > 0.0) || max_rounds < 1 || max_steps_out < 0) return fail(CEL_ERR_INVALID, "cel_slice_sample: sigma and max_rounds must be positive");
     if (param == 2) return slice_type_move(im, src, chain_ids, dirs, numdir, seed, x_out, llh_out, stats);
+    if (param == 3) return slice_hmc(im, src, chain_ids, dirs, numdir, sigma, phi_max, seed, max_rounds, x_out, llh_out, stats);
     const int D = param ? 4 : 2;
     const int compwise = dirs ? 0 : 1;
     const int ndir = compwise ? D : numdir;

@@ -489,6 +489,35 @@ class ImageSet(object):
         return (x[:, 0].astype(np.int32), np.ascontiguousarray(x[:, 1:]), la,
                 dict(evals=int(stats[1]), accepted=int(stats[2]), launches=int(stats[3])))
 
+    def hmc_step(self, sources, p0, imass, eps, steps, seed, phi_max=180., chain_ids=None):
+        """One HMC update of every source's location and shape at once, on the device (cel_slice_sample, param 3):
+        q = (ra, dec, theta, sigma, phi, rho), a star in (ra, dec) only, counts fixed, `steps` leapfrog steps of size eps against
+        the resident split under the reference's conditional.  p0 (S, 6): the momentum, refreshed by the caller; imass (S, 6):
+        the inverse mass (0 freezes a coordinate).  phi_max > 0: the built-in shape prior and its bound on phi.  Accepted rows
+        replace the sources' location and shape on the device.
+        -> (q[S,6], p[S,6], log_alpha[S], dict(steps, evals, accepted, launches)): p is the momentum to carry on with (the
+        trajectory's on accept, -p0 on reject); log_alpha is NaN for a chain left alone"""
+        S = sources.S
+        if p0 is None or imass is None:
+            raise ValueError("hmc_step needs the momentum p0 (S, 6) and the inverse mass imass (S, 6)")
+        p0, imass = L.f64(p0), L.f64(imass)
+        if p0.shape != (S, 6) or imass.shape != (S, 6):
+            raise ValueError("p0 and imass must be (S, 6)")
+        dirs = np.ascontiguousarray(np.concatenate([p0, imass], axis=1))
+        ids = None
+        if chain_ids is not None:
+            ids = np.ascontiguousarray(chain_ids, dtype=np.int32)
+            if ids.shape != (S,):
+                raise ValueError("chain_ids must have one entry per source")
+        x, la = np.zeros((S, 12)), np.zeros(S)
+        stats = np.zeros(4, dtype=np.int64)
+        # (CEL_OPT_SLICE_CONDITIONAL is left as the context has it: under the exact conditional the library refuses the step)
+        L.check(L.lib().cel_slice_sample(self._h, sources._h, 3, None if ids is None else ids.ctypes.data_as(L.c_int32_p),
+                                         L.dptr(dirs), 12, 0, 0, float(eps), float(phi_max), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                         int(steps), L.dptr(x), L.dptr(la), stats.ctypes.data_as(L.c_int64_p)))
+        return (np.ascontiguousarray(x[:, :6]), np.ascontiguousarray(x[:, 6:]), la,
+                dict(steps=int(stats[0]), evals=int(stats[1]), accepted=int(stats[2]), launches=int(stats[3])))
+
     def sample_sums(self):
         """photons attributed to every (source, band) by the resident split -> (S, B)"""
         S, tot = C.c_int64(0), C.c_int64(0)

@@ -539,7 +539,40 @@ int cel_slice_locations(cel_images *img, cel_sources *src, const int32_t *chain_
  *   stats      {1, scored slots (two per running chain), accepted moves, likelihood launches}
  * A proposal the cover test refuses scores -inf and is rejected.  A running chain whose CURRENT row scores -inf (it cannot
  * after a full-box split) stays where it is and the call returns CEL_ERR_INVALID behind the other chains' moves.  The same
- * refusals as params 0 and 1: a masked set, no resident split of these sources, under the exact conditional a row window. */
+ * refusals as params 0 and 1: a masked set, no resident split of these sources, under the exact conditional a row window.
+ *
+ * param 3: one HMC update (hmc_sample_galaxy_params, CelestePy/celeste_mcmc.py:281-331: util/infer/hmc.py's leapfrog with
+ * num_iter = 1) of every source's location and shape at once, q = (ra, dec, theta, sigma, phi, rho) with ra and dec in degrees;
+ * a star moves in (ra, dec) only.  The counts are held fixed: their conditional is a Gamma, which cel_flux_conditionals samples
+ * exactly -- HMC on it would be strictly worse.  The target v(q) is the score params 0-2 form under the reference's conditional
+ * (the bands' resident mode-0 values added in band order from 0.0, a band's parts first; for a galaxy under phi_max > 0 plus
+ * the log-prior of param 1); its gradient g(q) is slots 1-6 of cel_patch_loglik_multi's mode-8 row of the proposal, the prior's
+ * derivative 2 / sigma^3 - 4 / sigma added to the sigma entry; a star's entries 2-5 are 0.  Every chain's whole trajectory is
+ * queued on the stream, the gradients never leave the device, and there is one readback at the end:
+ *     p = p0 + (0.5 eps) g(q0)
+ *     for l in 0 .. L-1:   q = q + (eps imass) p;   p = p + (l == L-1 ? 0.5 eps : eps) g(q)
+ *     K(p) = 0.5 sum_i imass_i (p_i p_i)                  (added in coordinate order from 0.0)
+ *     log alpha = (v(qL) - v(q0)) + (K(p0) - K(pL));      accepted iff log(u) < log alpha
+ * with u the FIRST uniform of the chain's SplitMix64 stream keyed by (seed, chain id), as param 2 forms it.  Support: theta in
+ * (0,1), sigma > 0, rho in (0,1) always, phi in (0, phi_max) when phi_max > 0.  A trajectory with a position outside the support,
+ * or a position or gradient entry that is not finite, is dead: it is never rendered again and is rejected with log alpha = -inf.
+ * The arguments are re-read:
+ *   dirs       S*12 (host, required; numdir must be 12): per chain the momentum p0[6], then the inverse mass imass[6] (>= 0 and
+ *              finite; 0 freezes that coordinate).  A star's entries 2-5 are ignored.  A p0 that is not finite, or an imass
+ *              that is negative or not finite, in an entry that a star or galaxy with chain_ids[s] >= 0 reads gives
+ *              CEL_ERR_INVALID before any launch
+ *   sigma      the step size eps > 0;  max_rounds: the leapfrog steps L, 1 <= L <= 1024;  phi_max: as param 1
+ *   chain_ids  as above; a source without a sample patch in any band and a source of type 2 are left alone too: their rows
+ *              stay bit for bit
+ *   step_out, max_steps_out: not read
+ *   x_out      S*12 (host, may be NULL): the new q, then the momentum to carry on with: pL on accept, -p0 on reject (the
+ *              reference's negate, accept, negate); a chain left alone: its row and its p0.  An accepted row REPLACES src's
+ *              location and (a galaxy's) shape on the device; types and counts are untouched
+ *   llh_out    S (host, may be NULL): log alpha, NaN for a chain left alone
+ *   stats      {L, gradient evaluations (L + 1 per chain that runs to the end), accepted updates, launches}
+ * A running chain whose CURRENT row scores -inf stays where it is and the call returns CEL_ERR_INVALID behind the other chains'
+ * moves.  Refused before any launch, the outputs untouched: what params 0-2 refuse; an image set with a row window (the gradient
+ * form refuses it); CEL_OPT_SLICE_CONDITIONAL = 1 (the exact conditional's stamp-mass term has no analytic derivative yet). */
 int cel_slice_sample(cel_images *img, cel_sources *src, int param, const int32_t *chain_ids, const double *dirs, int numdir,
                      int step_out, int max_steps_out, double sigma, double phi_max, uint64_t seed, int max_rounds,
                      double *x_out, double *llh_out, int64_t *stats);
