@@ -217,8 +217,15 @@ class ModelGibbs(object):
 
     def __init__(self, fields, typ, u, fluxes, shape, seed=0, flux_a_0=5., flux_b_0=.005, slice_args=None, engine="auto",
                  deal=None, shape_args=None, shape_logprior=None, phi_period=180., shape_mass="reference", conditional="reference",
-                 mask="refuse", type_log_odds=0.0):
+                 mask="refuse", type_log_odds=0.0, grad_route="dense"):
         self.fields = list(fields)
+        # grad_route: where the resident gradients of resample_hmc and location_loglik_grad are summed.  "dense": over the sample
+        # patches (k_patch_grad.h).  "photons": at the split's photon lists (k_patch_grad_nz.h; CEL_OPT_PHOTON_LISTS + 4 around those
+        # calls): the same terms in another order, so the values agree to rounding and the host and device engines, which take the
+        # same gradients, stay bit for bit.
+        if grad_route not in ("dense", "photons"):
+            raise ValueError("grad_route must be 'dense' or 'photons'")
+        self.grad_route = grad_route
         # the type step's log prior odds, galaxy : star (resample_types; sweep(types=True))
         self.type_log_odds = float(type_log_odds)
         self.type_engine = None                 # "host" / "device": the type step's engine where it is not `engine`'s (tools/type_move_cost.py)
@@ -402,6 +409,29 @@ class ModelGibbs(object):
             finally:
                 for ctx, v in was:
                     ctx.set_option(_lib.CEL_OPT_HONOUR_MASK, v)
+        return cm()
+
+    def _grad_route(self):
+        """grad_route="photons": the gradient bit of CEL_OPT_PHOTON_LISTS (4 on top of the caller's 0 or 1) set on every field's
+        context around a resident gradient call, and what the caller had restored behind it -- as _honour_mask does it.  A
+        context under 2 (no lists are built) is left alone: its gradients are dense.  Otherwise nothing."""
+        import contextlib
+        from . import _lib
+
+        @contextlib.contextmanager
+        def cm():
+            was = []
+            try:
+                if self.grad_route == "photons":
+                    for ctx in {id(f.iset.ctx): f.iset.ctx for f in self.fields}.values():
+                        v = ctx.get_option(_lib.CEL_OPT_PHOTON_LISTS)
+                        if v in (0, 1):
+                            was.append((ctx, v))
+                            ctx.set_option(_lib.CEL_OPT_PHOTON_LISTS, v + 4)
+                yield
+            finally:
+                for ctx, v in was:
+                    ctx.set_option(_lib.CEL_OPT_PHOTON_LISTS, v)
         return cm()
 
     def counts(self, f, fluxes=None, idx=None):
@@ -608,7 +638,8 @@ class ModelGibbs(object):
         """location_loglik with its analytic gradient in (ra, dec), per degree, summed over fields (the gradient form of
         cel_patch_loglik_multi against the resident patches) -> (ll[P], g[P, 2]); ll is location_loglik's value, bit for bit.
         shape_grad=True: the six coordinates (ra, dec, theta, sigma, phi, rho) -> (ll[P], g[P, 6]) (a star's last four: 0).
-        The exact conditional's mass term has no derivative here: conditional="exact" raises."""
+        The exact conditional's mass term has no derivative here: conditional="exact" raises.
+        grad_route="photons": the gradients are summed at the split's photon lists (ll is unchanged)."""
         from . import field as _field
         if self.conditional == "exact":
             raise ValueError("location_loglik_grad: the exact conditional's stamp-mass term has no analytic derivative yet "
@@ -625,7 +656,8 @@ class ModelGibbs(object):
             cts = getattr(f, "_counts", None)
             pc = self.counts(f, idx=idx) if cts is None else cts[idx]
             f.prop.set(typ, U, pc, shape)
-            l, gr, _, gs = f.iset.patch_loglik_resident_grad(f.prop, owner)
+            with self._grad_route():
+                l, gr, _, gs = f.iset.patch_loglik_resident_grad(f.prop, owner)
             ll += l
             g += np.concatenate([gr, gs], axis=1) if shape_grad else gr
         return ll, g
@@ -962,7 +994,8 @@ class ModelGibbs(object):
         the normals of the streams of step_seed("hmc", 1) (refresh=0: a fresh momentum every call); a coordinate with
         imass = 0 is frozen and its momentum is 0.  imass: (6,) or (S, 6), default hmc_default_imass(); eps default 0.5, steps
         default 8.  hmc_preset("reference") holds the reference's numbers.  phi is wrapped afterwards, as resample_shapes wraps it.
-        The exact conditional's mass term has no derivative yet: conditional="exact" raises."""
+        The exact conditional's mass term has no derivative yet: conditional="exact" raises.
+        grad_route="photons": both engines take their gradients at the split's photon lists."""
         import time
         from .util.infer.slicesample import ChainStreams
         from .util.infer.hmc import hmc_lockstep
@@ -1003,7 +1036,8 @@ class ModelGibbs(object):
             f = self.fields[0]
             sset = self._sources(f)
             ids = np.where(runs, ids_all, -1).astype(np.int32)
-            q, pn, _, st = f.iset.hmc_step(sset, p, im, eps, steps, seed, phi_max=self.phi_period, chain_ids=ids)
+            with self._grad_route():
+                q, pn, _, st = f.iset.hmc_step(sset, p, im, eps, steps, seed, phi_max=self.phi_period, chain_ids=ids)
             evals, accepted = st["evals"], st["accepted"]
         else:
             q, pn = q0.copy(), p.copy()

@@ -101,6 +101,7 @@ static int fail(int code, const char *fmt, ...) {
 #include "k_estep.h"
 #include "k_grad.h"
 #include "k_patch_grad.h"
+#include "k_patch_grad_nz.h"
 #include "k_split.h"
 #include "k_slice.h"
 
@@ -198,6 +199,7 @@ struct cel_ctx {
     int split_reuse = getenv("CEL_SPLIT_REUSE") ? std::min(std::max(atoi(getenv("CEL_SPLIT_REUSE")), 0), 2) : 2;      // CEL_OPT_SPLIT_REUSE (the env var: the initial value, for A/B runs): 1 = the split's totals from a model image already on the device (k_border.h), 2 = ... and the stamp masses from the split's own sums
     bool mass_reuse_of() const { return split_reuse >= 2; }
     int nz_force = 0;         // CEL_OPT_PHOTON_LISTS: 0 = per patch, whichever is estimated cheaper; 1 = every patch at its photons; 2 = never
+    bool grad_nz = false;     // ... its values 4 and 5 (= 0 / 1 for the value): the resident gradient reads the lists too (k_patch_grad_nz.h)
     int debug = 0;            // CEL_OPT_DEBUG: timing-only ablation bits handed to the render kernel (results are wrong when set)
     int tile_layout = 1;      // 0: 64 x tile_rows tiles, one lane per column (k_render)
                               // 1: 32 x 64 tiles, two component groups per column (k_render_hw)
@@ -644,8 +646,10 @@ int cel_ctx_set_option(cel_ctx *c, int key, double v) {
         c->tile_layout = (int)v;
         return CEL_OK;
     case CEL_OPT_PHOTON_LISTS:
-        if (v != 0.0 && v != 1.0 && v != 2.0) return fail(CEL_ERR_INVALID, "CEL_OPT_PHOTON_LISTS must be 0, 1 or 2");
-        c->nz_force = (int)v;
+        if (v != 0.0 && v != 1.0 && v != 2.0 && v != 4.0 && v != 5.0)
+            return fail(CEL_ERR_INVALID, "CEL_OPT_PHOTON_LISTS must be 0, 1 or 2, or 4 or 5 (0 / 1 and the resident gradient at the photons)");
+        c->nz_force = (int)v & 3;
+        c->grad_nz = v >= 4.0;
         return CEL_OK;
     case CEL_OPT_SPLIT_REUSE:
         if (v != 0.0 && v != 1.0 && v != 2.0) return fail(CEL_ERR_INVALID, "CEL_OPT_SPLIT_REUSE must be 0, 1 or 2");
@@ -686,7 +690,7 @@ int cel_ctx_get_option(cel_ctx *c, int key, double *v) {
     case CEL_OPT_TILE_ROWS: *v = c->tile_rows; return CEL_OK;
     case CEL_OPT_TILE_TIMING: *v = c->tile_timing ? 1.0 : 0.0; return CEL_OK;
     case CEL_OPT_TILE_LAYOUT: *v = c->tile_layout; return CEL_OK;
-    case CEL_OPT_PHOTON_LISTS: *v = c->nz_force; return CEL_OK;
+    case CEL_OPT_PHOTON_LISTS: *v = c->nz_force + (c->grad_nz ? 4 : 0); return CEL_OK;
     case CEL_OPT_STAR_TILES: *v = c->star_tiles; return CEL_OK;
     case CEL_OPT_SPLIT_REUSE: *v = c->split_reuse; return CEL_OK;
     case CEL_OPT_DEBUG: *v = c->debug; return CEL_OK;
@@ -1655,6 +1659,7 @@ struct PllCall {
     int *d_owner = nullptr;
     double *d_data = nullptr, *d_out = nullptr;
     const int *i_data = nullptr;                    // the resident split's int32 photon counts (mode 0); everything else is double
+    bool owned = true;                              // false: cel_patch_loglik's single source (its gradient keeps the dense kernel)
 };
 // step 1: the argument checks and the boxes.  k.P == 0 with CEL_OK: nothing to score.
 static int pll_check(cel_images *im, cel_sources *src, const int32_t *owner, int64_t NB, const int32_t *boxes,
@@ -1795,6 +1800,12 @@ static void pll_sum(const std::vector<double> &hout, int64_t P, int B, int npart
     }
 }
 
+// The resident mode-0 gradient's route, read when a gradient is launched: the photon lists (k_patch_grad_nz.h) iff the option's
+// bit is set and the split's lists stand -- a split made under CEL_OPT_PHOTON_LISTS = 2, a direct-form split and a frame of
+// 65 536 columns or rows have none, and the dense kernel runs as the value's does.  CEL_OPT_KERNEL is not read.
+// `multi`: cel_patch_loglik_multi or the HMC step (cel_patch_loglik's single source keeps the dense kernel).
+static bool grad_at_photons(const cel_images *im, bool multi) { return multi && im->ctx->grad_nz && im->split.nz_valid; }
+
 // step 5, the gradient form (k_patch_grad.h): the same records, boxes, offsets, owners and staged data, still in their slots;
 // `val` is mode m's value per proposal, slot 0 of its row
 static int pll_gradient(cel_images *im, cel_sources *src, const PllCall &k, const std::vector<double> &val, double *ll_out) {
@@ -1812,7 +1823,11 @@ static int pll_gradient(cel_images *im, cel_sources *src, const PllCall &k, cons
 #define PGRAD_LAUNCH(M, TZ, DATA)                                                                                              \
     hipLaunchKernelGGL((k_patch_grad<M, TZ>), grid, dim3(64), 0, c->stream, im->d_bands, B, P, im->d_recs, (const int *)k.d_owner, \
                        (const int4 *)k.d_box, (const int64_t *)k.d_off, (const TZ *)(DATA), (const double *)im->d_nelec, im->H, im->W, d_sums)
-    if (k.i_data) PGRAD_LAUNCH(0, int, k.i_data);
+    // the resident split's patches: at their photon lists when CEL_OPT_PHOTON_LISTS asks for it (4, 5) and the lists stand
+    if (k.i_data && grad_at_photons(im, k.owned))
+        hipLaunchKernelGGL(pgrad_nz_sums, grid, dim3(64), 0, c->stream, im->d_bands, B, P, im->d_recs, (const int *)k.d_owner,
+                           (const int4 *)k.d_box, (const int64_t *)im->d_nzoff, (const NzEntry *)im->d_nzlist, d_sums);
+    else if (k.i_data) PGRAD_LAUNCH(0, int, k.i_data);
     else if (mode == 0) PGRAD_LAUNCH(0, double, k.d_data);
     else if (mode == 1) PGRAD_LAUNCH(1, double, k.d_data);
     else PGRAD_LAUNCH(2, double, k.d_data);
@@ -1830,10 +1845,10 @@ static int pll_gradient(cel_images *im, cel_sources *src, const PllCall &k, cons
     return CEL_OK;
 }
 
-int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owner, int64_t NB,
-                           const int32_t *boxes, const int64_t *offsets, const double *data, int mem, int mode_arg,
-                           double *ll_out) {
+static int pll_run(cel_images *im, cel_sources *src, const int32_t *owner, int64_t NB, const int32_t *boxes, const int64_t *offsets,
+                   const double *data, int mem, int mode_arg, double *ll_out, bool multi) {
     PllCall k;
+    k.owned = multi;
     int rc = pll_check(im, src, owner, NB, boxes, offsets, data, mode_arg, ll_out, k);
     if (rc || k.P == 0) return rc;
     if ((rc = run_prep(im, src)) || (rc = pll_stage(im, owner, offsets, data, mem, k))) return rc;
@@ -1850,9 +1865,15 @@ int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owne
     return k.grad ? pll_gradient(im, src, k, val, ll_out) : CEL_OK;
 }
 
+int cel_patch_loglik_multi(cel_images *im, cel_sources *src, const int32_t *owner, int64_t NB,
+                           const int32_t *boxes, const int64_t *offsets, const double *data, int mem, int mode_arg,
+                           double *ll_out) {
+    return pll_run(im, src, owner, NB, boxes, offsets, data, mem, mode_arg, ll_out, true);
+}
+
 int cel_patch_loglik(cel_images *im, cel_sources *src, const int32_t *boxes, const int64_t *offsets,
                      const double *data, int mem, int mode, double *ll_out) {
-    return cel_patch_loglik_multi(im, src, nullptr, 1, boxes, offsets, data, mem, mode, ll_out);
+    return pll_run(im, src, nullptr, 1, boxes, offsets, data, mem, mode, ll_out, false);
 }
 
 // (Round 4 measured this kernel on a SECOND stream beside the photon split -- its inputs are ready before the split when the
@@ -2559,15 +2580,22 @@ static int slice_hmc(cel_images *im, cel_sources *src, const int32_t *chain_ids,
         launches++;
     }
     // L + 1 gradients, a step behind each but the last: nothing here depends on what the device finds
+    // (their route -- the dense patches or the photon lists -- is chosen once for the call: grad_at_photons)
+    const bool grad_nz = grad_at_photons(im, true);
     int rc = CEL_OK;
     for (int l = 0; l <= L; l++) {
         prop->S = S;
         prop->all_rows_changed(true);
         if ((rc = run_prep(im, prop, d_owner, 1))) return rc; // the patch limits are fixed: no boxes
         const int pi = prof_begin(c, CEL_K_PATCH_LL);
-        hipLaunchKernelGGL((k_patch_grad<0, int>), dim3((unsigned)(S * B * PGRAD_PARTS)), dim3(64), 0, st, im->d_bands, B, S, im->d_recs,
-                           (const int *)d_owner, (const int4 *)im->d_sbox, (const int64_t *)im->d_soff, (const int *)im->d_samp,
-                           (const double *)im->d_nelec, im->H, im->W, d_sums);
+        if (grad_nz)
+            hipLaunchKernelGGL(pgrad_nz_sums, dim3((unsigned)(S * B * PGRAD_PARTS)), dim3(64), 0, st, im->d_bands, B, S, im->d_recs,
+                               (const int *)d_owner, (const int4 *)im->d_sbox, (const int64_t *)im->d_nzoff,
+                               (const NzEntry *)im->d_nzlist, d_sums);
+        else
+            hipLaunchKernelGGL((k_patch_grad<0, int>), dim3((unsigned)(S * B * PGRAD_PARTS)), dim3(64), 0, st, im->d_bands, B, S, im->d_recs,
+                               (const int *)d_owner, (const int4 *)im->d_sbox, (const int64_t *)im->d_soff, (const int *)im->d_samp,
+                               (const double *)im->d_nelec, im->H, im->W, d_sums);
         hipLaunchKernelGGL(k_patch_grad_chain, dim3(g256), dim3(256), 0, st, im->d_bands, B, S, im->d_recs, (const int *)d_owner,
                            (const int4 *)im->d_sbox, (const int *)prop->d_type, (const double *)prop->d_shape,
                            (const double *)prop->d_counts, (const double *)d_sums, 0, d_grad);

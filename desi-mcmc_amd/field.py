@@ -740,7 +740,9 @@ class ImageSet(object):
 
     def patch_loglik_resident_grad(self, proposals, owner, isolated=False):
         """patch_loglik_resident and its analytic gradient: against the resident sample patches (isolated=True: against the
-        observed image on the same boxes).  -> (ll[P], g_radec[P,2], g_counts[P,B], g_shape[P,4])"""
+        observed image on the same boxes).  -> (ll[P], g_radec[P,2], g_counts[P,B], g_shape[P,4])
+        Where the gradient is summed is the context's choice, not an argument: under CEL_OPT_PHOTON_LISTS = 4 or 5 (and not
+        isolated) at the split's photon lists, otherwise over the patches; the two agree to rounding and ll is the same bits."""
         if isolated:
             self._refuse_masked("patch_loglik_resident(isolated=True)")
         owner = np.ascontiguousarray(owner, dtype=np.int32)

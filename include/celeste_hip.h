@@ -144,7 +144,11 @@ enum {
     CEL_OPT_PHOTON_LISTS = 9, /* how the conditional likelihoods read a device-resident photon split: 0 (default) = per
                                patch, at the pixels that hold a photon or densely, whichever the layout pass estimates
                                cheaper; 1 = every patch at its photons; 2 = never (no lists are built).  The values
-                               agree to rounding; set it before cel_photon_split */
+                               agree to rounding; set it before cel_photon_split.  4 and 5 = as 0 / as 1 for the value, AND
+                               the resident gradient (cel_patch_loglik_multi's resident mode 8, cel_slice_sample's param 3)
+                               sums at the photon lists (k_patch_grad_nz.h) instead of over the patches: the same terms in
+                               another order, equal to rounding.  That bit is read when a gradient is launched; without
+                               lists (a split made under 2) the dense kernel runs.  3, 6 and anything else is refused */
     CEL_OPT_STAR_TILES = 10,/* which kernel renders the field of a catalogue WITHOUT galaxies (known when the types
                                came from host memory): 0 = the general one (k_render_hw); 1 (default) = k_render_stars
                                -- the same 32 x 64 tiles taken in two column halves, 8 KB of accumulator instead of 16,
@@ -431,7 +435,10 @@ int cel_render_stamps(cel_images *img, cel_sources *src, int band, int scaled, c
  *            nothing (every component at every pixel) and gives the same bits under CEL_OPT_KERNEL 0 and 1 and on every call.
  *            Refused with CEL_ERR_INVALID before anything is launched or written: whatever mode m refuses for the same
  *            arguments; 8 + 3, 8 + 4 and any other value; an image set with a row window (cel_images_set_window), as
- *            cel_loglik_grad refuses it.  The launches are timed under CEL_K_PATCH_LL. */
+ *            cel_loglik_grad refuses it.  The launches are timed under CEL_K_PATCH_LL.
+ *            Under CEL_OPT_PHOTON_LISTS = 4 or 5 cel_patch_loglik_multi's RESIDENT mode 8 takes slots 1 .. at the split's photon
+ *            lists (k_patch_grad_nz.h: the same sums in another order, nothing dropped, the same bits under CEL_OPT_KERNEL 0 and 1
+ *            and on every call); explicit patches, modes 9 and 10 and cel_patch_loglik keep the dense kernel. */
 int cel_patch_loglik(cel_images *img, cel_sources *src, const int32_t *boxes, const int64_t *offsets,
                      const double *data, int mem, int mode, double *ll_out);
 /* The same for proposals of MANY sources in one launch (a whole sweep of per-source updates):
@@ -572,7 +579,9 @@ int cel_slice_locations(cel_images *img, cel_sources *src, const int32_t *chain_
  *   stats      {L, gradient evaluations (L + 1 per chain that runs to the end), accepted updates, launches}
  * A running chain whose CURRENT row scores -inf stays where it is and the call returns CEL_ERR_INVALID behind the other chains'
  * moves.  Refused before any launch, the outputs untouched: what params 0-2 refuse; an image set with a row window (the gradient
- * form refuses it); CEL_OPT_SLICE_CONDITIONAL = 1 (the exact conditional's stamp-mass term has no analytic derivative yet). */
+ * form refuses it); CEL_OPT_SLICE_CONDITIONAL = 1 (the exact conditional's stamp-mass term has no analytic derivative yet).
+ * Under CEL_OPT_PHOTON_LISTS = 4 or 5 the L + 1 gradients are taken at the split's photon lists, as the resident mode 8 takes them
+ * then: g(q) is still that call's row bit for bit, and the launch count does not change. */
 int cel_slice_sample(cel_images *img, cel_sources *src, int param, const int32_t *chain_ids, const double *dirs, int numdir,
                      int step_out, int max_steps_out, double sigma, double phi_max, uint64_t seed, int max_rounds,
                      double *x_out, double *llh_out, int64_t *stats);

@@ -3,7 +3,10 @@
 mixed10k_2048) with a resident split, beside the host loop that makes one gradient call per leapfrog step.  Also the acceptance
 rates of the two presets on this field.  Diagnostic; not part of bench.py's contract.
 
-    (python tools/time_hmc.py; python tools/time_hmc.py test12) > profiles/hmc_time.txt
+    (python tools/time_hmc.py --route both; python tools/time_hmc.py test12 --route both) > profiles/hmc_time.txt
+
+--route dense | photons | both: where the step's gradients are summed (ModelGibbs(grad_route=)); both: the two routes in one
+process, interleaved call by call.
 
 Every time is the median of REPS calls after WARM warm-up calls (min and max beside it), wall-clock around the blocking call.
 The catalogue is put back before every call, so that each call starts from the same state.
@@ -18,9 +21,17 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import desi_mcmc_amd as cel  # noqa: E402
 from desi_mcmc_amd import celeste_mcmc, synth  # noqa: E402
 
+import argparse  # noqa: E402
+
 WARM, REPS = 3, 15
+ap = argparse.ArgumentParser()
+ap.add_argument("config", nargs="?", default="mixed10k_2048")
+ap.add_argument("--route", choices=("dense", "photons", "both"), default="dense")
+ap.add_argument("--no-host", action="store_true", help="leave out the host loop (one mode-8 call per step)")
+args = ap.parse_args()
+ROUTES = ("dense", "photons") if args.route == "both" else (args.route,)
 ctx = cel.Context(0)
-name = sys.argv[1] if len(sys.argv) > 1 else "mixed10k_2048"
+name = args.config
 if name == "test12":         # the two-band 96 x 112 scene of tests/test_hmc.py's engine test
     f = synth.SyntheticField(ctx, 12, 2, 96, 112, frac_gal=0.5, seed=23)
 else:
@@ -41,46 +52,57 @@ def timed(label, fn, before=None, reps=REPS, warm=WARM):
     return out
 
 
-def model(engine):
+def model(engine, route):
     imgs = cel.ImageSet(ctx, f.bands, f.H, f.W)
     imgs.set_nelec(f.nelec)
     gf = celeste_mcmc.GibbsField(imgs, list(range(f.B)), f.bands[:, 2], f.bands[:, 1], f.H * f.W)
-    g = celeste_mcmc.ModelGibbs([gf], f.src["type"], f.src["radec"], f.flux5(), f.src["shape"], seed=5, engine=engine)
+    g = celeste_mcmc.ModelGibbs([gf], f.src["type"], f.src["radec"], f.flux5(), f.src["shape"], seed=5, engine=engine, grad_route=route)
     g.resample_photons()
     return g
 
 
-g = model("auto")
-start = (g.u.copy(), g.shape.copy())
+g = {r: model("auto", r) for r in ROUTES}
+start = (g[ROUTES[0]].u.copy(), g[ROUTES[0]].shape.copy())
 
 
-def back(m=g):
+def back(m):
     m.u, m.shape, m._hmc_p = start[0].copy(), start[1].copy(), None
     m._sources(m.fields[0])                     # (the upload is not part of the step)
 
 
-for label, kw in (("library default (eps 0.5, 8 steps, scale-free mass)", {}), ("reference preset (eps 1e-5, 50 steps)", g.hmc_preset("reference"))):
-    steps = kw.get("steps", 8)
-    a0, e0 = g.timing["hmc_accepted"], g.timing["hmc_evals"]
-    timed("device engine, %s" % label, lambda: g.resample_hmc(**kw), before=back)
-    n = WARM + REPS
-    run = int(np.sum(g.active & (g.typ < 2)))
-    print("    acceptance %.3f (%d of %d updates), %d gradient evaluations per call"
-          % ((g.timing["hmc_accepted"] - a0) / float(n * run), g.timing["hmc_accepted"] - a0, n * run, (g.timing["hmc_evals"] - e0) // n))
-    t = []
-    for L in (1, steps):
-        k2 = dict(kw)
-        k2["steps"] = L
-        ts = []
-        for k in range(WARM + REPS):
-            back()
+def interleaved(kw):
+    """median, min, max per route of WARM + REPS calls, the routes taking turns call by call"""
+    ts = {r: [] for r in ROUTES}
+    for k in range(WARM + REPS):
+        for r in ROUTES:
+            back(g[r])
             t0 = time.perf_counter()
-            g.resample_hmc(**k2)
+            g[r].resample_hmc(**kw)
             if k >= WARM:
-                ts.append((time.perf_counter() - t0) * 1e3)
-        t.append(np.median(ts))
-    print("    per leapfrog step (median at %d steps - median at 1 step) / %d: %.3f ms" % (steps, steps - 1, (t[1] - t[0]) / (steps - 1)))
+                ts[r].append((time.perf_counter() - t0) * 1e3)
+    return ts
 
-h = model("host")
-timed("host loop (one mode-8 call per step), library default, 8 steps", lambda: h.resample_hmc(), before=lambda: back(h), reps=5, warm=1)
-timed("host loop, 1 step", lambda: h.resample_hmc(steps=1), before=lambda: back(h), reps=5, warm=1)
+
+g0 = g[ROUTES[0]]
+for label, kw in (("library default (eps 0.5, 8 steps, scale-free mass)", {}), ("reference preset (eps 1e-5, 50 steps)", g0.hmc_preset("reference"))):
+    steps = kw.get("steps", 8)
+    a0 = {r: (g[r].timing["hmc_accepted"], g[r].timing["hmc_evals"]) for r in ROUTES}
+    ts = interleaved(kw)
+    n = WARM + REPS
+    run = int(np.sum(g0.active & (g0.typ < 2)))
+    for r in ROUTES:
+        print("%-66s %9.3f ms  (%.3f .. %.3f)" % ("device engine, %s route, %s" % (r, label), np.median(ts[r]), min(ts[r]), max(ts[r])))
+        acc, ev = g[r].timing["hmc_accepted"] - a0[r][0], g[r].timing["hmc_evals"] - a0[r][1]
+        print("    acceptance %.3f (%d of %d updates), %d gradient evaluations per call" % (acc / float(n * run), acc, n * run, ev // n))
+    k1 = dict(kw)
+    k1["steps"] = 1
+    t1 = interleaved(k1)
+    for r in ROUTES:
+        print("    %s route, per leapfrog step (median at %d steps - median at 1 step) / %d: %.3f ms"
+              % (r, steps, steps - 1, (np.median(ts[r]) - np.median(t1[r])) / (steps - 1)))
+
+if not args.no_host:
+    for r in ROUTES:
+        h = model("host", r)
+        timed("host loop (one mode-8 call per step), %s route, library default, 8 steps" % r, lambda: h.resample_hmc(), before=lambda: back(h), reps=5, warm=1)
+        timed("host loop, %s route, 1 step" % r, lambda: h.resample_hmc(steps=1), before=lambda: back(h), reps=5, warm=1)

@@ -18,9 +18,18 @@ import desi_mcmc_amd as cel  # noqa: E402
 from desi_mcmc_amd import celeste_galaxy_conditionals as gc  # noqa: E402
 from desi_mcmc_amd import synth  # noqa: E402
 
+import argparse  # noqa: E402
+from desi_mcmc_amd import _lib  # noqa: E402
+
 WARM, REPS = 3, 15
+ap = argparse.ArgumentParser()
+ap.add_argument("config", nargs="?", default="mixed10k_2048")
+ap.add_argument("--route", choices=("dense", "photons", "both"), default="dense",
+                help="where the resident mode-8 gradient is summed (CEL_OPT_PHOTON_LISTS + 4 = photons); both: the two routes "
+                     "interleaved call by call in this process, and nothing else")
+args = ap.parse_args()
 ctx = cel.Context(0)
-name = sys.argv[1] if len(sys.argv) > 1 else "mixed10k_2048"
+name = args.config
 f = synth.SyntheticField.from_config(ctx, name)
 print("%s: %d sources, %d bands, %d x %d; median of %d calls after %d warm-up calls (min .. max)" % (name, f.S, f.B, f.H, f.W, REPS, WARM))
 
@@ -54,6 +63,45 @@ f.images.photon_split_resident(f.sources, seed=1)
 rs = np.random.RandomState(0)
 owner = np.arange(f.S, dtype=np.int32)
 prop = cel.SourceSet(ctx, f.S, f.B).set(f.src["type"], f.src["radec"] + rs.normal(0.0, 2e-5, size=(f.S, 2)), f.src["counts"], f.src["shape"])
+lists0 = ctx.get_option(_lib.CEL_OPT_PHOTON_LISTS)
+
+
+def set_route(route):
+    ctx.set_option(_lib.CEL_OPT_PHOTON_LISTS, lists0 + (4 if route == "photons" else 0))
+
+
+if args.route == "both":
+    # the two routes call by call: warm-up calls of each, then REPS pairs; wall-clock and the CEL_K_PATCH_LL brackets of the same calls
+    wall, devms, rows = {"dense": [], "photons": []}, {"dense": [], "photons": []}, {}
+    for k in range(WARM + REPS):
+        for route in ("dense", "photons"):
+            set_route(route)
+            ctx.profile(True)
+            t0 = time.perf_counter()
+            rows[route] = f.images.patch_loglik_resident_grad(prop, owner)
+            dt = (time.perf_counter() - t0) * 1e3
+            mean, n = ctx.profile_get("patch_ll")
+            if k >= WARM:
+                wall[route].append(dt)
+                devms[route].append(mean * n)
+    ctx.profile(False)
+    set_route("dense")
+    val = [(time.perf_counter(), f.images.patch_loglik_resident(prop, owner), time.perf_counter()) for _ in range(WARM + REPS)][WARM:]
+    vms = [(c - a) * 1e3 for a, _, c in val]
+    print("%-58s %9.3f ms  (%.3f .. %.3f)" % ("resident mode 0 (value), %d proposals" % f.S, np.median(vms), min(vms), max(vms)))
+    for route in ("dense", "photons"):
+        print("%-58s %9.3f ms  (%.3f .. %.3f)   device, CEL_K_PATCH_LL brackets: %.3f ms (%.3f .. %.3f)"
+              % ("resident mode 8, %s route, %d proposals" % (route, f.S), np.median(wall[route]), min(wall[route]), max(wall[route]),
+                 np.median(devms[route]), min(devms[route]), max(devms[route])))
+    spread = max(max(wall[r]) - min(wall[r]) for r in wall)
+    gain = np.median(wall["dense"]) - np.median(wall["photons"])
+    print("dense - photons = %.3f ms; the larger of the two runs' own ranges = %.3f ms: %s"
+          % (gain, spread, "the photon route is faster by more than that" if gain > spread else "NOT separated"))
+    a, b = [np.column_stack(r[1:]) for r in (rows["dense"], rows["photons"])]
+    print("largest |dense - photons| / column max over the rows: %.3g; values equal bit for bit: %s"
+          % (np.max(np.abs(a - b) / np.max(np.abs(a), axis=0)), np.array_equal(rows["dense"][0], rows["photons"][0])))
+    sys.exit(0)
+set_route(args.route)
 timed("resident mode 0 (value), %d proposals" % f.S, lambda: f.images.patch_loglik_resident(prop, owner))
 timed("resident mode 8 (value + gradient), %d proposals" % f.S, lambda: f.images.patch_loglik_resident_grad(prop, owner))
 d0 = device_ms(lambda: f.images.patch_loglik_resident(prop, owner))
