@@ -27,6 +27,9 @@ CEL_OPT_TAIL_LOG_SOURCE, CEL_OPT_TILE_PARTS, CEL_OPT_INCREMENTAL, CEL_OPT_SPLIT_
 CEL_OPT_HONOUR_MASK = 17
 #: what cel_slice_sample scores: 0 the reference's conditional (default), 1 the exact one (ImageSet.slice_sample(conditional=))
 CEL_OPT_SLICE_CONDITIONAL = 18
+#: which conditional the resident gradient (cel_patch_loglik_multi's resident mode 8) and the HMC step (cel_slice_sample, param 3)
+#: differentiate: 0 the reference's (default), 1 the exact one (ImageSet.patch_loglik_resident_grad / hmc_step(conditional=))
+CEL_OPT_GRAD_CONDITIONAL = 19
 #: CEL_OPT_TAIL_LOG presets.  32 (the default): a skipped component is below eps * e^-32 on its tile, model pixels
 #: agree with the reference to ~1e-13, which is what the parity tests assert (1e-10).  20: the documented fast
 #: preset for callers that need only north_star's 1e-6 -- a skipped component is below eps * 2e-9, the sum of

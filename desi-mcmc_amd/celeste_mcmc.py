@@ -217,8 +217,19 @@ class ModelGibbs(object):
 
     def __init__(self, fields, typ, u, fluxes, shape, seed=0, flux_a_0=5., flux_b_0=.005, slice_args=None, engine="auto",
                  deal=None, shape_args=None, shape_logprior=None, phi_period=180., shape_mass="reference", conditional="reference",
-                 mask="refuse", type_log_odds=0.0, grad_route="dense"):
+                 mask="refuse", type_log_odds=0.0, grad_route="dense", hmc_conditional=None):
         self.fields = list(fields)
+        # hmc_conditional: what location_loglik_grad and resample_hmc differentiate.  None: the reference's conditional, and under
+        # conditional="exact" both raise, as they always have (that default exists only because the suite pins those refusals).
+        # "exact" (needs conditional="exact"): the exact conditional's value and gradient -- the proposal's stamp mass on its own
+        # box and that mass's derivative at the fixed integer box (k_mass_grad.h, CEL_OPT_GRAD_CONDITIONAL around the calls), -inf
+        # where the box does not cover the source's photons -- so that resample_hmc and sweep(hmc=True) run under the exact sweep,
+        # on the device engine where _exact_on_device() holds and on the host engine otherwise: the same chains bit for bit.
+        if hmc_conditional not in (None, "exact"):
+            raise ValueError("hmc_conditional must be None or 'exact'")
+        if hmc_conditional == "exact" and conditional != "exact":
+            raise ValueError("hmc_conditional='exact' needs conditional='exact'")
+        self.hmc_conditional = hmc_conditional
         # grad_route: where the resident gradients of resample_hmc and location_loglik_grad are summed.  "dense": over the sample
         # patches (k_patch_grad.h).  "photons": at the split's photon lists (k_patch_grad_nz.h; CEL_OPT_PHOTON_LISTS + 4 around those
         # calls): the same terms in another order, so the values agree to rounding and the host and device engines, which take the
@@ -638,10 +649,13 @@ class ModelGibbs(object):
         """location_loglik with its analytic gradient in (ra, dec), per degree, summed over fields (the gradient form of
         cel_patch_loglik_multi against the resident patches) -> (ll[P], g[P, 2]); ll is location_loglik's value, bit for bit.
         shape_grad=True: the six coordinates (ra, dec, theta, sigma, phi, rho) -> (ll[P], g[P, 6]) (a star's last four: 0).
-        The exact conditional's mass term has no derivative here: conditional="exact" raises.
+        The exact conditional's mass term has no derivative here: conditional="exact" raises -- unless hmc_conditional="exact":
+        then ll is the exact location_loglik's value, bit for bit, and g the exact conditional's gradient at the proposals' fixed
+        integer boxes (ll = -inf and g = 0 where a proposal's box does not cover its source's photons).
         grad_route="photons": the gradients are summed at the split's photon lists (ll is unchanged)."""
         from . import field as _field
-        if self.conditional == "exact":
+        exact = self.hmc_conditional == "exact"
+        if self.conditional == "exact" and not exact:
             raise ValueError("location_loglik_grad: the exact conditional's stamp-mass term has no analytic derivative yet "
                              "(conditional='reference' only)")
         idx = np.asarray(idx, dtype=np.int64)
@@ -657,7 +671,7 @@ class ModelGibbs(object):
             pc = self.counts(f, idx=idx) if cts is None else cts[idx]
             f.prop.set(typ, U, pc, shape)
             with self._grad_route():
-                l, gr, _, gs = f.iset.patch_loglik_resident_grad(f.prop, owner)
+                l, gr, _, gs = f.iset.patch_loglik_resident_grad(f.prop, owner, conditional="exact" if exact else "reference")
             ll += l
             g += np.concatenate([gr, gs], axis=1) if shape_grad else gr
         return ll, g
@@ -979,6 +993,8 @@ class ModelGibbs(object):
         """the device runs the HMC step (cel_slice_sample, param 3) where it runs the type step under the reference's
         conditional: one field of unmasked frames"""
         ok = len(self.fields) == 1 and self.mask != "honour"
+        if self.hmc_conditional == "exact":             # (the exact step's cover test is not window-relative)
+            ok = ok and self._exact_on_device()
         if self.engine == "device" and not ok:
             raise ValueError("the device HMC step runs one field of whole, unmasked frames")
         return ok and self.engine != "host"
@@ -994,12 +1010,15 @@ class ModelGibbs(object):
         the normals of the streams of step_seed("hmc", 1) (refresh=0: a fresh momentum every call); a coordinate with
         imass = 0 is frozen and its momentum is 0.  imass: (6,) or (S, 6), default hmc_default_imass(); eps default 0.5, steps
         default 8.  hmc_preset("reference") holds the reference's numbers.  phi is wrapped afterwards, as resample_shapes wraps it.
-        The exact conditional's mass term has no derivative yet: conditional="exact" raises.
+        The exact conditional's mass term has no derivative yet: conditional="exact" raises -- unless hmc_conditional="exact":
+        then value and force are the exact conditional's; a trajectory that reaches a point whose box does not cover the source's
+        photons is dead, and a chain whose current row fails that test is left alone (it cannot after a full-box split).
         grad_route="photons": both engines take their gradients at the split's photon lists."""
         import time
         from .util.infer.slicesample import ChainStreams
         from .util.infer.hmc import hmc_lockstep
-        if self.conditional == "exact":
+        exact = self.hmc_conditional == "exact"
+        if self.conditional == "exact" and not exact:
             raise ValueError("resample_hmc: the exact conditional's stamp-mass term has no analytic derivative yet "
                              "(conditional='reference' only)")
         if not self._default_shape_prior:
@@ -1037,7 +1056,8 @@ class ModelGibbs(object):
             sset = self._sources(f)
             ids = np.where(runs, ids_all, -1).astype(np.int32)
             with self._grad_route():
-                q, pn, _, st = f.iset.hmc_step(sset, p, im, eps, steps, seed, phi_max=self.phi_period, chain_ids=ids)
+                q, pn, _, st = f.iset.hmc_step(sset, p, im, eps, steps, seed, phi_max=self.phi_period, chain_ids=ids,
+                                               conditional="exact" if exact else "reference")
             evals, accepted = st["evals"], st["accepted"]
         else:
             q, pn = q0.copy(), p.copy()
@@ -1059,7 +1079,9 @@ class ModelGibbs(object):
 
                 def grad_fn(i, Q):
                     idx = act[i]
-                    _, g = self.location_loglik_grad(idx, Q[:, :2], shape=Q[:, 2:], shape_grad=True)
+                    l, g = self.location_loglik_grad(idx, Q[:, :2], shape=Q[:, 2:], shape_grad=True)
+                    if exact:
+                        g[l == -np.inf] = np.nan            # an uncovered point: the trajectory is dead, as the device engine has it
                     gal = self.typ[idx] == 1
                     g[~gal, 2:] = 0.0
                     s = Q[gal, 3]
@@ -1073,8 +1095,10 @@ class ModelGibbs(object):
                     return ~gal | inside
 
                 st = {}
-                log_u = np.log(ChainStreams(seed, act).uniform(np.arange(act.size)))
                 try:
+                    if exact:                               # a chain whose current row fails the cover test does not run
+                        act = act[self.location_loglik(act, q0[act, :2], shape=q0[act, 2:]) > -np.inf]
+                    log_u = np.log(ChainStreams(seed, act).uniform(np.arange(act.size)))
                     qa, pa, _, _ = hmc_lockstep(q0[act], p[act], im[act], eps, steps, value_fn, grad_fn, log_u, support_fn, stats=st)
                 finally:
                     for f in self.fields:

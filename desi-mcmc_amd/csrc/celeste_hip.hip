@@ -102,6 +102,7 @@ static int fail(int code, const char *fmt, ...) {
 #include "k_grad.h"
 #include "k_patch_grad.h"
 #include "k_patch_grad_nz.h"
+#include "k_mass_grad.h"
 #include "k_split.h"
 #include "k_slice.h"
 
@@ -185,6 +186,7 @@ struct cel_ctx {
     int slice_fuse = SLICE_FUSE_DEFAULT;   // CEL_OPT_SLICE_FUSE
     int honour_mask = 0;        // CEL_OPT_HONOUR_MASK
     int slice_conditional = 0;  // CEL_OPT_SLICE_CONDITIONAL
+    int grad_conditional = 0;   // CEL_OPT_GRAD_CONDITIONAL
     int incremental = (getenv("CEL_INCREMENTAL") && atoi(getenv("CEL_INCREMENTAL")) == 0) ? 0 : 1;       // CEL_OPT_INCREMENTAL
     int tile_parts = (getenv("CEL_TILE_PARTS") && (atoi(getenv("CEL_TILE_PARTS")) == 1 || atoi(getenv("CEL_TILE_PARTS")) == 2 || atoi(getenv("CEL_TILE_PARTS")) == 4))
                          ? atoi(getenv("CEL_TILE_PARTS")) : 0;       // CEL_OPT_TILE_PARTS (the env var: the initial value, for A/B runs)
@@ -621,6 +623,11 @@ int cel_ctx_set_option(cel_ctx *c, int key, double v) {
         if (v != 0.0 && v != 1.0) return fail(CEL_ERR_INVALID, "CEL_OPT_SLICE_CONDITIONAL must be 0 (the reference's conditional) or 1 (the exact one)");
         c->slice_conditional = (int)v;
         return CEL_OK;
+    case CEL_OPT_GRAD_CONDITIONAL:
+        static_assert(CEL_OPT_GRAD_CONDITIONAL == 19, "the key is 19 in every binding");
+        if (v != 0.0 && v != 1.0) return fail(CEL_ERR_INVALID, "CEL_OPT_GRAD_CONDITIONAL must be 0 (the reference's conditional) or 1 (the exact one)");
+        c->grad_conditional = (int)v;
+        return CEL_OK;
     case CEL_OPT_TILE_PARTS:
         if (v != 0.0 && v != 1.0 && v != 2.0 && v != 4.0) return fail(CEL_ERR_INVALID, "CEL_OPT_TILE_PARTS must be 0 (by the frame's size), 1, 2 or 4");
         c->tile_parts = (int)v;
@@ -685,6 +692,7 @@ int cel_ctx_get_option(cel_ctx *c, int key, double *v) {
     case CEL_OPT_SLICE_FUSE: *v = c->slice_fuse; return CEL_OK;
     case CEL_OPT_HONOUR_MASK: *v = c->honour_mask; return CEL_OK;
     case CEL_OPT_SLICE_CONDITIONAL: *v = c->slice_conditional; return CEL_OK;
+    case CEL_OPT_GRAD_CONDITIONAL: *v = c->grad_conditional; return CEL_OK;
     case CEL_OPT_PROFILE: *v = (double)c->profile; return CEL_OK;
     case CEL_OPT_TILE_ORDER: *v = (double)c->tile_order; return CEL_OK;
     case CEL_OPT_TILE_ROWS: *v = c->tile_rows; return CEL_OK;
@@ -1660,6 +1668,10 @@ struct PllCall {
     double *d_data = nullptr, *d_out = nullptr;
     const int *i_data = nullptr;                    // the resident split's int32 photon counts (mode 0); everything else is double
     bool owned = true;                              // false: cel_patch_loglik's single source (its gradient keeps the dense kernel)
+    // CEL_OPT_GRAD_CONDITIONAL = 1 on the resident mode 8: the exact conditional's row (k_mass_grad.h).  d_owner is then a copy the
+    // cover test may retire slots in; pri holds -inf for those
+    bool exact = false;
+    double *d_pri = nullptr, *d_mass = nullptr, *d_exact = nullptr, *d_msums = nullptr, *d_mg = nullptr;
 };
 // step 1: the argument checks and the boxes.  k.P == 0 with CEL_OK: nothing to score.
 static int pll_check(cel_images *im, cel_sources *src, const int32_t *owner, int64_t NB, const int32_t *boxes,
@@ -1678,6 +1690,10 @@ static int pll_check(cel_images *im, cel_sources *src, const int32_t *owner, int
     if (!resident && (!boxes || !offsets)) return fail(CEL_ERR_INVALID, "cel_patch_loglik: null boxes / offsets");
     if (resident && mode > 1) return fail(CEL_ERR_INVALID, "the resident form scores mode 0 or 1");
     const int nplanes = (mode == 4) ? 2 : 1;               // mode 4: data plane, then background plane
+    // the exact conditional's gradient: the resident mode 8 of cel_patch_loglik_multi alone reads the key; it has the exact slice
+    // engine's preconditions (an unmasked set; the row window is the gradient form's refusal below; the split's just below)
+    k.exact = grad && mode == 0 && resident && k.owned && im->ctx->grad_conditional == 1;
+    if (k.exact) { int rm = refuse_masked(im, "cel_patch_loglik_multi (resident gradient under CEL_OPT_GRAD_CONDITIONAL = 1)"); if (rm) return rm; }
     // (a masked set is refused as such before the missing split is named: cel_images_set_nelec drops the split it masks)
     if (mode == 1) { int rm = refuse_masked(im, "cel_patch_loglik (isolated form)"); if (rm) return rm; }
     if (resident && !im->split.resident_of(NB))
@@ -1738,6 +1754,26 @@ static int pll_stage(cel_images *im, const int32_t *owner, const int64_t *offset
         return rc;
     carve(d_blk);
     if (owner) HIP_TRY(hipMemcpyAsync(k.d_owner, owner, sizeof(int) * P, hipMemcpyHostToDevice, c->stream));
+    if (k.exact) {                   // the exact row's extras, one block: cover flags, masses, terms, the mass gradient's sums and rows
+        int *d_own2 = nullptr;
+        auto carve2 = [&](char *base) {
+            Carver cv{base};
+            k.d_pri = cv.take<double>(P);
+            k.d_mass = cv.take<double>(P * B);
+            k.d_exact = cv.take<double>(P);
+            k.d_msums = cv.take<double>((size_t)GRAD_NS * PGRAD_PARTS * P * B);
+            k.d_mg = cv.take<double>(P * (7 + B));
+            d_own2 = cv.take<int>(P);
+            return cv.off;
+        };
+        char *d_ex = nullptr;
+        if ((rc = scratch_get(c, SCR_TMP_C, carve2(nullptr), (void **)&d_ex))) return rc;
+        carve2(d_ex);
+        if (k.d_owner) HIP_TRY(hipMemcpyAsync(d_own2, k.d_owner, sizeof(int) * P, hipMemcpyDeviceToDevice, c->stream));
+        else HIP_TRY(hipMemsetAsync(d_own2, 0, sizeof(int) * P, c->stream));
+        HIP_TRY(hipMemsetAsync(k.d_pri, 0, sizeof(double) * P, c->stream));
+        k.d_owner = d_own2;
+    }
     if (resident) {
         k.d_nz = im->d_snz; k.d_box = im->d_sbox; k.d_off = im->d_soff;
         if (k.mode == 0) k.i_data = im->d_samp;           // mode 0: the int32 patches; mode 1 reads nelec on the boxes
@@ -1835,12 +1871,33 @@ static int pll_gradient(cel_images *im, cel_sources *src, const PllCall &k, cons
     hipLaunchKernelGGL(k_patch_grad_chain, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, c->stream, im->d_bands, B, P, im->d_recs,
                        (const int *)k.d_owner, (const int4 *)k.d_box, (const int *)src->d_type, (const double *)src->d_shape,
                        (const double *)src->d_counts, (const double *)d_sums, mode, d_grad);
+    std::vector<double> hpe((size_t)(k.exact ? 2 * P : 0));           // the cover flags (pri), then the exact terms
+    if (k.exact) {
+        // the exact conditional (k_mass_grad.h): the masses and the term per proposal as the exact slice engine forms them, the
+        // mass gradient's sums, the same chain rule on them (mode 2: nothing but the sums), and the exact rows from the two
+        launch_stamp_mass(c, im, P, k.d_owner, k.d_mass, P * B);
+        hipLaunchKernelGGL(k_sg_exact_terms, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, c->stream, P, B, (const int *)k.d_owner,
+                           (const BandDev *)im->d_bands, (const double *)src->d_counts, (const double *)k.d_mass,
+                           (const int64_t *)im->d_soff, k.d_exact);
+        hipLaunchKernelGGL(k_mass_grad, grid, dim3(64), 0, c->stream, im->d_bands, B, P, im->d_recs, (const int *)k.d_owner, k.d_msums);
+        hipLaunchKernelGGL(k_patch_grad_chain, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, c->stream, im->d_bands, B, P, im->d_recs,
+                           (const int *)k.d_owner, (const int4 *)k.d_box, (const int *)src->d_type, (const double *)src->d_shape,
+                           (const double *)src->d_counts, (const double *)k.d_msums, 2, k.d_mg);
+        hipLaunchKernelGGL(k_mass_grad_apply, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, c->stream, P, B, (const int *)k.d_owner,
+                           (const BandDev *)im->d_bands, (const int64_t *)im->d_soff, (const double *)k.d_mass, (const double *)k.d_mg, d_grad);
+        HIP_TRY(hipMemcpyAsync(hpe.data(), k.d_pri, sizeof(double) * P, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(hpe.data() + P, k.d_exact, sizeof(double) * P, hipMemcpyDeviceToHost, c->stream));
+    }
     prof_end(c, pi);
     HIP_TRY(hipGetLastError());
     std::vector<double> hg(ng);
     HIP_TRY(hipMemcpyAsync(hg.data(), d_grad, sizeof(double) * ng, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int64_t p = 0; p < P; p++) hg[(size_t)p * (7 + B)] = val[(size_t)p];
+    for (int64_t p = 0; p < P; p++) {
+        double v = val[(size_t)p];
+        if (k.exact) v = (hpe[(size_t)p] > -INFINITY) ? v + hpe[(size_t)(P + p)] : -INFINITY;     // ll = patch sum; ll += e (uncovered: -inf)
+        hg[(size_t)p * (7 + B)] = v;
+    }
     memcpy(ll_out, hg.data(), sizeof(double) * ng);
     return CEL_OK;
 }
@@ -1853,6 +1910,9 @@ static int pll_run(cel_images *im, cel_sources *src, const int32_t *owner, int64
     if (rc || k.P == 0) return rc;
     if ((rc = run_prep(im, src)) || (rc = pll_stage(im, owner, offsets, data, mem, k))) return rc;
     cel_ctx *c = im->ctx;
+    if (k.exact)                     // the cover test first: an uncovered proposal's slot retires (its jobs return at their first instructions)
+        hipLaunchKernelGGL(k_sg_cover, dim3((unsigned)((k.P + 255) / 256)), dim3(256), 0, c->stream, k.P, im->B, k.d_owner, k.d_pri,
+                           (const int4 *)im->d_boxes, (const int *)im->d_status, (const int4 *)im->d_snz);
     const int pi = prof_begin(c, CEL_K_PATCH_LL);
     pll_launch_values(im, k);
     prof_end(c, pi);
@@ -2484,9 +2544,11 @@ static int slice_hmc(cel_images *im, cel_sources *src, const int32_t *chain_ids,
     if (!dirs || numdir != 2 * HMC_D)
         return fail(CEL_ERR_INVALID, "cel_slice_sample: the HMC step (param 3) needs dirs = S rows of (momentum[6], inverse mass[6]) and numdir = 12");
     cel_ctx *c = im->ctx;
-    if (c->slice_conditional == 1)
+    // CEL_OPT_GRAD_CONDITIONAL = 1: v and g are the exact conditional's (k_mass_grad.h); CEL_OPT_SLICE_CONDITIONAL is not read then
+    const bool exact = c->grad_conditional == 1;
+    if (!exact && c->slice_conditional == 1)
         return fail(CEL_ERR_INVALID, "cel_slice_sample: the HMC step (param 3): the exact conditional's stamp-mass term has no analytic derivative yet "
-                                     "(CEL_OPT_SLICE_CONDITIONAL = 0 only)");
+                                     "(CEL_OPT_SLICE_CONDITIONAL = 0 only); the exact HMC step is CEL_OPT_GRAD_CONDITIONAL = 1");
     if (im->win_y0 != 0 || im->full_H != im->H)
         return fail(CEL_ERR_INVALID, "cel_slice_sample: the HMC step (param 3) is not supported on an image set with a row window "
                                      "(cel_images_set_window): the gradient form refuses it");
@@ -2514,7 +2576,7 @@ static int slice_hmc(cel_images *im, cel_sources *src, const int32_t *chain_ids,
     const bool lists = c->variant != 0;
     // one allocation, carved (Carver: once for the size, once for the pointers)
     Hmc hm;
-    double *d_dirs, *d_ll, *d_sums, *d_grad, *d_out;
+    double *d_dirs, *d_ll, *d_sums, *d_grad, *d_out, *d_mass = nullptr, *d_exact = nullptr, *d_msums = nullptr, *d_mg = nullptr, *d_cpri = nullptr;
     int *d_owner, *d_owner2, *d_ids, *d_list, *d_list_nz, *d_flags, *d_flag;
     auto carve = [&](char *base) {
         Carver k{base};
@@ -2541,6 +2603,13 @@ static int slice_hmc(cel_images *im, cel_sources *src, const int32_t *chain_ids,
         d_list = k.take<int>(lists ? 2 * n * B * PLL_PARTS : 0);
         d_list_nz = k.take<int>(lists ? 2 * n * B * PLL_PARTS : 0);
         d_flags = k.take<int>(8, 16);                         // [1] error bits, [4] / [5] dense / photon-list blocks
+        if (exact) {
+            d_mass = k.take<double>(2 * n * B);               // the slots' stamp masses, per (slot, band)
+            d_exact = k.take<double>(2 * n);                  // the exact conditional's term per scored slot (k_sg_exact_terms)
+            d_msums = k.take<double>((size_t)GRAD_NS * PGRAD_PARTS * n * B);     // k_mass_grad's sums per (chain, band, part)
+            d_mg = k.take<double>(n * (7 + B));               // the chain rule on them
+            d_cpri = k.take<double>(n);                       // k_sg_cover's flag per gradient evaluation (owner carries the verdict)
+        }
         return k.off;
     };
     const size_t need = carve(nullptr);
@@ -2558,6 +2627,7 @@ static int slice_hmc(cel_images *im, cel_sources *src, const int32_t *chain_ids,
     if (chain_ids) HIP_TRY(hipMemcpyAsync(d_ids, chain_ids, sizeof(int) * S, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));                        // pageable sources must stay valid
     HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(int) * 8, st));
+    if (exact) HIP_TRY(hipMemsetAsync(d_exact, 0, sizeof(double) * 2 * S, st));      // (a slot that is not scored gets no term)
     const unsigned g256 = (unsigned)((S + 255) / 256), j256 = (unsigned)((S * B + 255) / 256);
     hipLaunchKernelGGL(k_hmc_fill, dim3(g256), dim3(256), 0, st, hm, S, B, phi_max, (const int *)src->d_type, (const double *)src->d_radec,
                        (const double *)src->d_counts, (const double *)src->d_shape, (const double *)d_dirs,
@@ -2586,7 +2656,14 @@ static int slice_hmc(cel_images *im, cel_sources *src, const int32_t *chain_ids,
     for (int l = 0; l <= L; l++) {
         prop->S = S;
         prop->all_rows_changed(true);
-        if ((rc = run_prep(im, prop, d_owner, 1))) return rc; // the patch limits are fixed: no boxes
+        // the patch limits are fixed: no boxes -- but the exact conditional needs the proposals' own (cover test, mass)
+        if ((rc = run_prep(im, prop, d_owner, exact ? 0 : 1))) return rc;
+        if (exact) {
+            hipLaunchKernelGGL(k_sg_cover, dim3(g256), dim3(256), 0, st, S, B, d_owner, d_cpri, (const int4 *)im->d_boxes,
+                               (const int *)im->d_status, (const int4 *)im->d_snz);
+            hipLaunchKernelGGL(k_hmc_cover, dim3(g256), dim3(256), 0, st, hm, S, (const int *)d_owner, l == 0 ? 1 : 0);
+            launches += 2;
+        }
         const int pi = prof_begin(c, CEL_K_PATCH_LL);
         if (grad_nz)
             hipLaunchKernelGGL(pgrad_nz_sums, dim3((unsigned)(S * B * PGRAD_PARTS)), dim3(64), 0, st, im->d_bands, B, S, im->d_recs,
@@ -2599,6 +2676,17 @@ static int slice_hmc(cel_images *im, cel_sources *src, const int32_t *chain_ids,
         hipLaunchKernelGGL(k_patch_grad_chain, dim3(g256), dim3(256), 0, st, im->d_bands, B, S, im->d_recs, (const int *)d_owner,
                            (const int4 *)im->d_sbox, (const int *)prop->d_type, (const double *)prop->d_shape,
                            (const double *)prop->d_counts, (const double *)d_sums, 0, d_grad);
+        if (exact) {                 // the mass, its gradient's sums, the chain rule on them, the exact rows
+            launch_stamp_mass(c, im, S, d_owner, d_mass, S * B);
+            hipLaunchKernelGGL(k_mass_grad, dim3((unsigned)(S * B * PGRAD_PARTS)), dim3(64), 0, st, im->d_bands, B, S, im->d_recs,
+                               (const int *)d_owner, d_msums);
+            hipLaunchKernelGGL(k_patch_grad_chain, dim3(g256), dim3(256), 0, st, im->d_bands, B, S, im->d_recs, (const int *)d_owner,
+                               (const int4 *)im->d_sbox, (const int *)prop->d_type, (const double *)prop->d_shape,
+                               (const double *)prop->d_counts, (const double *)d_msums, 2, d_mg);
+            hipLaunchKernelGGL(k_mass_grad_apply, dim3(g256), dim3(256), 0, st, S, B, (const int *)d_owner, (const BandDev *)im->d_bands,
+                               (const int64_t *)im->d_soff, (const double *)d_mass, (const double *)d_mg, d_grad);
+            launches += 4;
+        }
         prof_end(c, pi);
         launches += 3;
         if (l < L) {
@@ -2612,9 +2700,18 @@ static int slice_hmc(cel_images *im, cel_sources *src, const int32_t *chain_ids,
                        prop->d_counts, prop->d_shape, d_owner2);
     prop->S = P;
     prop->all_rows_changed(true);
-    if ((rc = run_prep(im, prop, d_owner2, 1))) return rc;
+    if ((rc = run_prep(im, prop, d_owner2, exact ? 0 : 1))) return rc;
+    if (exact) {                     // the two scored slots get their cover test ...
+        hipLaunchKernelGGL(k_sg_cover, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, P, B, d_owner2, hm.pri, (const int4 *)im->d_boxes,
+                           (const int *)im->d_status, (const int4 *)im->d_snz);
+        launches++;
+    }
     launches += 2 + launch_resident_ll(c, im, P, d_owner2, d_ll, use_nz, {n_dense, d_list, nullptr}, {n_nz, d_list_nz, nullptr}, nullptr);
-    hipLaunchKernelGGL(k_hmc_decide, dim3(g256), dim3(256), 0, st, hm, S, B, ostr, (const double *)d_ll, (const int *)src->d_type,
+    if (exact) {                     // ... and their e
+        launch_exact_terms(c, im, prop, P, d_owner2, P * B, nullptr, d_mass, d_exact);
+        launches += 2;
+    }
+    hipLaunchKernelGGL(k_hmc_decide, dim3(g256), dim3(256), 0, st, hm, S, B, ostr, (const double *)d_ll, (const double *)d_exact, (const int *)src->d_type,
                        (double *)src->d_radec, (double *)src->d_shape, d_out, d_flag, d_flags + 1);
     launches++;
     HIP_TRY(hipGetLastError());

@@ -194,7 +194,9 @@ k_hmc_slots(Hmc hm, int64_t S, int B, double eps, double phi_max, const int *__r
 // caller's momentum), then log alpha per chain (NaN for a chain left alone, -inf for a dead trajectory); flag: -1 left alone,
 // 0 rejected, 1 accepted.  err |= 1: a running chain whose current state scores -inf (or NaN): it stays where it is.
 __global__ void __launch_bounds__(256)
-k_hmc_decide(Hmc hm, int64_t S, int B, int nparts, const double *__restrict__ ll_pb, const int *__restrict__ type,
+k_hmc_decide(Hmc hm, int64_t S, int B, int nparts, const double *__restrict__ ll_pb,
+             const double *__restrict__ exact /* 2S: the exact conditional's term per slot (k_sg_exact_terms), or nullptr */,
+             const int *__restrict__ type,
              double *__restrict__ radec, double *__restrict__ shape, double *__restrict__ out /* [S][12], then [S] */,
              int *__restrict__ flag /* S */, int *__restrict__ err) {
 #pragma clang fp contract(off)
@@ -218,6 +220,7 @@ k_hmc_decide(Hmc hm, int64_t S, int B, int nparts, const double *__restrict__ ll
                     for (int j = 1; j < nparts; j++) y += x[j];
                     acc += y;
                 }
+                if (exact) acc += exact[2 * s + k];         // ll = patch sum; ll += e; v = ll + prior
                 v[k] = acc + hm.pri[2 * s + k];
             }
             if (!(v[0] > -INFINITY)) {
@@ -239,4 +242,24 @@ k_hmc_decide(Hmc hm, int64_t S, int B, int nparts, const double *__restrict__ ll
     for (int i = 0; i < HMC_D; i++) o[HMC_D + i] = (f == 1) ? p[i] : (f == 0 ? -p0[i] : p0[i]);
     out[2 * HMC_D * S + s] = la;
     flag[s] = f;
+}
+
+// ---- the exact conditional (CEL_OPT_GRAD_CONDITIONAL = 1) -------------------------------------------------------------------
+// v and g are the exact conditional's: per gradient evaluation the proposals' records are written WITH their boxes, k_sg_cover
+// retires the slot of a proposal whose box does not cover its source's photons, and this kernel, one thread per chain, tells
+// the state machine: at the first evaluation (the catalogue's own row) the chain does not run at all -- it is reported as a
+// chain left alone; later the trajectory is dead, exactly like one that left the support (the evaluation is counted: k_hmc_step
+// counted it when it named the point).  The force is a function of q alone, piecewise smooth with jumps where the integer box
+// changes: the leapfrog stays reversible and volume-preserving, and the Metropolis test on the exact v keeps the update exact.
+__global__ void __launch_bounds__(256)
+k_hmc_cover(Hmc hm, int64_t S, const int *__restrict__ owner /* S, after k_sg_cover */, int first) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    if (!hm.run[s] || hm.dead[s] || owner[s] >= 0) return;
+    if (first) {
+        hm.run[s] = 0;
+        hm.nev[s] = 0;
+    } else {
+        hm.dead[s] = 1;
+    }
 }

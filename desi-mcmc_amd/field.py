@@ -489,12 +489,32 @@ class ImageSet(object):
         return (x[:, 0].astype(np.int32), np.ascontiguousarray(x[:, 1:]), la,
                 dict(evals=int(stats[1]), accepted=int(stats[2]), launches=int(stats[3])))
 
-    def hmc_step(self, sources, p0, imass, eps, steps, seed, phi_max=180., chain_ids=None):
+    def _grad_conditional(self, conditional):
+        """CEL_OPT_GRAD_CONDITIONAL set around a resident gradient call or an HMC step and the caller's value restored behind it,
+        also when the call fails -- as slice_sample(conditional=) does it for CEL_OPT_SLICE_CONDITIONAL"""
+        import contextlib
+        if conditional not in ("reference", "exact"):
+            raise ValueError("conditional must be 'reference' or 'exact'")
+
+        @contextlib.contextmanager
+        def cm():
+            was = self.ctx.get_option(L.CEL_OPT_GRAD_CONDITIONAL)
+            try:
+                self.ctx.set_option(L.CEL_OPT_GRAD_CONDITIONAL, 1 if conditional == "exact" else 0)
+                yield
+            finally:
+                self.ctx.set_option(L.CEL_OPT_GRAD_CONDITIONAL, was)
+        return cm()
+
+    def hmc_step(self, sources, p0, imass, eps, steps, seed, phi_max=180., chain_ids=None, conditional="reference"):
         """One HMC update of every source's location and shape at once, on the device (cel_slice_sample, param 3):
         q = (ra, dec, theta, sigma, phi, rho), a star in (ra, dec) only, counts fixed, `steps` leapfrog steps of size eps against
         the resident split under the reference's conditional.  p0 (S, 6): the momentum, refreshed by the caller; imass (S, 6):
         the inverse mass (0 freezes a coordinate).  phi_max > 0: the built-in shape prior and its bound on phi.  Accepted rows
         replace the sources' location and shape on the device.
+        conditional="exact": value and force are the exact conditional's (CEL_OPT_GRAD_CONDITIONAL, set around the call): the
+        proposal's stamp mass on its own box and that mass's derivative at the fixed integer box; a trajectory that reaches a point
+        whose box does not cover the source's photons is dead, a chain whose current row fails that test is left alone.
         -> (q[S,6], p[S,6], log_alpha[S], dict(steps, evals, accepted, launches)): p is the momentum to carry on with (the
         trajectory's on accept, -p0 on reject); log_alpha is NaN for a chain left alone"""
         S = sources.S
@@ -511,10 +531,12 @@ class ImageSet(object):
                 raise ValueError("chain_ids must have one entry per source")
         x, la = np.zeros((S, 12)), np.zeros(S)
         stats = np.zeros(4, dtype=np.int64)
-        # (CEL_OPT_SLICE_CONDITIONAL is left as the context has it: under the exact conditional the library refuses the step)
-        L.check(L.lib().cel_slice_sample(self._h, sources._h, 3, None if ids is None else ids.ctypes.data_as(L.c_int32_p),
-                                         L.dptr(dirs), 12, 0, 0, float(eps), float(phi_max), C.c_uint64(int(seed) & (2 ** 64 - 1)),
-                                         int(steps), L.dptr(x), L.dptr(la), stats.ctypes.data_as(L.c_int64_p)))
+        # (CEL_OPT_SLICE_CONDITIONAL is left as the context has it: under the exact conditional the library refuses the step unless
+        # CEL_OPT_GRAD_CONDITIONAL asks for the exact one)
+        with self._grad_conditional(conditional):
+            L.check(L.lib().cel_slice_sample(self._h, sources._h, 3, None if ids is None else ids.ctypes.data_as(L.c_int32_p),
+                                             L.dptr(dirs), 12, 0, 0, float(eps), float(phi_max), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                             int(steps), L.dptr(x), L.dptr(la), stats.ctypes.data_as(L.c_int64_p)))
         return (np.ascontiguousarray(x[:, :6]), np.ascontiguousarray(x[:, 6:]), la,
                 dict(steps=int(stats[0]), evals=int(stats[1]), accepted=int(stats[2]), launches=int(stats[3])))
 
@@ -738,11 +760,15 @@ class ImageSet(object):
         boxes = np.ascontiguousarray(boxes, dtype=np.int32).reshape(1, self.B, 4)
         return self.patch_loglik_multi_grad(sources, np.zeros(sources.S, dtype=np.int32), boxes, [patches], mode=mode)
 
-    def patch_loglik_resident_grad(self, proposals, owner, isolated=False):
+    def patch_loglik_resident_grad(self, proposals, owner, isolated=False, conditional="reference"):
         """patch_loglik_resident and its analytic gradient: against the resident sample patches (isolated=True: against the
         observed image on the same boxes).  -> (ll[P], g_radec[P,2], g_counts[P,B], g_shape[P,4])
         Where the gradient is summed is the context's choice, not an argument: under CEL_OPT_PHOTON_LISTS = 4 or 5 (and not
-        isolated) at the split's photon lists, otherwise over the patches; the two agree to rounding and ll is the same bits."""
+        isolated) at the split's photon lists, otherwise over the patches; the two agree to rounding and ll is the same bits.
+        conditional="exact" (not isolated): the exact conditional's value and gradient (CEL_OPT_GRAD_CONDITIONAL, set around the
+        call): ll is -inf and the gradient 0 for a proposal whose box does not cover its source's photons."""
+        if conditional == "exact" and isolated:
+            raise ValueError("conditional='exact' is the conditional form's (isolated=False)")
         if isolated:
             self._refuse_masked("patch_loglik_resident(isolated=True)")
         owner = np.ascontiguousarray(owner, dtype=np.int32)
@@ -751,8 +777,9 @@ class ImageSet(object):
         S, tot = C.c_int64(0), C.c_int64(0)
         L.check(L.lib().cel_samples_info(self._h, C.byref(S), C.byref(tot)))
         out = np.zeros(proposals.S * (7 + self.B))
-        L.check(L.lib().cel_patch_loglik_multi(self._h, proposals._h, owner.ctypes.data_as(L.c_int32_p), S.value, None, None, None,
-                                               L.CEL_DEVICE, L.CEL_PLL_GRAD + (1 if isolated else 0), L.dptr(out)))
+        with self._grad_conditional(conditional):
+            L.check(L.lib().cel_patch_loglik_multi(self._h, proposals._h, owner.ctypes.data_as(L.c_int32_p), S.value, None, None, None,
+                                                   L.CEL_DEVICE, L.CEL_PLL_GRAD + (1 if isolated else 0), L.dptr(out)))
         return self._split_grad(out, proposals.S)
 
     def stamp_boxes(self, sources, band):

@@ -119,6 +119,29 @@ enum {
                                  the exact conditional is cel_slice_sample(param 0, dirs = NULL, step_out = 0).  Under 1 a masked set is
                                  refused as under 0, and so is an image set with a row window (cel_images_set_window: the cover test
                                  is not window-relative).  Any other value: CEL_ERR_INVALID */
+    /* exact gradient: */ CEL_OPT_GRAD_CONDITIONAL = 19, /* which conditional the RESIDENT GRADIENT differentiates.  0 (default): the reference's, as
+                                 before: the same kernels, launches and bits, and every refusal of the exact conditional stands.  1: the
+                                 EXACT conditional of ModelGibbs(conditional="exact") (the option above describes it), value and gradient.
+                                 Exactly two calls read it.
+                                 (a) cel_patch_loglik_multi's RESIDENT mode 8 (boxes = offsets = data = NULL, mode = 8).  The row of
+                                 proposal p with owner s, v_ref / g_ref being the row under 0:
+                                   slot 0      v_ref + e,  e = -sum_b (counts[p][b] * (mass_b - wsum_b)) * has_patch(s, b), added in band order
+                                               from 0.0 without FMA contraction (k_sg_exact_terms), mass_b the mass kernel's value on the
+                                               proposal's own box
+                                   slots 1-6   g_ref[i] + ge[i],  ge[i] = -sum_b (counts[p][b] * d mass_b / d q_i) * has_patch(s, b), same order;
+                                               the derivative is taken at the proposal's FIXED integer box (the box moves in jumps: between
+                                               two jumps the sum's limits are constants), in cel_loglik_grad's units and conventions
+                                   slot 7 + b  the reference's entry + -(mass_b - wsum_b) * has_patch(s, b)
+                                 A proposal that fails the cover test (k_sg_cover's rule, see the option above) has slot 0 = -inf and
+                                 slots 1 .. = 0; its jobs retire at their first instructions.  d mass_b / d q comes from k_mass_grad.h: the
+                                 plain form -- every component at every pixel of the box, nothing dropped, neither CEL_OPT_TAIL_LOG_SOURCE
+                                 nor CEL_OPT_KERNEL read, the same bits on every call -- followed by the gradient form's chain rule.
+                                 The call then has the exact slice engine's preconditions: a masked set, a row window and a missing
+                                 resident split are refused before any launch, ll_out untouched.  Mode 9, mode 10, explicit patches
+                                 and cel_patch_loglik do not read the key.
+                                 (b) cel_slice_sample(param = 3): the HMC step's v and g are the exact ones above (see there);
+                                 CEL_OPT_SLICE_CONDITIONAL is not read by param 3 then.
+                                 Any other value: CEL_ERR_INVALID, the stored value unchanged */
     CEL_OPT_TILE_PARTS = 13, /* how many one-wave blocks share a render tile of the general 32 x 64 kernel.  0 (default) = by
                                the frame's size: 4 for at most 512 tiles, 2 for at most 3 072, else 1 -- a frame of few tiles
                                (one rank's row strip of a field cut 8 ways, a 51 x 51 real field) finishes when its heaviest
@@ -581,7 +604,21 @@ int cel_slice_locations(cel_images *img, cel_sources *src, const int32_t *chain_
  * moves.  Refused before any launch, the outputs untouched: what params 0-2 refuse; an image set with a row window (the gradient
  * form refuses it); CEL_OPT_SLICE_CONDITIONAL = 1 (the exact conditional's stamp-mass term has no analytic derivative yet).
  * Under CEL_OPT_PHOTON_LISTS = 4 or 5 the L + 1 gradients are taken at the split's photon lists, as the resident mode 8 takes them
- * then: g(q) is still that call's row bit for bit, and the launch count does not change. */
+ * then: g(q) is still that call's row bit for bit, and the launch count does not change.
+ * CEL_OPT_GRAD_CONDITIONAL = 1: v and g are the EXACT conditional's -- v = prior + (the mode-0 values + e), g = slots 1-6 of the
+ * resident mode-8 row under that option, bit for bit.  Each of the L + 1 gradient evaluations writes the proposals' records WITH
+ * their boxes, then runs the cover test (k_sg_cover + k_hmc_cover), the likelihood gradient by whichever route
+ * CEL_OPT_PHOTON_LISTS selects, the mass kernel, k_mass_grad, the chain rule on its sums and k_mass_grad_apply.  A trajectory that
+ * reaches a point whose box does not cover the source's photons is dead (owner = -1, log alpha = -inf), exactly like one that
+ * leaves the support; the evaluation that found it is counted.  The two slots scored at the end get their cover test and their e.
+ * A chain whose CURRENT row already fails the cover test does not run: it is reported as a chain left alone (its row, its p0,
+ * log alpha NaN, no evaluation).  The force is a function of q alone, so the leapfrog with this piecewise force is still a
+ * reversible, volume-preserving map and the Metropolis test keeps the update exact across the jumps of v at a change of the
+ * integer box.  No further host synchronisation.  Launches (stats[3]), with J = 1 under CEL_OPT_KERNEL = 1 (the job lists) else 0
+ * and V = the value launches of the two scored slots (1 or 2):
+ *     reference's conditional:  1 + J + 3 (L + 1) + L + 2 + V + 1
+ *     exact conditional:        1 + J + 9 (L + 1) + L + 3 + V + 2 + 1
+ * Refused as under 0, and a masked set, a row window and a missing split as params 0-2 refuse them. */
 int cel_slice_sample(cel_images *img, cel_sources *src, int param, const int32_t *chain_ids, const double *dirs, int numdir,
                      int step_out, int max_steps_out, double sigma, double phi_max, uint64_t seed, int max_rounds,
                      double *x_out, double *llh_out, int64_t *stats);

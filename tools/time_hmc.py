@@ -7,6 +7,11 @@ rates of the two presets on this field.  Diagnostic; not part of bench.py's cont
 
 --route dense | photons | both: where the step's gradients are summed (ModelGibbs(grad_route=)); both: the two routes in one
 process, interleaved call by call.
+--conditional reference | exact: exact = the step under the exact conditional (ModelGibbs(conditional="exact", hmc_conditional=
+"exact"): CEL_OPT_GRAD_CONDITIONAL, k_mass_grad.h) BESIDE the reference's, in one process, the conditionals (and routes) taking
+turns call by call:
+
+    python tools/time_hmc.py --conditional exact --route both > profiles/hmc_exact_time.txt
 
 Every time is the median of REPS calls after WARM warm-up calls (min and max beside it), wall-clock around the blocking call.
 The catalogue is put back before every call, so that each call starts from the same state.
@@ -27,9 +32,17 @@ WARM, REPS = 3, 15
 ap = argparse.ArgumentParser()
 ap.add_argument("config", nargs="?", default="mixed10k_2048")
 ap.add_argument("--route", choices=("dense", "photons", "both"), default="dense")
+ap.add_argument("--conditional", choices=("reference", "exact"), default="reference")
 ap.add_argument("--no-host", action="store_true", help="leave out the host loop (one mode-8 call per step)")
 args = ap.parse_args()
 ROUTES = ("dense", "photons") if args.route == "both" else (args.route,)
+CONDS = ("reference", "exact") if args.conditional == "exact" else ("reference",)
+# a variant: (conditional, route); its label names the conditional only where there are two
+ROUTES = tuple((c, r) for r in ROUTES for c in CONDS)
+
+
+def vname(v):
+    return v[1] if len(CONDS) == 1 else "%s conditional, %s" % v
 ctx = cel.Context(0)
 name = args.config
 if name == "test12":         # the two-band 96 x 112 scene of tests/test_hmc.py's engine test
@@ -52,11 +65,13 @@ def timed(label, fn, before=None, reps=REPS, warm=WARM):
     return out
 
 
-def model(engine, route):
+def model(engine, variant):
+    cond, route = variant
+    kw = dict(conditional="exact", hmc_conditional="exact") if cond == "exact" else {}
     imgs = cel.ImageSet(ctx, f.bands, f.H, f.W)
     imgs.set_nelec(f.nelec)
     gf = celeste_mcmc.GibbsField(imgs, list(range(f.B)), f.bands[:, 2], f.bands[:, 1], f.H * f.W)
-    g = celeste_mcmc.ModelGibbs([gf], f.src["type"], f.src["radec"], f.flux5(), f.src["shape"], seed=5, engine=engine, grad_route=route)
+    g = celeste_mcmc.ModelGibbs([gf], f.src["type"], f.src["radec"], f.flux5(), f.src["shape"], seed=5, engine=engine, grad_route=route, **kw)
     g.resample_photons()
     return g
 
@@ -91,7 +106,7 @@ for label, kw in (("library default (eps 0.5, 8 steps, scale-free mass)", {}), (
     n = WARM + REPS
     run = int(np.sum(g0.active & (g0.typ < 2)))
     for r in ROUTES:
-        print("%-66s %9.3f ms  (%.3f .. %.3f)" % ("device engine, %s route, %s" % (r, label), np.median(ts[r]), min(ts[r]), max(ts[r])))
+        print("%-66s %9.3f ms  (%.3f .. %.3f)" % ("device engine, %s route, %s" % (vname(r), label), np.median(ts[r]), min(ts[r]), max(ts[r])))
         acc, ev = g[r].timing["hmc_accepted"] - a0[r][0], g[r].timing["hmc_evals"] - a0[r][1]
         print("    acceptance %.3f (%d of %d updates), %d gradient evaluations per call" % (acc / float(n * run), acc, n * run, ev // n))
     k1 = dict(kw)
@@ -99,10 +114,10 @@ for label, kw in (("library default (eps 0.5, 8 steps, scale-free mass)", {}), (
     t1 = interleaved(k1)
     for r in ROUTES:
         print("    %s route, per leapfrog step (median at %d steps - median at 1 step) / %d: %.3f ms"
-              % (r, steps, steps - 1, (np.median(ts[r]) - np.median(t1[r])) / (steps - 1)))
+              % (vname(r), steps, steps - 1, (np.median(ts[r]) - np.median(t1[r])) / (steps - 1)))
 
 if not args.no_host:
     for r in ROUTES:
         h = model("host", r)
-        timed("host loop (one mode-8 call per step), %s route, library default, 8 steps" % r, lambda: h.resample_hmc(), before=lambda: back(h), reps=5, warm=1)
-        timed("host loop, %s route, 1 step" % r, lambda: h.resample_hmc(steps=1), before=lambda: back(h), reps=5, warm=1)
+        timed("host loop (one mode-8 call per step), %s route, library default, 8 steps" % vname(r), lambda: h.resample_hmc(), before=lambda: back(h), reps=5, warm=1)
+        timed("host loop, %s route, 1 step" % vname(r), lambda: h.resample_hmc(steps=1), before=lambda: back(h), reps=5, warm=1)
