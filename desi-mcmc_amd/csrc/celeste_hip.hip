@@ -1360,10 +1360,15 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
     // with that table ON THE DEVICE, on every call, and the binning kernels return at once unless it found a difference.
     // CEL_OPT_INCREMENTAL = 0: no comparison, the binning runs in full.
     bool bins_stand = c->incremental && im->lists.binning_of(S);
+    // No source preparation when the records stand as well.  The records are a function of the catalogue's rows, the bands' WCS
+    // and PSF tables, the window and the source count; when the tables hold those of exactly this generation and the last
+    // render binned its lists from them (prep_stands, asked BEFORE render_begins drops lists_gen), k_prep would store what
+    // stands there and find nothing to change: it is not launched, and the binning launch leaves every word as it is
+    // (BIN_LEAVE).  A new sky level, new pixels, a log-likelihood after a plain render, a call that read the boxes in between:
+    // all render from the records in place.  Every tile is rendered all the same.
+    bool recs_stand = im->prep_stands(*src, S, c->incremental != 0);
     im->render_begins((flags & CEL_RENDER_LOGLIK) != 0, !lambda_out && !(flags & CEL_RENDER_NO_STORE));
-    rc = run_prep(im, src, nullptr, 0, bins_stand ? ++im->bin_step : 0ull);
-    if (rc) return rc;
-    if (incr) mark_dirty();     // ... and the tiles their new boxes touch
+    // (the list buffers first: one that had to be re-allocated holds no lists, whatever the stamps said)
     const int64_t lists_cap0 = im->d_lists.cap, clist_cap0 = im->d_clist.cap;
     if (im->d_lists.cap == 0) {
         // first guess: every (band, source) touches ~6 tiles; grown on overflow below
@@ -1379,12 +1384,18 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
     const int tile_order = plan.tile_order, parts = plan.parts;
     const bool bin_direct = plan.bin_direct, diag = plan.diag;
     if (bin_direct) HIP_TRY(im->d_lists.grow((int64_t)T * S, (int64_t)T * S, st));
-    if (im->d_lists.cap != lists_cap0 || im->d_clist.cap != clist_cap0) { im->lists_regrown(); bins_stand = false; }
+    if (im->d_lists.cap != lists_cap0 || im->d_clist.cap != clist_cap0) { im->lists_regrown(); bins_stand = recs_stand = false; }
+    if (!recs_stand) {
+        rc = run_prep(im, src, nullptr, 0, bins_stand ? ++im->bin_step : 0ull);
+        if (rc) return rc;
+    }
+    if (incr) mark_dirty();     // ... and the tiles their new boxes touch
     for (int attempt = 0; attempt < 8; attempt++) {
         // (a retry bins: its cursor words were zeroed by hand, the attempt before it left half-built lists)
-        const BinStep bs = {im->d_cursor, im->bin_step, (bins_stand && attempt == 0) ? 0 : 1};
+        const BinStep bs = {im->d_cursor, im->bin_step, attempt > 0 ? BIN_ALWAYS : (recs_stand ? BIN_LEAVE : (bins_stand ? BIN_IF_CHANGED : BIN_ALWAYS))};
         // d_cursor: [0] fine cursor, [1] fine overflow, [2] coarse cursor, [3] coarse overflow;
-        // zeroed by k_prep (no memset in the queue), by hand only when that did not run or on a retry
+        // zeroed by k_prep (no memset in the queue), by hand only for an empty catalogue or on a retry; a render that launched
+        // no k_prep (recs_stand) leaves them as the binning that built the lists left them
         if (attempt > 0 || S * im->B == 0) HIP_TRY(hipMemsetAsync(im->d_cursor, 0, sizeof(unsigned long long) * 4, st));
         // one event pair over the binning kernels: start on the first, stop on the last
         int pi = prof_slot(c, CEL_K_BIN);

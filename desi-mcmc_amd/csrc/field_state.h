@@ -150,6 +150,23 @@ struct FieldState {
                (!need_partials || (model.partials_gen == model.lambda_gen && !nelec_shared));
     }
 
+    // the records, boxes, kinds and status words in the tables are what a k_prep of exactly this catalogue generation of S
+    // sources would store now, AND the tile lists with their counts, offsets and cursor words were binned from that table by
+    // the last general render, which was of this generation: a general render may launch NO k_prep (the binning launch then
+    // leaves everything as it is, k_prep_bin.h: BIN_LEAVE).  The records are a function of the catalogue's rows, the bands'
+    // WCS and PSF tables, the window and S -- no sky level, pixel, threshold or kernel choice enters them -- so what falsifies
+    // it is: any change of the catalogue (a new src.gen: cel_sources_set / _set_rows with whatever values, every sampler, the
+    // flux step, the type move), another catalogue object or generation prepared or rendered into this set (records_written,
+    // small_star_render: recs_gen is theirs), new_window, records_regrown, ANY k_prep outside a render (records_written drops
+    // binned_S: it zeroed the cursor words; a partial or box-less one writes generation 0), a render that did not end well
+    // (render_begins drops lists_gen, only render_succeeded sets it again; render_overflowed), lists_regrown,
+    // bin_form_changed, and the option (CEL_OPT_INCREMENTAL = 0: never).  Another image set rendered from the same catalogue
+    // changes no stamp here.  Asked BEFORE render_begins; the render's own terms (the general path, no live list, boxes
+    // wanted, no list buffer re-allocated in this call) stay in render_impl.
+    bool prep_stands(const SourceStamps &src, int64_t S, bool option_on) const {
+        return option_on && rec.of(src) && rec.last_S == S && lists.lists_gen == src.gen && lists.binning_of(S);
+    }
+
     // ---- events: the only writers ----
     // cel_images_set_nelec: the partials were formed against the old pixels, the resident split was drawn from them
     void new_pixels() { model.partials_gen = 0; split.drop(); nelec_u16 = false; }

@@ -16,7 +16,8 @@
 //
 // Every kernel here takes a BinStep (k_prep_bin.h): when this render's k_prep found no (box, kind) to change and the host
 // vouches that the lists in front of it were binned from exactly this table, every block returns at its first instruction
-// and block 0 puts the cursor words of that binning back.  The launch (and its event pair) stays.
+// and block 0 puts the cursor words of that binning back.  When the render launched no k_prep at all (BIN_LEAVE) every block
+// returns and nobody writes a word.  The launch (and its event pair) stays.
 #pragma once
 #include "device_common.h"
 #include "k_prep_bin.h"

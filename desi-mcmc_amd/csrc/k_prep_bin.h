@@ -201,6 +201,10 @@ __device__ __forceinline__ void prep_one(const BandDev *__restrict__ bands, int 
 // A binning kernel whose step stands in none of the BIN_NCHANGED words has the lists of exactly this table in front of it -- when
 // the host vouches for that (ListStamps::binning_of, field_state.h; force = 1 otherwise) -- and returns at once, its block 0
 // putting the saved words back: the mailbox copy then carries the totals and flags of the binning that built the lists.
+// A render that launched NO k_prep (the records and the lists both stand, FieldState::prep_stands) has nothing saved for it:
+// BIN_KEEP holds what the last k_prep saved, which may be the totals of an older binning than the one that built the lists.  Its
+// binning launch runs in the third state, BIN_LEAVE: every block returns and nobody writes a word -- the cursor words are
+// those the last real binning, or the last put-back, left, and the mailbox copy reads them.
 // (Why not ONE word: in a chain that moves every source, every wave of k_prep stores it, and stores to one cache line queue up
 // behind one another -- 782 of them cost the flagship's k_prep 21 us.  Dealt over 32 lines of their own they cost nothing.)
 #define BIN_KEEP 4
@@ -208,14 +212,18 @@ __device__ __forceinline__ void prep_one(const BandDev *__restrict__ bands, int 
 #define BIN_CHANGED 16          // (the cursor words start a line of their own: the changed-at words follow on the next)
 #define BIN_NCHANGED 32
 #define BIN_WORDS (BIN_CHANGED + BIN_LINE * BIN_NCHANGED)
+#define BIN_IF_CHANGED 0        // bin when a changed-at word holds this step; otherwise return, block 0 putting the saved words back
+#define BIN_ALWAYS 1            // bin whatever the words say
+#define BIN_LEAVE 2             // no k_prep ran for this render: return, and leave every word as it is
 struct BinStep {
     unsigned long long *words;      // the BIN_WORDS words: cursors, saved cursors, changed-at words
-    unsigned long long step;        // this render's step number (never 0)
-    int force;                      // 1: bin whatever the words say
+    unsigned long long step;        // this render's step number (never 0; not read under BIN_ALWAYS / BIN_LEAVE)
+    int mode;                       // BIN_IF_CHANGED, BIN_ALWAYS, BIN_LEAVE
 };
 // true: nothing to do (every thread of the block gets the same answer)
 __device__ __forceinline__ bool bin_unchanged(const BinStep &bs) {
-    if (bs.force) return false;
+    if (bs.mode == BIN_ALWAYS) return false;
+    if (bs.mode == BIN_LEAVE) return true;
     int hit = 0;
     if (threadIdx.x < BIN_NCHANGED) hit = bs.words[BIN_CHANGED + BIN_LINE * threadIdx.x] == bs.step;
     if (__syncthreads_or(hit)) return false;        // (bs and the words are the same for every thread of every block)

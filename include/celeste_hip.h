@@ -81,7 +81,10 @@ enum {
                                from its complete source list, so every pixel and the log-likelihood are the full render's bit
                                for bit (source preparation and binning still run in full).  The reference's single-source moves
                                (util/infer/mcmc_transitions.py:37-152) evaluate the whole likelihood after changing one source.
-                               A render after cel_sources_set, or with nothing changed, renders every tile.  0 = always every tile */
+                               A render after cel_sources_set, or with nothing changed, renders every tile.  A render of a
+                               catalogue that has not changed since this image set's last render of it (a new sky level or new
+                               pixels in between, a log-likelihood after a plain render) prepares no source again: the records
+                               and tile lists on the device are this catalogue's.  0 = always every tile, always prepared and binned */
     CEL_OPT_SPLIT_FULL_BOX = 15, /* 0 (default): the photon split gives a source photons only STRICTLY inside its box on the low side, as
                                the reference does (celeste_sample_sources.pyx:50-51: the first row and column of every sample patch
                                stay 0) -- although the renderer adds the source on its whole box (celeste.py:217-219).  1 = on the
