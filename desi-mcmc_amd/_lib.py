@@ -30,6 +30,9 @@ CEL_OPT_SLICE_CONDITIONAL = 18
 #: which conditional the resident gradient (cel_patch_loglik_multi's resident mode 8) and the HMC step (cel_slice_sample, param 3)
 #: differentiate: 0 the reference's (default), 1 the exact one (ImageSet.patch_loglik_resident_grad / hmc_step(conditional=))
 CEL_OPT_GRAD_CONDITIONAL = 19
+#: 1 (default): renders that prepare no source load every record's mixture components from a cache built once per record
+#: generation (k_comps, counted under KERNELS["gmm"]; k_render_hwc) -- the same bits as the plain kernel's; 0 = never
+CEL_OPT_COMP_CACHE = 20
 #: CEL_OPT_TAIL_LOG presets.  32 (the default): a skipped component is below eps * e^-32 on its tile, model pixels
 #: agree with the reference to ~1e-13, which is what the parity tests assert (1e-10).  20: the documented fast
 #: preset for callers that need only north_star's 1e-6 -- a skipped component is below eps * 2e-9, the sum of

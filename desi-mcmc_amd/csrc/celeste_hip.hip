@@ -187,6 +187,7 @@ struct cel_ctx {
     int honour_mask = 0;        // CEL_OPT_HONOUR_MASK
     int slice_conditional = 0;  // CEL_OPT_SLICE_CONDITIONAL
     int grad_conditional = 0;   // CEL_OPT_GRAD_CONDITIONAL
+    int comp_cache = (getenv("CEL_COMP_CACHE") && atoi(getenv("CEL_COMP_CACHE")) == 0) ? 0 : 1;          // CEL_OPT_COMP_CACHE (the env var: the initial value, for A/B runs)
     int incremental = (getenv("CEL_INCREMENTAL") && atoi(getenv("CEL_INCREMENTAL")) == 0) ? 0 : 1;       // CEL_OPT_INCREMENTAL
     int tile_parts = (getenv("CEL_TILE_PARTS") && (atoi(getenv("CEL_TILE_PARTS")) == 1 || atoi(getenv("CEL_TILE_PARTS")) == 2 || atoi(getenv("CEL_TILE_PARTS")) == 4))
                          ? atoi(getenv("CEL_TILE_PARTS")) : 0;       // CEL_OPT_TILE_PARTS (the env var: the initial value, for A/B runs)
@@ -244,6 +245,7 @@ struct cel_images : FieldState {
     DevBuf<int4> d_boxes;
     DevBuf<int> d_kind;
     DevBuf<int> d_status;          // per (band, source): 1 has a stamp, 0 empty box, -1 overlap-test miss
+    DevBuf<double> d_comps;        // the component cache: COMP_ROW doubles per (band, source) record (k_comps.h; rec.comps_gen), grown on first use
     // the host copy of the boxes / status that cel_stamp_boxes / cel_source_boxes hand out (rec.hbox_gen):
     // a stamp call (boxes, then stamps) runs k_prep and the D2H once, not twice
     DevBuf<unsigned long long> d_massfx;      // the split's integer stamp-mass sums (k_split.h, k_border.h), per (source, band): split.massfx_gen
@@ -628,6 +630,11 @@ int cel_ctx_set_option(cel_ctx *c, int key, double v) {
         if (v != 0.0 && v != 1.0) return fail(CEL_ERR_INVALID, "CEL_OPT_GRAD_CONDITIONAL must be 0 (the reference's conditional) or 1 (the exact one)");
         c->grad_conditional = (int)v;
         return CEL_OK;
+    case CEL_OPT_COMP_CACHE:
+        static_assert(CEL_OPT_COMP_CACHE == 20, "the key is 20 in every binding");
+        if (v != 0.0 && v != 1.0) return fail(CEL_ERR_INVALID, "CEL_OPT_COMP_CACHE must be 0 or 1");
+        c->comp_cache = (int)v;
+        return CEL_OK;
     case CEL_OPT_TILE_PARTS:
         if (v != 0.0 && v != 1.0 && v != 2.0 && v != 4.0) return fail(CEL_ERR_INVALID, "CEL_OPT_TILE_PARTS must be 0 (by the frame's size), 1, 2 or 4");
         c->tile_parts = (int)v;
@@ -693,6 +700,7 @@ int cel_ctx_get_option(cel_ctx *c, int key, double *v) {
     case CEL_OPT_HONOUR_MASK: *v = c->honour_mask; return CEL_OK;
     case CEL_OPT_SLICE_CONDITIONAL: *v = c->slice_conditional; return CEL_OK;
     case CEL_OPT_GRAD_CONDITIONAL: *v = c->grad_conditional; return CEL_OK;
+    case CEL_OPT_COMP_CACHE: *v = c->comp_cache; return CEL_OK;
     case CEL_OPT_PROFILE: *v = (double)c->profile; return CEL_OK;
     case CEL_OPT_TILE_ORDER: *v = (double)c->tile_order; return CEL_OK;
     case CEL_OPT_TILE_ROWS: *v = c->tile_rows; return CEL_OK;
@@ -1249,7 +1257,9 @@ static void launch_bin_fine(cel_ctx *c, cel_images *im, int64_t S, int NS, bool 
 }
 
 // the render kernel of the image set's tile layout and the plan
-static void launch_render(cel_ctx *c, const cel_images *im, const RenderPlan &p, int T, const RenderArgs &a, hipEvent_t e0, hipEvent_t e1) {
+// comps != nullptr: the general one-block kernel on the component cache (the caller has checked that the plan is that kernel's)
+static void launch_render(cel_ctx *c, const cel_images *im, const RenderPlan &p, int T, const RenderArgs &a, hipEvent_t e0, hipEvent_t e1,
+                          const double *comps = nullptr) {
     hipStream_t st = c->stream;
     if (im->TW == QW_TW)
         LAUNCH_EV(k_render_qw, dim3(T), dim3(64), st, e0, e1, a);
@@ -1263,6 +1273,7 @@ static void launch_render(cel_ctx *c, const cel_images *im, const RenderPlan &p,
             if (p.parts == 4) LAUNCH_EV((k_render_hw<false, 4>), dim3(grid), dim3(64), st, e0, e1, a);
             else LAUNCH_EV((k_render_hw<false, 2>), dim3(grid), dim3(64), st, e0, e1, a);
         }
+        else if (comps) LAUNCH_EV(k_render_hwc, dim3(T), dim3(64), st, e0, e1, a, comps);
         else LAUNCH_EV(k_render_hw<false>, dim3(T), dim3(64), st, e0, e1, a);
     }
     else if (im->TH == 64)
@@ -1390,6 +1401,25 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
         if (rc) return rc;
     }
     if (incr) mark_dirty();     // ... and the tiles their new boxes touch
+    // The component cache (k_comps.h).  A render that launched no k_prep reads records that stand from call to call: what a
+    // tile entry's set-up computes from its record alone is built once per record generation, in front of the first such
+    // render, and loaded by this and every later one (k_render_hwc) until an event disowns the records.  A render whose k_prep
+    // ran takes the plain kernel and leaves the cache stale (records_written): the dirty-tile render, the chain that moves
+    // every source and the whole upload run exactly the code they ran without it.
+    const double *comps = nullptr;
+    if (recs_stand && c->comp_cache && im->TW == HW_TW && !diag && !plan.stars_only && parts == 1 && c->variant != 0 && S > 0) {
+        const int64_t n_rec = S * im->B;
+        const int64_t cap0 = im->d_comps.cap;
+        HIP_TRY(im->d_comps.grow(n_rec * COMP_ROW, n_rec * COMP_ROW + n_rec * COMP_ROW / 4, st));
+        if (im->d_comps.cap != cap0 || !im->rec.comps_of_records()) {      // (a block just allocated holds nobody's rows)
+            int pi = prof_slot(c, CEL_K_GMM);
+            LAUNCH_EV(k_comps, dim3((unsigned)((n_rec + COMPS_WAVES - 1) / COMPS_WAVES)), dim3(64 * COMPS_WAVES), st, EV0(c, pi), EV1(c, pi),
+                      (const BandDev *)im->d_bands, (const SrcRec *)im->d_recs, S, n_rec, im->d_comps.get());
+            HIP_TRY(hipGetLastError());
+            im->comps_built();
+        }
+        comps = im->d_comps;
+    }
     for (int attempt = 0; attempt < 8; attempt++) {
         // (a retry bins: its cursor words were zeroed by hand, the attempt before it left half-built lists)
         const BinStep bs = {im->d_cursor, im->bin_step, attempt > 0 ? BIN_ALWAYS : (recs_stand ? BIN_LEAVE : (bins_stand ? BIN_IF_CHANGED : BIN_ALWAYS))};
@@ -1445,7 +1475,7 @@ static int render_impl(cel_images *im, cel_sources *src, int flags, double *ll_b
             a.slabs = im->d_slabs; a.part_cnt = im->d_part_cnt;
         }
         pi = prof_slot(c, plan.stars_only ? CEL_K_RENDER_STARS : CEL_K_RENDER);
-        launch_render(c, im, plan, T, a, EV0(c, pi), EV1(c, pi));
+        launch_render(c, im, plan, T, a, EV0(c, pi), EV1(c, pi), comps);
         if (plan.masked_ll) launch_masked_ll(c, im, plan);
         else if (flags & CEL_RENDER_LOGLIK) {
             pi = prof_slot(c, CEL_K_REDUCE);

@@ -57,7 +57,12 @@ struct SourceStamps {
 struct RecordStamps {
     uint64_t recs_gen = 0, hbox_gen = 0;    // the catalogue generation they belong to (0: nobody's)
     int64_t last_S = 0;                     // sources of the last k_prep
+    uint64_t comps_gen = 0;                 // the record generation the component cache (k_comps.h) was built from (0: of none)
     bool of(const SourceStamps &src) const { return src.gen != 0 && recs_gen == src.gen; }
+    // the component cache holds the rows k_comps would build NOW from the records that stand in d_recs: it was built from records
+    // of this generation, and nobody has written, re-allocated or disowned the records since (those events zero the stamp).  The
+    // rows are a function of the records and the bands' PSF tables alone: no sky level, threshold, tile or kernel choice
+    bool comps_of_records() const { return comps_gen != 0 && comps_gen == recs_gen; }
     bool host_boxes_of(const SourceStamps &src) const { return of(src) && hbox_gen == src.gen; }
 };
 
@@ -177,16 +182,19 @@ struct FieldState {
     void new_sky_level() { model.lambda_gen = 0; model.partials_gen = 0; }
     // cel_images_set_window (another window than before): boxes are cut to the window, and the resident split's patches are
     // boxes of the old one
-    void new_window() { rec.recs_gen = rec.hbox_gen = 0; model.lambda_gen = lists.lists_gen = 0; lists.binned_S = -1; split.drop(); }
-    void records_regrown() { rec.recs_gen = rec.hbox_gen = 0; lists.binned_S = -1; }
+    void new_window() { rec.recs_gen = rec.hbox_gen = rec.comps_gen = 0; model.lambda_gen = lists.lists_gen = 0; lists.binned_S = -1; split.drop(); }
+    void records_regrown() { rec.recs_gen = rec.hbox_gen = rec.comps_gen = 0; lists.binned_S = -1; }
     // k_prep ran on S sources; gen = 0: a partial table or one without boxes is nobody's.  Whoever ran it, the table the
     // lists were binned from may be gone (a partial k_prep, one without boxes, one that compared against another step's
-    // word): a render asks binning_of BEFORE its own k_prep and vouches again in render_succeeded
-    void records_written(uint64_t gen, int64_t S) { rec.recs_gen = gen; rec.last_S = S; lists.binned_S = -1; }
+    // word): a render asks binning_of BEFORE its own k_prep and vouches again in render_succeeded.  The component cache was built
+    // from the records that stood before: whoever wrote, with whatever values, it is of no records now
+    void records_written(uint64_t gen, int64_t S) { rec.recs_gen = gen; rec.last_S = S; rec.comps_gen = 0; lists.binned_S = -1; }
+    // k_comps ran on the records that stand (a general render that launched no k_prep: prep_stands held)
+    void comps_built() { rec.comps_gen = rec.recs_gen; }
     void host_boxes_read(uint64_t gen) { rec.hbox_gen = gen; }
     // the one-launch render of a small star field wrote k_prep's records, no tile lists and no tile durations
     void small_star_render(uint64_t gen, int64_t S, bool stored) {
-        rec.recs_gen = gen; rec.last_S = S;
+        rec.recs_gen = gen; rec.last_S = S; rec.comps_gen = 0;
         lists.lists_gen = 0; lists.cost_S = lists.order_S = -1; lists.binned_S = -1;
         if (stored) model.lambda_gen = 0;
     }

@@ -12,6 +12,7 @@
 // Component parameters are read from LDS per half (two broadcast addresses per read).
 #pragma once
 #include "k_render.h"
+#include "k_comps.h"
 
 // timing-only ablation bits of CEL_OPT_DEBUG ride in bits 8.. of the render flags; they exist only in a
 // -DCEL_ABLATE build (tools/ablate_render.py builds its own library), never in the shipped one
@@ -607,9 +608,18 @@ static_assert(sizeof(CompTab) >= 128 * sizeof(double), "log table must fit the c
 // acquire, plain loads): correct wherever a tile's parts run.  A tile's parts sit on ONE XCD (block id -> XCD is round
 // robin: ids that agree mod 8 share an L2), where the slabs are read at twice the cross-XCD rate.  Values agree with the
 // one-wave form to rounding (a pixel's terms are added part by part), and are the same bits in every run.
-template <bool DIAG, int PARTS = 1>
-__global__ void __launch_bounds__(64)
-k_render_hw(RenderArgs a) {
+//
+// CACHED (the component cache, k_comps.h; the one-block production form only: DIAG = false, PARTS = 1, variant != 0).  What a
+// galaxy entry's set-up computes from the record and the band's PSF alone -- make_comp_lc, exp(-qc), log |A|: about 100 of the
+// set-up's 342 VALU instructions, fourteen of the record's nineteen v_readlane among them -- is loaded from the record's row of
+// `comps` instead, eight coalesced loads per lane issued where the NEXT entry's record is fetched (its list index is known one
+// entry early), so they land under the current entry's walk.  From the record only the box and the type are taken; the drop
+// test, the row ranges, the slot sort and the table writes run unchanged on the loaded values, which are the bits the plain
+// path computes (k_comps runs the same functions), so every decision, table entry and pixel is the plain kernel's.  LaneConst
+// (29 VGPRs held across the entry loop) does not exist in this form: a refused star's three components are in its row too.
+template <bool DIAG, int PARTS, bool CACHED>
+__device__ __forceinline__ void render_hw_body(const RenderArgs &a, const double *__restrict__ comps) {
+    static_assert(!CACHED || (!DIAG && PARTS == 1), "the cached path is the one-block production form's");
     __shared__ double acc[HW_TH * HW_TW];
     __shared__ CompTab T;
     __shared__ double et[64];
@@ -682,7 +692,8 @@ k_render_hw(RenderArgs a) {
         star_pass<DIAG>(a, *reinterpret_cast<StarTab *>(&T), et, acc, recs, off, nstar, lane, X0, Y0, strict, dbg_halfrows, dbg_pairs,
                         PARTS > 1 ? part : 0, peff);
 
-    const LaneConst lc = lane_consts(lane, bd);
+    LaneConst lc;
+    if constexpr (!CACHED) lc = lane_consts(lane, bd);
     // the rest of the tile's list (everything when there was no star pass), 64 indices per coalesced
     // load; the next source's record is in flight while the current one is evaluated
     const int64_t off2 = off + nstar_all + (PARTS > 1 ? part : 0);
@@ -690,12 +701,23 @@ k_render_hw(RenderArgs a) {
     if (PARTS > 1) nent = (nent > part) ? (nent - part + peff - 1) / peff : 0;            // entries part, part + peff, ... of the rest
     int idx64 = (lane < nent) ? a.lists[off2 + (int64_t)peff * lane] : 0;
     int recw_next = (nent > 0) ? rec_fetch(recs, __builtin_amdgcn_readlane(idx64, 0), lane) : 0;
+    // CACHED: the rows of this band's records; an entry's row is in flight one entry ahead, beside its record
+    const double *const crows = CACHED ? comps + (int64_t)b * a.S * COMP_ROW : nullptr;
+    // (EVERY lane loads -- those behind the last component read its words again and use none of them: with the loads under
+    // `lane < K_GAL` the compiler merged the loaded registers with a copy of their old values on both sides of the branch, 17
+    // more v_mov per entry, and the kernel measured 0.7 % under the plain one instead of 3 %, profiles/comp_cache_ab.txt)
+    const int clane = min(lane, K_GAL - 1);
+    CompRow crow_next = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.f};
+    if (CACHED && nent > 0) crow_next = comp_row_load(crows + (int64_t)__builtin_amdgcn_readlane(idx64, 0) * COMP_ROW, clane);
 
     for (int e = 0; e < nent; e++) {
         const int recw = recw_next;
+        const CompRow crow = crow_next;
         if (e + 1 < nent) {
             if (((e + 1) & 63) == 0) idx64 = (e + 1 + lane < nent) ? a.lists[off2 + (int64_t)peff * (e + 1 + lane)] : 0;
-            recw_next = rec_fetch(recs, __builtin_amdgcn_readlane(idx64, (e + 1) & 63), lane);
+            const int s_next = __builtin_amdgcn_readlane(idx64, (e + 1) & 63);
+            recw_next = rec_fetch(recs, s_next, lane);
+            if (CACHED) crow_next = comp_row_load(crows + (int64_t)s_next * COMP_ROW, clane);
         }
         const RecU rec = rec_unpack(recw);
         const RecU *rp = &rec;
@@ -711,8 +733,16 @@ k_render_hw(RenderArgs a) {
         Comp c;
         int Lk = 0, rlo = ra, rhi = rb;
         if (lane < K) {
-            c = make_comp_lc(lc, rec);
-            double Tk = dropping ? Tdrop + (double)(__logf((float)fabs(c.A)) - log_eps) : 100.0;   // T + log(A / eps), no fp64 division
+            float logA;
+            if constexpr (CACHED) {
+                c.A = crow.A; c.mx = crow.mx; c.my = crow.my; c.qa = crow.qa; c.qb = crow.qb; c.qc = crow.qc;
+                c.ixx = c.iyy = 0.0;      // (the marginals feed the DIAG counters only)
+                logA = crow.logA;
+            } else {
+                c = make_comp_lc(lc, rec);
+                logA = comp_log_amp(c.A);
+            }
+            double Tk = dropping ? Tdrop + (double)(logA - log_eps) : 100.0;   // T + log(A / eps), no fp64 division
             if (dropping) {
                 // rows on which the component can matter on THIS tile's columns, and from the same ellipse the drop test: the
                 // minimum of the form over the rectangle (quad_min_rect, ~45 VALU) only for the few components per 10^5 whose
@@ -754,7 +784,7 @@ k_render_hw(RenderArgs a) {
             const int p = slot;
             T.A[p] = c.A; T.mx[p] = c.mx; T.my[p] = c.my;
             T.qa[p] = c.qa * EXP_SCALE; T.qb[p] = c.qb * EXP_SCALE; T.qc[p] = c.qc * EXP_SCALE;
-            T.eq[p] = exp_tab64(-c.qc * EXP_SCALE, et);
+            T.eq[p] = CACHED ? crow.eq : comp_eq(c.qc, et);
             // LDS operations of one wave execute in order: the min/max below land after the resets above
             const int gi = p / (2 * REC_G);
             atomicMin(&T.gL[gi], Lk);
@@ -881,4 +911,17 @@ k_render_hw(RenderArgs a) {
         if ((a.flags >> 8) & 128)   // diagnostic (tools/row_waste.py): what the kept components need one by one
             timing[3 * (size_t)tile + 2] = (unsigned long long)dbg_pairrows | ((unsigned long long)(unsigned)(dbg_area / 32.f) << 32);
     }
+}
+
+template <bool DIAG, int PARTS = 1>
+__global__ void __launch_bounds__(64)
+k_render_hw(RenderArgs a) {
+    render_hw_body<DIAG, PARTS, false>(a, nullptr);
+}
+
+// the one-block production form on the component cache: comps = the image set's rows, built by k_comps from the records that
+// stand in a.recs (the host vouches: RecordStamps::comps_of_records)
+__global__ void __launch_bounds__(64)
+k_render_hwc(RenderArgs a, const double *__restrict__ comps) {
+    render_hw_body<false, 1, true>(a, comps);
 }

@@ -85,6 +85,13 @@ enum {
                                catalogue that has not changed since this image set's last render of it (a new sky level or new
                                pixels in between, a log-likelihood after a plain render) prepares no source again: the records
                                and tile lists on the device are this catalogue's.  0 = always every tile, always prepared and binned */
+    /* component cache: */ CEL_OPT_COMP_CACHE = 20,  /* 1 (default): a general cel_render_field that prepares no source (see CEL_OPT_INCREMENTAL: the records
+                               on the device are this catalogue's) builds every record's mixture components once -- k_comps, timed
+                               under CEL_K_GMM -- and this and the following such renders load them per tile entry instead of
+                               computing them (k_render_hwc; the one-block form of the 32 x 64 layout: CEL_OPT_TILE_PARTS = 1 or a
+                               frame of more than 3 072 tiles).  The rows hold what the plain kernel computes, bit for bit, so
+                               pixels and log-likelihoods are the same bits either way; 2 520 bytes per (band, source).  A render
+                               that prepares its sources takes the plain kernel.  0 = always the plain kernel */
     CEL_OPT_SPLIT_FULL_BOX = 15, /* 0 (default): the photon split gives a source photons only STRICTLY inside its box on the low side, as
                                the reference does (celeste_sample_sources.pyx:50-51: the first row and column of every sample patch
                                stay 0) -- although the renderer adds the source on its whole box (celeste.py:217-219).  1 = on the
@@ -212,7 +219,7 @@ enum {
 /* kernels reported by cel_profile_get */
 enum {
     CEL_K_PREP = 0, CEL_K_BIN = 1, CEL_K_RENDER = 2, CEL_K_REDUCE = 3, CEL_K_STAMPS = 4,
-    CEL_K_GMM = 5,
+    CEL_K_GMM = 5,          /* the mixture builders: cel_mog_loglike, cel_galaxy_mixture_params, and k_comps (CEL_OPT_COMP_CACHE) */
     CEL_K_PATCH_LL = 6,     /* k_patch_ll[_hw]: cel_patch_loglik[_multi] and every round of cel_slice_locations */
     CEL_K_SPLIT = 7,        /* k_photon_split[_hw] */
     CEL_K_MASS = 8,         /* cel_stamp_mass */
