@@ -7,8 +7,8 @@
 //
 // k_mass_grad: one wave per (proposal, band, part), the seven sums u; m0, m1; w00, w01, w11; th of k_patch_grad's layout (GRAD_NS
 // doubles per part), so that k_patch_grad_chain (mode 2: no - wsum on the counts entry) takes them to the public coordinates
-// unchanged.  The rows of the box are dealt to PGRAD_PARTS parts from the box's size alone.  The component table is
-// k_patch_grad's (grad_src_body's arithmetic, restated: k_patch_grad.h keeps its bits); the pixels of a part are lane-strided;
+// unchanged.  The rows of the box are dealt to PGRAD_PARTS parts from the box's size alone.  The component table and the
+// per-pixel terms are k_patch_grad's (grad_tab_fill and grad_pixel, k_grad_common.h); the pixels of a part are lane-strided;
 // per pixel K direct exponentials.  NOTHING IS DROPPED: this is the plain form, every component at every pixel; neither
 // CEL_OPT_TAIL_LOG_SOURCE nor CEL_OPT_KERNEL is read, so the bits depend on the inputs alone (fixed order, wave_sum, no atomics).
 // A proposal without a stamp (record type < 0: own box empty, overlap-test miss) and a retired slot (owner < 0) write zeros:
@@ -24,7 +24,7 @@
 __global__ void __launch_bounds__(64)
 k_mass_grad(const BandDev *__restrict__ bands, int B, int64_t P, const SrcRec *__restrict__ recs /* [B][P], WITH boxes */,
             const int *__restrict__ owner /* P, or nullptr */, double *__restrict__ sums /* P*B*PGRAD_PARTS*GRAD_NS */) {
-    __shared__ double tab[8 * K_GAL];      // A, B, mx, my, qa, qb, qc, var (k_patch_grad's layout)
+    __shared__ double tab[GRAD_TAB];
     const int lane = threadIdx.x;
     const int part = (int)(blockIdx.x % (unsigned)PGRAD_PARTS);
     const int64_t job = (int64_t)(blockIdx.x / (unsigned)PGRAD_PARTS);
@@ -46,64 +46,15 @@ k_mass_grad(const BandDev *__restrict__ bands, int B, int64_t P, const SrcRec *_
     const BandDev *bd = bands + b;
     const bool gal = (type != 0);
     const int K = gal ? K_GAL : K_PSF;
-    if (lane < K) {
-        // k_patch_grad's table: A = theta_k A', the theta factor kept apart
-        const int kk = gal ? lane / K_PROF : lane;
-        double cxx = bd->cxx[kk], cxy = bd->cxy[kk], cyy = bd->cyy[kk], wt = bd->w[kk];
-        double var = 0.0, tf = 1.0, sg = 0.0;
-        if (gal) {
-            const int j = c_prof_order[lane - kk * K_PROF];
-            var = c_prof_var[j];
-            cxx += var * rp->w00; cxy += var * rp->w01; cyy += var * rp->w11;
-            wt *= c_prof_amp[j];
-            const bool ex = (j < K_EXP);
-            tf = ex ? rp->theta : 1.0 - rp->theta;
-            sg = ex ? 1.0 : -1.0;
-        }
-        const double det = cxx * cyy - cxy * cxy;
-        const double inv = 1.0 / det;
-        const double a1 = wt * (0.5 / PI_D) * sqrt(inv);
-        tab[lane] = tf * a1;
-        tab[K_GAL + lane] = sg * a1;
-        tab[2 * K_GAL + lane] = rp->px + bd->mux[kk];
-        tab[3 * K_GAL + lane] = rp->py + bd->muy[kk];
-        tab[4 * K_GAL + lane] = cyy * inv; tab[5 * K_GAL + lane] = -cxy * inv; tab[6 * K_GAL + lane] = cxx * inv;
-        tab[7 * K_GAL + lane] = var;
-    }
+    if (lane < K) grad_tab_fill(bd, *rp, gal, lane, tab);
     __syncthreads();
-    const double *tA = tab, *tB = tab + K_GAL, *tmx = tab + 2 * K_GAL, *tmy = tab + 3 * K_GAL, *tqa = tab + 4 * K_GAL,
-                 *tqb = tab + 5 * K_GAL, *tqc = tab + 6 * K_GAL, *tvar = tab + 7 * K_GAL;
     double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     const int n = nx * (rb - ra);
     for (int i = lane; i < n; i += 64) {
         const int yy = i / nx, xx = i - yy * nx;
-        const double x = (double)(x0 + xx), y = (double)(y0 + ra + yy);
-        for (int k = 0; k < K; k++) {
-            const double dx = x - tmx[k], dy = y - tmy[k];
-            const double qa = tqa[k], qb = tqb[k], qc = tqc[k];
-            const double pdx = fma(qa, dx, qb * dy), pdy = fma(qb, dx, qc * dy);
-            const double h = 0.5 * fma(dx, pdx, dy * pdy);
-            const double e = exp(-h);
-            const double g = tA[k] * e;
-            acc[0] += g;
-            acc[1] = fma(g, pdx, acc[1]);
-            acc[2] = fma(g, pdy, acc[2]);
-            if (gal) {
-                const double hv = 0.5 * tvar[k] * g;
-                acc[3] = fma(hv, fma(pdx, pdx, -qa), acc[3]);
-                acc[4] = fma(hv, fma(pdx, pdy, -qb), acc[4]);
-                acc[5] = fma(hv, fma(pdy, pdy, -qc), acc[5]);
-                acc[6] = fma(tB[k], e, acc[6]);
-            }
-        }
+        grad_pixel<false>(tab, nullptr, K, gal, (double)(x0 + xx), (double)(y0 + ra + yy), acc);      // r = 1 at every pixel
     }
-#pragma unroll
-    for (int i = 0; i < 7; i++) acc[i] = wave_sum(acc[i]);
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 7; i++) out[i] = acc[i];
-        out[7] = 0.0;
-    }
+    grad_store_sums(acc, lane, out);
 }
 
 __global__ void __launch_bounds__(256)

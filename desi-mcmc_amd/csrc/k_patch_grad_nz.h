@@ -229,7 +229,8 @@ pgrad_nz_sums(const BandDev *__restrict__ bands, int B, int64_t P, const SrcRec 
 #pragma unroll
     for (int i = 0; i < 16; i++) rk[i] = 0.0;
     if (lane < K) {
-        // grad_src_body's quantities (A = theta_k A' with the theta factor kept apart, B = d A / d theta), reciprocals by Newton steps
+        // grad_tab_fill's quantities (k_grad_common.h: A = theta_k A' with the theta factor kept apart, B = d A / d theta), kept as
+        // this kernel's own copy: reciprocals by Newton steps, centres seen from the source, the record in registers
         const int kk = gal ? lane / K_PROF : lane;
         double cxx = bd->cxx[kk], cxy = bd->cxy[kk], cyy = bd->cyy[kk], wt = bd->w[kk];
         const double ux = bd->mux[kk], uy = bd->muy[kk];           // the component's centre seen from the source
@@ -305,11 +306,5 @@ pgrad_nz_sums(const BandDev *__restrict__ bands, int B, int64_t P, const SrcRec 
             else pgnz_trip_quad<1, false>(L, n, i0, lane, K, tc, et, rec.px, rec.py, counts, acc);
         }
     }
-#pragma unroll
-    for (int i = 0; i < 7; i++) acc[i] = wave_sum(acc[i]);
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 7; i++) out[i] = acc[i];
-        out[7] = 0.0;
-    }
+    grad_store_sums(acc, lane, out);
 }
