@@ -33,6 +33,10 @@ CEL_OPT_GRAD_CONDITIONAL = 19
 #: 1 (default): renders that prepare no source load every record's mixture components from a cache built once per record
 #: generation (k_comps, counted under KERNELS["gmm"]; k_render_hwc) -- the same bits as the plain kernel's; 0 = never
 CEL_OPT_COMP_CACHE = 20
+#: 1 (with CEL_OPT_HONOUR_MASK = 1): the device samplers of the exact conditional (cel_slice_sample under CEL_OPT_SLICE_CONDITIONAL /
+#: CEL_OPT_GRAD_CONDITIONAL = 1) and the exact resident mode 8 accept a masked image set and charge the OBSERVED stamp mass and its
+#: derivative (ImageSet.slice_sample / type_move / hmc_step / patch_loglik_resident_grad(mask="honour")); 0 (default): they refuse it
+CEL_OPT_SAMPLER_MASK = 21
 #: CEL_OPT_TAIL_LOG presets.  32 (the default): a skipped component is below eps * e^-32 on its tile, model pixels
 #: agree with the reference to ~1e-13, which is what the parity tests assert (1e-10).  20: the documented fast
 #: preset for callers that need only north_star's 1e-6 -- a skipped component is below eps * 2e-9, the sum of

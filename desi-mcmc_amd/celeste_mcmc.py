@@ -217,8 +217,16 @@ class ModelGibbs(object):
 
     def __init__(self, fields, typ, u, fluxes, shape, seed=0, flux_a_0=5., flux_b_0=.005, slice_args=None, engine="auto",
                  deal=None, shape_args=None, shape_logprior=None, phi_period=180., shape_mass="reference", conditional="reference",
-                 mask="refuse", type_log_odds=0.0, grad_route="dense", hmc_conditional=None):
+                 mask="refuse", type_log_odds=0.0, grad_route="dense", hmc_conditional=None, mask_engine="host"):
         self.fields = list(fields)
+        # mask_engine: which slice engine a masked sweep (mask="honour") may take.  "host" (default): the host engine, as ever --
+        # engine="device" raises.  "device": the device samplers of the exact conditional charge the OBSERVED mass per round
+        # (CEL_OPT_SAMPLER_MASK around their calls; ImageSet.slice_sample / type_move / hmc_step(mask="honour")), so engine="auto"
+        # and "device" run the location, shape and type steps -- and, under hmc_conditional="exact", the HMC step -- on the device:
+        # the host engine's chains, bit for bit.  A strip deal and several fields keep the host engine.
+        if mask_engine not in ("host", "device"):
+            raise ValueError("mask_engine must be 'host' or 'device'")
+        self.mask_engine = mask_engine
         # hmc_conditional: what location_loglik_grad and resample_hmc differentiate.  None: the reference's conditional, and under
         # conditional="exact" both raise, as they always have (that default exists only because the suite pins those refusals).
         # "exact" (needs conditional="exact"): the exact conditional's value and gradient -- the proposal's stamp mass on its own
@@ -255,7 +263,7 @@ class ModelGibbs(object):
                 raise ValueError("mask='honour' needs conditional='exact': the reference's location conditional charges "
                                  "counts * sum(psf weights) wherever the source sits, but beside a mask the term is counts * (the "
                                  "stamp's mass over the OBSERVED pixels of the proposal's box), which moves with the proposal")
-            if engine == "device":
+            if engine == "device" and mask_engine != "device":
                 raise ValueError("mask='honour' runs on the host slice engine: the device slice sampler does not charge the "
                                  "observed mass per round (cel_slice_* refuse a masked set)")
             for f in self.fields:
@@ -379,7 +387,9 @@ class ModelGibbs(object):
             if honour and kw.get("conditional", "reference") != "exact":
                 raise ValueError("mask='honour' needs conditional='exact' (the reference's location conditional does not charge "
                                  "the observed mass of the proposal's box)")
-            if honour and kw.get("engine", "auto") == "device":
+            if kw.get("mask_engine", "host") not in ("host", "device"):
+                raise ValueError("mask_engine must be 'host' or 'device'")
+            if honour and kw.get("engine", "auto") == "device" and kw.get("mask_engine", "host") != "device":
                 raise ValueError("mask='honour' runs on the host slice engine")
             if not honour and any(getattr(im, "n_masked", 0) for im in imgs):
                 from ._lib import MaskedImagesError
@@ -671,7 +681,8 @@ class ModelGibbs(object):
             pc = self.counts(f, idx=idx) if cts is None else cts[idx]
             f.prop.set(typ, U, pc, shape)
             with self._grad_route():
-                l, gr, _, gs = f.iset.patch_loglik_resident_grad(f.prop, owner, conditional="exact" if exact else "reference")
+                l, gr, _, gs = f.iset.patch_loglik_resident_grad(f.prop, owner, conditional="exact" if exact else "reference",
+                                                                 mask=self.mask if exact else "refuse")
             ll += l
             g += np.concatenate([gr, gs], axis=1) if shape_grad else gr
         return ll, g
@@ -743,7 +754,7 @@ class ModelGibbs(object):
             ids = np.where(mine & (self.typ == 1), np.arange(self.S), -1).astype(np.int32)
             new, _, st = f.iset.slice_sample(sset, 1, a.get("sigma", 1.0), seed, dirs=dirs, step_out=a.get("step_out", True),
                                              max_steps_out=a.get("max_steps_out", 1000), phi_max=self.phi_period, chain_ids=ids,
-                                             conditional=self.conditional)
+                                             conditional=self.conditional, mask=self._sampler_mask())
             new[:, 2] = np.where(ids >= 0, (new[:, 2] + self.phi_period) % self.phi_period, new[:, 2])
             self.shape = new
             f._uploaded = None                                 # (the device holds the unwrapped angles)
@@ -782,8 +793,13 @@ class ModelGibbs(object):
 
     def _exact_on_device(self):
         """what the exact conditional needs of the chain to run on the device (cel_slice_sample under
-        CEL_OPT_SLICE_CONDITIONAL): whole, unmasked frames"""
-        return self.mask != "honour" and not (self.deal is not None and getattr(self.deal, "kind", "") == "strips")
+        CEL_OPT_SLICE_CONDITIONAL): whole frames, unmasked -- or masked under mask_engine="device" (CEL_OPT_SAMPLER_MASK)"""
+        return ((self.mask != "honour" or self.mask_engine == "device")
+                and not (self.deal is not None and getattr(self.deal, "kind", "") == "strips"))
+
+    def _sampler_mask(self):
+        """the mask= of the device samplers' calls: "honour" on a masked sweep (they run under mask_engine="device" alone)"""
+        return "honour" if self.mask == "honour" and self.conditional == "exact" else "refuse"
 
     def _device_engine_applies(self):
         a = self.slice_args
@@ -808,7 +824,8 @@ class ModelGibbs(object):
         mine = self.active if self.deal is None else (self.active & self.deal.mask)
         ids = np.where(mine, np.arange(self.S), -1).astype(np.int32)
         new_u, _, st = f.iset.slice_sample(sset, 0, a.get("sigma", 1.0), seed, dirs=dirs, step_out=a.get("step_out", True),
-                                           max_steps_out=a.get("max_steps_out", 1000), chain_ids=ids, conditional="exact")
+                                           max_steps_out=a.get("max_steps_out", 1000), chain_ids=ids, conditional="exact",
+                                           mask=self._sampler_mask())
         self.u = new_u
         if getattr(f, "_uploaded", None) is not None:      # the device's catalogue moved with the chains: it IS the new state
             f._uploaded = (f._uploaded[0], new_u.copy(), f._uploaded[2], f._uploaded[3])
@@ -880,7 +897,7 @@ class ModelGibbs(object):
     def _type_engine_on_device(self):
         """the device runs the type step (cel_slice_sample, param 2) where the exact slice engine applies: one field, and
         under conditional="exact" whole, unmasked frames"""
-        ok = len(self.fields) == 1 and self.mask != "honour" and (self.conditional != "exact" or self._exact_on_device())
+        ok = len(self.fields) == 1 and (self.conditional != "exact" or self._exact_on_device())     # (mask="honour" is exact)
         engine = self.type_engine or self.engine
         if engine == "device" and not ok:
             raise ValueError("the device type move runs one field of whole, unmasked frames")
@@ -922,7 +939,8 @@ class ModelGibbs(object):
             f = self.fields[0]
             sset = self._sources(f)
             ids = np.where(runs, ids_all, -1).astype(np.int32)
-            typ, shape, _, st = f.iset.type_move(sset, shapes, h, seed, chain_ids=ids, conditional=self.conditional)
+            typ, shape, _, st = f.iset.type_move(sset, shapes, h, seed, chain_ids=ids, conditional=self.conditional,
+                                                 mask=self._sampler_mask())
             self.typ, self.shape = typ, shape
             if getattr(f, "_uploaded", None) is not None:      # the device's catalogue moved with the chains: it IS the new state
                 f._uploaded = (typ.copy(), f._uploaded[1], f._uploaded[2], shape.copy())
@@ -992,9 +1010,11 @@ class ModelGibbs(object):
     def _hmc_engine_on_device(self):
         """the device runs the HMC step (cel_slice_sample, param 3) where it runs the type step under the reference's
         conditional: one field of unmasked frames"""
-        ok = len(self.fields) == 1 and self.mask != "honour"
+        ok = len(self.fields) == 1
         if self.hmc_conditional == "exact":             # (the exact step's cover test is not window-relative)
             ok = ok and self._exact_on_device()
+        else:                                           # (the reference's conditional charges no observed mass)
+            ok = ok and self.mask != "honour"
         if self.engine == "device" and not ok:
             raise ValueError("the device HMC step runs one field of whole, unmasked frames")
         return ok and self.engine != "host"
@@ -1057,7 +1077,8 @@ class ModelGibbs(object):
             ids = np.where(runs, ids_all, -1).astype(np.int32)
             with self._grad_route():
                 q, pn, _, st = f.iset.hmc_step(sset, p, im, eps, steps, seed, phi_max=self.phi_period, chain_ids=ids,
-                                               conditional="exact" if exact else "reference")
+                                               conditional="exact" if exact else "reference",
+                                               mask=self._sampler_mask() if exact else "refuse")
             evals, accepted = st["evals"], st["accepted"]
         else:
             q, pn = q0.copy(), p.copy()

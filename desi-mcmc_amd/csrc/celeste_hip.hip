@@ -187,6 +187,7 @@ struct cel_ctx {
     int honour_mask = 0;        // CEL_OPT_HONOUR_MASK
     int slice_conditional = 0;  // CEL_OPT_SLICE_CONDITIONAL
     int grad_conditional = 0;   // CEL_OPT_GRAD_CONDITIONAL
+    int sampler_mask = 0;       // CEL_OPT_SAMPLER_MASK
     int comp_cache = (getenv("CEL_COMP_CACHE") && atoi(getenv("CEL_COMP_CACHE")) == 0) ? 0 : 1;          // CEL_OPT_COMP_CACHE (the env var: the initial value, for A/B runs)
     int incremental = (getenv("CEL_INCREMENTAL") && atoi(getenv("CEL_INCREMENTAL")) == 0) ? 0 : 1;       // CEL_OPT_INCREMENTAL
     int tile_parts = (getenv("CEL_TILE_PARTS") && (atoi(getenv("CEL_TILE_PARTS")) == 1 || atoi(getenv("CEL_TILE_PARTS")) == 2 || atoi(getenv("CEL_TILE_PARTS")) == 4))
@@ -635,6 +636,11 @@ int cel_ctx_set_option(cel_ctx *c, int key, double v) {
         if (v != 0.0 && v != 1.0) return fail(CEL_ERR_INVALID, "CEL_OPT_COMP_CACHE must be 0 or 1");
         c->comp_cache = (int)v;
         return CEL_OK;
+    case CEL_OPT_SAMPLER_MASK:
+        static_assert(CEL_OPT_SAMPLER_MASK == 21, "the key is 21 in every binding");
+        if (v != 0.0 && v != 1.0) return fail(CEL_ERR_INVALID, "CEL_OPT_SAMPLER_MASK must be 0 (the samplers refuse a masked set) or 1 (the exact ones honour it)");
+        c->sampler_mask = (int)v;
+        return CEL_OK;
     case CEL_OPT_TILE_PARTS:
         if (v != 0.0 && v != 1.0 && v != 2.0 && v != 4.0) return fail(CEL_ERR_INVALID, "CEL_OPT_TILE_PARTS must be 0 (by the frame's size), 1, 2 or 4");
         c->tile_parts = (int)v;
@@ -701,6 +707,7 @@ int cel_ctx_get_option(cel_ctx *c, int key, double *v) {
     case CEL_OPT_SLICE_CONDITIONAL: *v = c->slice_conditional; return CEL_OK;
     case CEL_OPT_GRAD_CONDITIONAL: *v = c->grad_conditional; return CEL_OK;
     case CEL_OPT_COMP_CACHE: *v = c->comp_cache; return CEL_OK;
+    case CEL_OPT_SAMPLER_MASK: *v = c->sampler_mask; return CEL_OK;
     case CEL_OPT_PROFILE: *v = (double)c->profile; return CEL_OK;
     case CEL_OPT_TILE_ORDER: *v = (double)c->tile_order; return CEL_OK;
     case CEL_OPT_TILE_ROWS: *v = c->tile_rows; return CEL_OK;
@@ -850,6 +857,32 @@ static int refuse_masked(const cel_images *im, const char *who) {
 static inline bool honours_mask(const cel_images *im) { return im->any_masked && im->ctx->honour_mask != 0; }
 static int refuse_masked_unless_honoured(const cel_images *im, const char *who) {
     return im->ctx->honour_mask ? CEL_OK : refuse_masked(im, who);
+}
+// ... and the device samplers of the EXACT conditional and the exact resident gradient once CEL_OPT_SAMPLER_MASK says so as well:
+// samplers_honour_mask: this call charges the OBSERVED mass (k_stamp_mass_masked) and its derivative (k_mass_grad_masked), one for
+// one in place of the plain kernels.  The reference's conditional charges the sum of the PSF weights, which is wrong beside a mask:
+// a call that does not run the exact conditional keeps being refused.
+static inline bool samplers_honour_mask(const cel_images *im) { return honours_mask(im) && im->ctx->sampler_mask != 0; }
+static int refuse_masked_sampler(const cel_images *im, const char *who, bool exact_call) {
+    return (exact_call && im->ctx->honour_mask && im->ctx->sampler_mask) ? CEL_OK : refuse_masked(im, who);
+}
+// the exact conditional's mass launch for the P slots of a proposal set (the records WITH boxes are on the device): launch_stamp_mass,
+// or its observed twin on the same blocks, job list and owners -- one launch either way
+static void launch_proposal_mass(cel_ctx *c, const cel_images *im, int64_t P, const int *owner, double *out, int64_t blocks, const int *jobs = nullptr) {
+    if (samplers_honour_mask(im))
+        hipLaunchKernelGGL(k_stamp_mass_masked, dim3((unsigned)blocks), dim3(64), 0, c->stream, im->d_bands, im->B, im->H, im->W, P,
+                           im->d_recs, (const double *)im->d_nelec, c->tail_T, out, jobs, owner);
+    else
+        launch_stamp_mass(c, im, P, owner, out, blocks, jobs);
+}
+// ... and the launch of that mass's derivative sums (k_mass_grad.h), P * B * PGRAD_PARTS blocks
+static void launch_mass_grad(cel_ctx *c, const cel_images *im, int64_t P, const int *owner, double *sums) {
+    const dim3 grid((unsigned)(P * im->B * PGRAD_PARTS));
+    if (samplers_honour_mask(im))
+        hipLaunchKernelGGL(k_mass_grad_masked, grid, dim3(64), 0, c->stream, im->d_bands, im->B, P, im->d_recs, owner,
+                           (const double *)im->d_nelec, im->H, im->W, sums);
+    else
+        hipLaunchKernelGGL(k_mass_grad, grid, dim3(64), 0, c->stream, im->d_bands, im->B, P, im->d_recs, owner, sums);
 }
 
 int cel_images_set_epsilon(cel_images *im, int band, double eps) {
@@ -1732,9 +1765,9 @@ static int pll_check(cel_images *im, cel_sources *src, const int32_t *owner, int
     if (resident && mode > 1) return fail(CEL_ERR_INVALID, "the resident form scores mode 0 or 1");
     const int nplanes = (mode == 4) ? 2 : 1;               // mode 4: data plane, then background plane
     // the exact conditional's gradient: the resident mode 8 of cel_patch_loglik_multi alone reads the key; it has the exact slice
-    // engine's preconditions (an unmasked set; the row window is the gradient form's refusal below; the split's just below)
+    // engine's preconditions (an unmasked set, or CEL_OPT_SAMPLER_MASK; the row window is the gradient form's refusal below; the split's just below)
     k.exact = grad && mode == 0 && resident && k.owned && im->ctx->grad_conditional == 1;
-    if (k.exact) { int rm = refuse_masked(im, "cel_patch_loglik_multi (resident gradient under CEL_OPT_GRAD_CONDITIONAL = 1)"); if (rm) return rm; }
+    if (k.exact) { int rm = refuse_masked_sampler(im, "cel_patch_loglik_multi (resident gradient under CEL_OPT_GRAD_CONDITIONAL = 1)", true); if (rm) return rm; }
     // (a masked set is refused as such before the missing split is named: cel_images_set_nelec drops the split it masks)
     if (mode == 1) { int rm = refuse_masked(im, "cel_patch_loglik (isolated form)"); if (rm) return rm; }
     if (resident && !im->split.resident_of(NB))
@@ -1916,11 +1949,12 @@ static int pll_gradient(cel_images *im, cel_sources *src, const PllCall &k, cons
     if (k.exact) {
         // the exact conditional (k_mass_grad.h): the masses and the term per proposal as the exact slice engine forms them, the
         // mass gradient's sums, the same chain rule on them (mode 2: nothing but the sums), and the exact rows from the two
-        launch_stamp_mass(c, im, P, k.d_owner, k.d_mass, P * B);
+        // (on a masked set under CEL_OPT_SAMPLER_MASK: the observed mass and its derivative, launch for launch)
+        launch_proposal_mass(c, im, P, k.d_owner, k.d_mass, P * B);
         hipLaunchKernelGGL(k_sg_exact_terms, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, c->stream, P, B, (const int *)k.d_owner,
                            (const BandDev *)im->d_bands, (const double *)src->d_counts, (const double *)k.d_mass,
                            (const int64_t *)im->d_soff, k.d_exact);
-        hipLaunchKernelGGL(k_mass_grad, grid, dim3(64), 0, c->stream, im->d_bands, B, P, im->d_recs, (const int *)k.d_owner, k.d_msums);
+        launch_mass_grad(c, im, P, k.d_owner, k.d_msums);
         hipLaunchKernelGGL(k_patch_grad_chain, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, c->stream, im->d_bands, B, P, im->d_recs,
                            (const int *)k.d_owner, (const int4 *)k.d_box, (const int *)src->d_type, (const double *)src->d_shape,
                            (const double *)src->d_counts, (const double *)k.d_msums, 2, k.d_mg);
@@ -2031,7 +2065,7 @@ int cel_stamp_mass_begin(cel_images *im, cel_sources *src) {
         HIP_TRY(hipMemcpyAsync(&c->mail->mass_todo, d_ntodo, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     } else if (observed) {
         hipLaunchKernelGGL(k_stamp_mass_masked, dim3((unsigned)(S * B)), dim3(64), 0, c->stream, im->d_bands, B, im->H, im->W, S,
-                           im->d_recs, (const double *)im->d_nelec, c->tail_T, d_out, (const int *)nullptr);
+                           im->d_recs, (const double *)im->d_nelec, c->tail_T, d_out, (const int *)nullptr, (const int *)nullptr);
     } else {
         launch_stamp_mass(c, im, S, nullptr, d_out, S * B);
     }
@@ -2196,11 +2230,12 @@ static int launch_resident_ll(cel_ctx *c, cel_images *im, int64_t P, const int *
 }
 
 // The exact conditional's pair (k_slice_gen.h) for the P slots of `prop`: the mass kernel proper, cel_stamp_mass_begin's plain
-// branch, on the running chains' jobs (a slot that is not scored retires by its owner; a launch of P B blocks that find
+// branch (its observed branch on a masked set under CEL_OPT_SAMPLER_MASK), on the running chains' jobs
+// (a slot that is not scored retires by its owner; a launch of P B blocks that find
 // nothing to do costs 0.15 ms, see there), then the term per slot
 static void launch_exact_terms(cel_ctx *c, cel_images *im, const cel_sources *prop, int64_t P, const int *d_owner, int64_t n_mass,
                                const int *d_list_mass, double *d_mass, double *d_exact) {
-    if (n_mass > 0) launch_stamp_mass(c, im, P, d_owner, d_mass, n_mass, d_list_mass);
+    if (n_mass > 0) launch_proposal_mass(c, im, P, d_owner, d_mass, n_mass, d_list_mass);
     hipLaunchKernelGGL(k_sg_exact_terms, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, c->stream, P, im->B, d_owner, (const BandDev *)im->d_bands,
                        (const double *)prop->d_counts, (const double *)d_mass, (const int64_t *)im->d_soff, d_exact);
 }
@@ -2718,9 +2753,8 @@ static int slice_hmc(cel_images *im, cel_sources *src, const int32_t *chain_ids,
                            (const int4 *)im->d_sbox, (const int *)prop->d_type, (const double *)prop->d_shape,
                            (const double *)prop->d_counts, (const double *)d_sums, 0, d_grad);
         if (exact) {                 // the mass, its gradient's sums, the chain rule on them, the exact rows
-            launch_stamp_mass(c, im, S, d_owner, d_mass, S * B);
-            hipLaunchKernelGGL(k_mass_grad, dim3((unsigned)(S * B * PGRAD_PARTS)), dim3(64), 0, st, im->d_bands, B, S, im->d_recs,
-                               (const int *)d_owner, d_msums);
+            launch_proposal_mass(c, im, S, d_owner, d_mass, S * B);
+            launch_mass_grad(c, im, S, d_owner, d_msums);
             hipLaunchKernelGGL(k_patch_grad_chain, dim3(g256), dim3(256), 0, st, im->d_bands, B, S, im->d_recs, (const int *)d_owner,
                                (const int4 *)im->d_sbox, (const int *)prop->d_type, (const double *)prop->d_shape,
                                (const double *)prop->d_counts, (const double *)d_msums, 2, d_mg);
@@ -2783,7 +2817,9 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
                      int step_out, int max_steps_out, double sigma, double phi_max, uint64_t seed, int max_rounds,
                      double *x_out, double *llh_out, int64_t *stats) {
     if (!im || !src) return fail(CEL_ERR_INVALID, "cel_slice_sample: null argument");
-    { int rm = refuse_masked(im, "cel_slice_sample"); if (rm) return rm; }
+    // (a masked set: refused, unless CEL_OPT_SAMPLER_MASK and CEL_OPT_HONOUR_MASK hold and this call runs the exact conditional)
+    { int rm = refuse_masked_sampler(im, "cel_slice_sample", param == 3 ? im->ctx->grad_conditional == 1 : im->ctx->slice_conditional == 1);
+      if (rm) return rm; }
     // CEL_OPT_SLICE_CONDITIONAL = 1: the exact conditional (k_slice_gen.h) -- the proposal's stamp mass on its own box and the
     // cover test per round
     const bool exact = im->ctx->slice_conditional == 1;

@@ -13,6 +13,8 @@
 // CEL_OPT_TAIL_LOG_SOURCE nor CEL_OPT_KERNEL is read, so the bits depend on the inputs alone (fixed order, wave_sum, no atomics).
 // A proposal without a stamp (record type < 0: own box empty, overlap-test miss) and a retired slot (owner < 0) write zeros:
 // their mass is 0 whatever q is.  The kernel reads the records and the band table only -- no pixel data, no box table.
+// k_mass_grad_masked is the same sum over the OBSERVED pixels of the box (it reads the counts to find the NaNs): the derivative of
+// the mass k_stamp_mass_masked forms, for the samplers on a masked image set (CEL_OPT_SAMPLER_MASK).
 //
 // k_mass_grad_apply: one thread per proposal, the exact row from the reference's row:
 //     slots 1..6   += -(sum_b counts_b d mass_b / d q_i)      (the chain's band-order sum over the bands that have a patch)
@@ -21,10 +23,12 @@
 #pragma once
 #include "k_patch_grad.h"
 
-__global__ void __launch_bounds__(64)
-k_mass_grad(const BandDev *__restrict__ bands, int B, int64_t P, const SrcRec *__restrict__ recs /* [B][P], WITH boxes */,
-            const int *__restrict__ owner /* P, or nullptr */, double *__restrict__ sums /* P*B*PGRAD_PARTS*GRAD_NS */) {
-    __shared__ double tab[GRAD_TAB];
+// the two kernels' body.  MASKED: the band's counts are read at the pixel and a pixel whose count is NaN is skipped BEFORE any
+// arithmetic (no r = 0 multiply), so a box without a masked pixel leaves the unmasked kernel's bits and a box masked everywhere
+// exact zeros
+template <bool MASKED>
+__device__ __forceinline__ void mass_grad_sums(const BandDev *bands, int B, int64_t P, const SrcRec *recs, const int *owner,
+                                               const double *nelec, int H, int W, double *sums, double *tab) {
     const int lane = threadIdx.x;
     const int part = (int)(blockIdx.x % (unsigned)PGRAD_PARTS);
     const int64_t job = (int64_t)(blockIdx.x / (unsigned)PGRAD_PARTS);
@@ -50,11 +54,35 @@ k_mass_grad(const BandDev *__restrict__ bands, int B, int64_t P, const SrcRec *_
     __syncthreads();
     double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     const int n = nx * (rb - ra);
+    // (MASKED: the box lies inside the frame -- 0 <= y0, y1 <= H, 0 <= x0, x1 <= W: k_prep cuts it -- so every address is a pixel's)
+    const double *zn = MASKED ? nelec + (int64_t)b * H * W + (int64_t)(y0 + ra) * W + x0 : nullptr;
     for (int i = lane; i < n; i += 64) {
         const int yy = i / nx, xx = i - yy * nx;
+        if (MASKED) {
+            const double z = zn[(int64_t)yy * W + xx];
+            if (z != z) continue;                                                                      // NaN: not observed
+        }
         grad_pixel<false>(tab, nullptr, K, gal, (double)(x0 + xx), (double)(y0 + ra + yy), acc);      // r = 1 at every pixel
     }
     grad_store_sums(acc, lane, out);
+}
+
+__global__ void __launch_bounds__(64)
+k_mass_grad(const BandDev *__restrict__ bands, int B, int64_t P, const SrcRec *__restrict__ recs /* [B][P], WITH boxes */,
+            const int *__restrict__ owner /* P, or nullptr */, double *__restrict__ sums /* P*B*PGRAD_PARTS*GRAD_NS */) {
+    __shared__ double tab[GRAD_TAB];
+    mass_grad_sums<false>(bands, B, P, recs, owner, nullptr, 0, 0, sums, tab);
+}
+
+// the derivative of the OBSERVED mass (CEL_OPT_SAMPLER_MASK on a masked image set): k_mass_grad's table, dealing of rows, pixel
+// order and sums, over the pixels of the box whose count is not NaN.  No drop threshold, no CEL_OPT_KERNEL: the bits depend on the
+// inputs alone.  nelec: [B][H][W], the whole frame (a row window is refused before the launch)
+__global__ void __launch_bounds__(64)
+k_mass_grad_masked(const BandDev *__restrict__ bands, int B, int64_t P, const SrcRec *__restrict__ recs /* [B][P], WITH boxes */,
+                   const int *__restrict__ owner /* P, or nullptr */, const double *__restrict__ nelec, int H, int W,
+                   double *__restrict__ sums /* P*B*PGRAD_PARTS*GRAD_NS */) {
+    __shared__ double tab[GRAD_TAB];
+    mass_grad_sums<true>(bands, B, P, recs, owner, nelec, H, W, sums, tab);
 }
 
 __global__ void __launch_bounds__(256)

@@ -394,11 +394,12 @@ k_patch_ll_hw(const BandDev *__restrict__ bands, int B, int64_t P, const SrcRec 
 // not NaN; then the wave's sum.  The order is fixed: the same bits on every run.  One wave per job; job_order: a list of
 // (source, band) jobs s * B + b (as MODE 3's leftovers), or nullptr = every job in index order.  The records are those of whichever
 // catalogue was prepared last: a batch of proposals is such a catalogue.  A box masked everywhere gives exactly 0, a source
-// without a record (type < 0) likewise.  LDS: MODE 2's (the 16 KB tile + the component table: eight blocks per CU).
+// without a record (type < 0) likewise, and so does a slot that its `owner` retires (the device samplers' finished or uncovered
+// chains, CEL_OPT_SAMPLER_MASK: as MODE 3 retires them).  LDS: MODE 2's (the 16 KB tile + the component table: eight blocks per CU).
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_stamp_mass_masked(const BandDev *__restrict__ bands, int B, int H, int W, int64_t S, const SrcRec *__restrict__ recs,
                     const double *__restrict__ nelec, double Tdrop, double *__restrict__ out /* S*B */,
-                    const int *__restrict__ job_order) {
+                    const int *__restrict__ job_order, const int *__restrict__ owner /* S, or nullptr: a slot with owner < 0 is retired */) {
     __shared__ double acc[HW_TH * HW_TW];
     __shared__ CompTab T;
     __shared__ double et[64];
@@ -407,6 +408,10 @@ k_stamp_mass_masked(const BandDev *__restrict__ bands, int B, int H, int W, int6
     const int64_t job = job_order ? (int64_t)job_order[blockIdx.x] : (int64_t)blockIdx.x;
     const int b = (int)(job % B);
     const int64_t s = job / B;
+    if (owner && owner[s] < 0) {                                     // a retired proposal slot of a device sampler: its record is not read
+        if (lane == 0) out[job] = 0.0;
+        return;
+    }
     RecU rec = rec_unpack(rec_fetch(recs + (int64_t)b * S, (int)s, lane));
     if (rec.type < 0 || rec.x1 <= rec.x0 || rec.y1 <= rec.y0) {      // no stamp
         if (lane == 0) out[job] = 0.0;

@@ -234,6 +234,30 @@ class ImageSet(object):
             raise L.MaskedImagesError("%s: the image set holds %d masked pixels (NaN counts) and this call does not honour a mask"
                                       % (who, n))
 
+    def _sampler_mask(self, who, mask, conditional):
+        """mask="honour" on a device sampler or the exact resident gradient: CEL_OPT_HONOUR_MASK and CEL_OPT_SAMPLER_MASK set around
+        the call and the caller's values restored behind it, also when the call fails.  Only the exact conditional charges the
+        observed mass: every other combination on a masked set is refused here, before any device call.  mask="refuse": nothing is
+        set, the library refuses a masked set as it always has."""
+        import contextlib
+        if mask not in ("refuse", "honour"):
+            raise ValueError("mask must be 'refuse' or 'honour'")
+        if mask == "honour" and conditional != "exact":
+            self._refuse_masked("%s(mask='honour', conditional=%r)" % (who, conditional))
+
+        @contextlib.contextmanager
+        def cm():
+            keys = (L.CEL_OPT_HONOUR_MASK, L.CEL_OPT_SAMPLER_MASK) if mask == "honour" else ()
+            was = [(k, self.ctx.get_option(k)) for k in keys]
+            try:
+                for k in keys:
+                    self.ctx.set_option(k, 1)
+                yield
+            finally:
+                for k, v in was:
+                    self.ctx.set_option(k, v)
+        return cm()
+
     def npix_observed(self):
         """unmasked pixels per band of a whole-frame set, H W - masked -> float64[B]: what the sky step's Gamma conditional
         counts (GibbsField(npix_observed=))"""
@@ -417,15 +441,18 @@ class ImageSet(object):
         return radec, llh, dict(rounds=int(stats[0]), evals=int(stats[1]), algorithmic_bytes=int(stats[2]), launches=int(stats[3]))
 
     def slice_sample(self, sources, param, sigma, seed, dirs=None, step_out=True, max_steps_out=1000, phi_max=180.,
-                     chain_ids=None, max_rounds=20000, conditional="reference"):
+                     chain_ids=None, max_rounds=20000, conditional="reference", mask="refuse"):
         """slicesample with random directions / stepping out by doubling for every source's location (param 0) or every
         galaxy's shape (param 1) on the device (cel_slice_sample).  dirs (S, numdir, D) unit directions or None =
         component-wise.  The sampled parameter is updated in place on the device.
         conditional="exact": the exact conditional of ModelGibbs(conditional="exact") -- the proposal's stamp mass on its own
         box, -inf where its box does not cover the source's photons (CEL_OPT_SLICE_CONDITIONAL, set around the call).
+        mask="honour" (with conditional="exact"): a masked image set is accepted and the proposals are charged their OBSERVED mass
+        (CEL_OPT_HONOUR_MASK and CEL_OPT_SAMPLER_MASK, set around the call); type_move and hmc_step likewise.
         -> (x[S,D], llh[S], dict(rounds, evals))"""
         if conditional not in ("reference", "exact"):
             raise ValueError("conditional must be 'reference' or 'exact'")
+        honour = self._sampler_mask("slice_sample", mask, conditional)
         S = sources.S
         D = 4 if param else 2
         x, llh = np.zeros((S, D)), np.zeros(S)
@@ -444,10 +471,11 @@ class ImageSet(object):
         was = self.ctx.get_option(L.CEL_OPT_SLICE_CONDITIONAL)
         try:
             self.ctx.set_option(L.CEL_OPT_SLICE_CONDITIONAL, 1 if conditional == "exact" else 0)
-            L.check(L.lib().cel_slice_sample(self._h, sources._h, int(param), None if ids is None else ids.ctypes.data_as(L.c_int32_p),
-                                             None if dirs is None else L.dptr(dirs), int(numdir), 1 if step_out else 0,
-                                             int(max_steps_out), float(sigma), float(phi_max), C.c_uint64(int(seed) & (2 ** 64 - 1)),
-                                             int(max_rounds), L.dptr(x), L.dptr(llh), stats.ctypes.data_as(L.c_int64_p)))
+            with honour:
+                L.check(L.lib().cel_slice_sample(self._h, sources._h, int(param), None if ids is None else ids.ctypes.data_as(L.c_int32_p),
+                                                 None if dirs is None else L.dptr(dirs), int(numdir), 1 if step_out else 0,
+                                                 int(max_steps_out), float(sigma), float(phi_max), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                                 int(max_rounds), L.dptr(x), L.dptr(llh), stats.ctypes.data_as(L.c_int64_p)))
         except ValueError as e:
             if "Slice sampler" in str(e):
                 raise Exception(str(e))
@@ -456,7 +484,7 @@ class ImageSet(object):
             self.ctx.set_option(L.CEL_OPT_SLICE_CONDITIONAL, was)
         return x, llh, dict(rounds=int(stats[0]), evals=int(stats[1]), launches=int(stats[3]))
 
-    def type_move(self, sources, shapes, h, seed, chain_ids=None, conditional="reference"):
+    def type_move(self, sources, shapes, h, seed, chain_ids=None, conditional="reference", mask="refuse"):
         """Source.resample_type (sources.py:247-306) for every source at once, on the device (cel_slice_sample, param 2): one
         Metropolis-Hastings star <-> galaxy proposal per chain against the resident split.  shapes (S, 4): the galaxy shape
         proposed for a chain that is a star now; h (S,): the caller's term of the log acceptance ratio (prior odds, proposal
@@ -464,6 +492,7 @@ class ImageSet(object):
         -> (typ[S] int32, shape[S,4], log_alpha[S], dict(evals, accepted, launches))"""
         if conditional not in ("reference", "exact"):
             raise ValueError("conditional must be 'reference' or 'exact'")
+        honour = self._sampler_mask("type_move", mask, conditional)
         S = sources.S
         if shapes is None or h is None:
             raise ValueError("type_move needs the proposed shapes (S, 4) and h (S,)")
@@ -481,9 +510,10 @@ class ImageSet(object):
         was = self.ctx.get_option(L.CEL_OPT_SLICE_CONDITIONAL)
         try:
             self.ctx.set_option(L.CEL_OPT_SLICE_CONDITIONAL, 1 if conditional == "exact" else 0)
-            L.check(L.lib().cel_slice_sample(self._h, sources._h, 2, None if ids is None else ids.ctypes.data_as(L.c_int32_p),
-                                             L.dptr(dirs), 1, 0, 0, 1.0, 0.0, C.c_uint64(int(seed) & (2 ** 64 - 1)), 1,
-                                             L.dptr(x), L.dptr(la), stats.ctypes.data_as(L.c_int64_p)))
+            with honour:
+                L.check(L.lib().cel_slice_sample(self._h, sources._h, 2, None if ids is None else ids.ctypes.data_as(L.c_int32_p),
+                                                 L.dptr(dirs), 1, 0, 0, 1.0, 0.0, C.c_uint64(int(seed) & (2 ** 64 - 1)), 1,
+                                                 L.dptr(x), L.dptr(la), stats.ctypes.data_as(L.c_int64_p)))
         finally:
             self.ctx.set_option(L.CEL_OPT_SLICE_CONDITIONAL, was)
         return (x[:, 0].astype(np.int32), np.ascontiguousarray(x[:, 1:]), la,
@@ -506,7 +536,7 @@ class ImageSet(object):
                 self.ctx.set_option(L.CEL_OPT_GRAD_CONDITIONAL, was)
         return cm()
 
-    def hmc_step(self, sources, p0, imass, eps, steps, seed, phi_max=180., chain_ids=None, conditional="reference"):
+    def hmc_step(self, sources, p0, imass, eps, steps, seed, phi_max=180., chain_ids=None, conditional="reference", mask="refuse"):
         """One HMC update of every source's location and shape at once, on the device (cel_slice_sample, param 3):
         q = (ra, dec, theta, sigma, phi, rho), a star in (ra, dec) only, counts fixed, `steps` leapfrog steps of size eps against
         the resident split under the reference's conditional.  p0 (S, 6): the momentum, refreshed by the caller; imass (S, 6):
@@ -517,6 +547,9 @@ class ImageSet(object):
         whose box does not cover the source's photons is dead, a chain whose current row fails that test is left alone.
         -> (q[S,6], p[S,6], log_alpha[S], dict(steps, evals, accepted, launches)): p is the momentum to carry on with (the
         trajectory's on accept, -p0 on reject); log_alpha is NaN for a chain left alone"""
+        if conditional not in ("reference", "exact"):
+            raise ValueError("conditional must be 'reference' or 'exact'")
+        honour = self._sampler_mask("hmc_step", mask, conditional)
         S = sources.S
         if p0 is None or imass is None:
             raise ValueError("hmc_step needs the momentum p0 (S, 6) and the inverse mass imass (S, 6)")
@@ -533,7 +566,7 @@ class ImageSet(object):
         stats = np.zeros(4, dtype=np.int64)
         # (CEL_OPT_SLICE_CONDITIONAL is left as the context has it: under the exact conditional the library refuses the step unless
         # CEL_OPT_GRAD_CONDITIONAL asks for the exact one)
-        with self._grad_conditional(conditional):
+        with self._grad_conditional(conditional), honour:
             L.check(L.lib().cel_slice_sample(self._h, sources._h, 3, None if ids is None else ids.ctypes.data_as(L.c_int32_p),
                                              L.dptr(dirs), 12, 0, 0, float(eps), float(phi_max), C.c_uint64(int(seed) & (2 ** 64 - 1)),
                                              int(steps), L.dptr(x), L.dptr(la), stats.ctypes.data_as(L.c_int64_p)))
@@ -760,15 +793,20 @@ class ImageSet(object):
         boxes = np.ascontiguousarray(boxes, dtype=np.int32).reshape(1, self.B, 4)
         return self.patch_loglik_multi_grad(sources, np.zeros(sources.S, dtype=np.int32), boxes, [patches], mode=mode)
 
-    def patch_loglik_resident_grad(self, proposals, owner, isolated=False, conditional="reference"):
+    def patch_loglik_resident_grad(self, proposals, owner, isolated=False, conditional="reference", mask="refuse"):
         """patch_loglik_resident and its analytic gradient: against the resident sample patches (isolated=True: against the
         observed image on the same boxes).  -> (ll[P], g_radec[P,2], g_counts[P,B], g_shape[P,4])
         Where the gradient is summed is the context's choice, not an argument: under CEL_OPT_PHOTON_LISTS = 4 or 5 (and not
         isolated) at the split's photon lists, otherwise over the patches; the two agree to rounding and ll is the same bits.
         conditional="exact" (not isolated): the exact conditional's value and gradient (CEL_OPT_GRAD_CONDITIONAL, set around the
-        call): ll is -inf and the gradient 0 for a proposal whose box does not cover its source's photons."""
+        call): ll is -inf and the gradient 0 for a proposal whose box does not cover its source's photons.
+        mask="honour" (with conditional="exact"): on a masked image set the observed mass and its derivative (CEL_OPT_HONOUR_MASK
+        and CEL_OPT_SAMPLER_MASK, set around the call)."""
         if conditional == "exact" and isolated:
             raise ValueError("conditional='exact' is the conditional form's (isolated=False)")
+        if conditional not in ("reference", "exact"):
+            raise ValueError("conditional must be 'reference' or 'exact'")
+        honour = self._sampler_mask("patch_loglik_resident_grad", mask, conditional)
         if isolated:
             self._refuse_masked("patch_loglik_resident(isolated=True)")
         owner = np.ascontiguousarray(owner, dtype=np.int32)
@@ -777,7 +815,7 @@ class ImageSet(object):
         S, tot = C.c_int64(0), C.c_int64(0)
         L.check(L.lib().cel_samples_info(self._h, C.byref(S), C.byref(tot)))
         out = np.zeros(proposals.S * (7 + self.B))
-        with self._grad_conditional(conditional):
+        with self._grad_conditional(conditional), honour:
             L.check(L.lib().cel_patch_loglik_multi(self._h, proposals._h, owner.ctypes.data_as(L.c_int32_p), S.value, None, None, None,
                                                    L.CEL_DEVICE, L.CEL_PLL_GRAD + (1 if isolated else 0), L.dptr(out)))
         return self._split_grad(out, proposals.S)

@@ -115,7 +115,25 @@ enum {
                                  cel_flux_conditionals runs on those sums and masses (a source masked in every band draws from its
                                  prior).  On a set without a NaN the option changes nothing: the same kernels, launches and bits.
                                  cel_slice_locations, cel_slice_sample and the isolated forms of cel_patch_loglik[_multi] refuse a
-                                 masked set whatever this option says */
+                                 masked set whatever this option says (the device samplers of the exact conditional: CEL_OPT_SAMPLER_MASK) */
+    /* samplers on a masked set: */ CEL_OPT_SAMPLER_MASK = 21, /* 0 (default): every device sampler and the exact resident gradient refuse a MASKED
+                                 image set, as before.  1, together with CEL_OPT_HONOUR_MASK = 1: a masked set is accepted by exactly
+                                 these calls, each under the exact conditional alone --
+                                   cel_slice_sample, params 0, 1, 2 under CEL_OPT_SLICE_CONDITIONAL = 1: the per-round mass launch is the
+                                     OBSERVED-mass kernel (k_stamp_mass_masked: the unit stamp over the unmasked pixels of the proposal's
+                                     own box, bit for bit what cel_stamp_mass returns under CEL_OPT_HONOUR_MASK) on the same job list;
+                                     the cover test, the likelihood launches and the launch count in `stats` are untouched (the masked
+                                     split places no photon at a masked pixel);
+                                   cel_slice_sample, param 3 and cel_patch_loglik_multi's resident mode 8, both under the
+                                     exact gradient's key (CEL_OPT_GRAD_CONDITIONAL = 1): e and slots 7 + b come from the observed mass, slots 1-6 from its
+                                     derivative (k_mass_grad_masked: k_mass_grad's sum over the observed pixels of the box alone; a pixel
+                                     whose count is NaN is skipped before any arithmetic, so a box without a masked pixel gives
+                                     k_mass_grad's bits and a box masked everywhere exact zeros).
+                                 Still refused, in the words they always had: cel_slice_locations, the isolated forms, a row window
+                                 and the reference's conditional (it charges the sum of the PSF weights, which is wrong beside a mask).
+                                 On a set without a NaN the option changes nothing: the same kernels, launches and bits.  It only
+                                 stores; cel_images_set_nelec drops the split a new mask invalidates.  Any other value:
+                                 CEL_ERR_INVALID, the stored value unchanged */
     /* exact conditional: */ CEL_OPT_SLICE_CONDITIONAL = 18, /* what cel_slice_sample scores.  0 (default): the reference's conditional, as before: the same
                                  kernels, launches and bits.  1: the EXACT conditional of ModelGibbs(conditional="exact") (DESIGN Q20):
                                  a proposal of a chain with expected photons c_b scores  prior + (sum_b mode-0 likelihood + e),
@@ -127,7 +145,7 @@ enum {
                                  k_sg_exact_terms; no further host synchronisation.  It applies to cel_slice_sample ALONE:
                                  cel_slice_locations does not read it and keeps its code, launches and bits -- the location step under
                                  the exact conditional is cel_slice_sample(param 0, dirs = NULL, step_out = 0).  Under 1 a masked set is
-                                 refused as under 0, and so is an image set with a row window (cel_images_set_window: the cover test
+                                 refused as under 0 (unless CEL_OPT_SAMPLER_MASK admits it), and so is an image set with a row window (cel_images_set_window: the cover test
                                  is not window-relative).  Any other value: CEL_ERR_INVALID */
     /* exact gradient: */ CEL_OPT_GRAD_CONDITIONAL = 19, /* which conditional the RESIDENT GRADIENT differentiates.  0 (default): the reference's, as
                                  before: the same kernels, launches and bits, and every refusal of the exact conditional stands.  1: the
@@ -146,7 +164,7 @@ enum {
                                  slots 1 .. = 0; its jobs retire at their first instructions.  d mass_b / d q comes from k_mass_grad.h: the
                                  plain form -- every component at every pixel of the box, nothing dropped, neither CEL_OPT_TAIL_LOG_SOURCE
                                  nor CEL_OPT_KERNEL read, the same bits on every call -- followed by the gradient form's chain rule.
-                                 The call then has the exact slice engine's preconditions: a masked set, a row window and a missing
+                                 The call then has the exact slice engine's preconditions: a masked set (unless CEL_OPT_SAMPLER_MASK admits it), a row window and a missing
                                  resident split are refused before any launch, ll_out untouched.  Mode 9, mode 10, explicit patches
                                  and cel_patch_loglik do not read the key.
                                  (b) cel_slice_sample(param = 3): the HMC step's v and g are the exact ones above (see there);
