@@ -20,6 +20,9 @@ CEL_PLL_GRAD = 8
 #: k_patch_grad_nz.h (the resident gradient at the photon lists, CEL_OPT_PHOTON_LISTS = 4 / 5): the photons of a trip, and the
 #: longest list that one block takes whole (a longer one is dealt to four blocks, trip by trip)
 PGNZ_TRIP, PGNZ_DEAL_PHOTONS = 128, 512
+#: cel_slice_sample: param = CEL_SLICE_MOMENTS runs no sampler; stats receives the S * B * 6 int64 moments of the resident split
+#: (ImageSet.photon_moments; k_moments.h).  A patch of more than CEL_MOMENTS_SPLIT_PIXELS pixels is dealt to four blocks
+CEL_SLICE_MOMENTS, CEL_MOMENTS_SPLIT_PIXELS = 10, 4096
 CEL_OPT_KERNEL, CEL_OPT_TAIL_LOG, CEL_OPT_PROFILE, CEL_OPT_TILE_ORDER, CEL_OPT_TILE_ROWS = 1, 2, 3, 4, 5
 CEL_OPT_TILE_TIMING, CEL_OPT_TILE_LAYOUT, CEL_OPT_DEBUG, CEL_OPT_PHOTON_LISTS, CEL_OPT_STAR_TILES, CEL_OPT_SPLIT_REUSE = 6, 7, 8, 9, 10, 11
 CEL_OPT_TAIL_LOG_SOURCE, CEL_OPT_TILE_PARTS, CEL_OPT_INCREMENTAL, CEL_OPT_SPLIT_FULL_BOX, CEL_OPT_SLICE_FUSE = 12, 13, 14, 15, 16

@@ -115,6 +115,263 @@ def gamma_by_stream(a, seed, ids):
     return out
 
 
+# ---- the type move's data-driven proposal: a galaxy shape from the second moments of the source's photons -------------------
+def _profile_variances():
+    """(V_exp, V_dev): the amplitude-weighted variances of mixture_profiles' two profiles, in units of r_e^2"""
+    from . import mixture_profiles as mp
+    return float(np.sum(mp.exp_amp * mp.exp_var)), float(np.sum(mp.dev_amp * mp.dev_var))
+
+
+def psf_covariance(band):
+    """the covariance of a band's PSF mixture about its own mean, in pixels^2, from its (37,) record:
+    sum_k w_k (Sigma_k + mu_k mu_k^T) / sum_k w_k - mubar mubar^T"""
+    band = np.asarray(band, dtype=np.float64)
+    w, mu, cov = band[3:6], band[6:12].reshape(3, 2), band[12:24].reshape(3, 2, 2)
+    ws = w.sum()
+    mubar = (w[:, None] * mu).sum(axis=0) / ws
+    return (w[:, None, None] * (cov + mu[:, :, None] * mu[:, None, :])).sum(axis=0) / ws - np.outer(mubar, mubar)
+
+
+def _band_pixel2equa(band, p):
+    rho, phi, ups = band[24:26], band[26:28], band[28:32].reshape(2, 2)
+    iwc = (p - rho[None, :]) @ ups.T
+    return iwc[:, 0] / np.cos(phi[1] / 180. * np.pi) + phi[0], iwc[:, 1] + phi[1]
+
+
+def band_cd_at(band, u):
+    """cd_at_pixel (fits_image.py:196-216, the 10-px finite difference the renderer takes) of a (37,) band record at the pixel
+    positions of the sky positions u (S, 2) -> (S, 2, 2), degrees per pixel"""
+    band = np.asarray(band, dtype=np.float64)
+    u = np.asarray(u, dtype=np.float64).reshape(-1, 2)
+    rho, phi, ups_inv = band[24:26], band[26:28], band[32:36].reshape(2, 2)
+    iwc = np.stack([(u[:, 0] - phi[0]) * np.cos(phi[1] / 180. * np.pi), u[:, 1] - phi[1]], axis=1)
+    p = iwc @ ups_inv.T + rho[None, :]
+    ra0, dec0 = _band_pixel2equa(band, p)
+    rax, decx = _band_pixel2equa(band, p + np.array([10., 0.]))
+    ray, decy = _band_pixel2equa(band, p + np.array([0., 10.]))
+    cosd = np.cos(dec0 * (np.pi / 180.))
+    cd = np.empty((u.shape[0], 2, 2))
+    cd[:, 0, 0], cd[:, 0, 1] = (rax - ra0) / 10. * cosd, (ray - ra0) / 10. * cosd
+    cd[:, 1, 0], cd[:, 1, 1] = (decx - dec0) / 10., (decy - dec0) / 10.
+    return cd
+
+
+def moment_centre(N, C, psf_cov, cd, n_min=50):
+    """From the photons' second moments to the centre of a shape proposal, for S chains and n (field, band) images at once.
+        N        (S, n)        photons of the chain in the image
+        C        (S, n, 2, 2)  their central second moment in pixels^2, S2 / N - m m^T (ignored where N < 1)
+        psf_cov  (n, 2, 2)     the image's PSF covariance (psf_covariance)
+        cd       (S, n, 2, 2)  the image's cd_at_pixel at the source
+    D = C - psf_cov is carried to the sky, A_b = cd D cd^T (degrees^2), and pooled, A = sum N_b A_b / sum N_b.  A galaxy's stamp
+    has A = vbar(theta) G G^T with G G^T = r_e^2 R diag(1, rho^2) R^T (gen_galaxy_ra_dec_basis: R's first column is
+    (cos phi', -sin phi'), phi' = 90 - phi degrees), so the larger eigenvalue is vbar r_e^2, the ratio of the two rho^2 and the
+    major eigenvector gives phi modulo 180.
+    -> (usable (S,) bool, lam_max (S,) degrees^2, rho_hat (S,) UNCLIPPED, phi_hat (S,) in [0, 180) degrees); a chain is usable when
+    sum N >= n_min and A has two positive eigenvalues (the other outputs are 1, 0.5, 0 where it is not)."""
+    N = np.asarray(N, dtype=np.float64)
+    S = N.shape[0]
+    has = N >= 1.0
+    C, P, cd = np.asarray(C, dtype=np.float64), np.asarray(psf_cov, dtype=np.float64), np.asarray(cd, dtype=np.float64)
+    Nw = np.where(has, N, 0.0)
+    Ntot = Nw.sum(axis=1)
+    wgt = Nw / np.maximum(Ntot, 1.0)[:, None]                 # (a band without photons has weight 0: its C is never read as data)
+    d00, d01, d11 = C[..., 0, 0] - P[None, :, 0, 0], 0.5 * (C[..., 0, 1] + C[..., 1, 0]) - P[None, :, 0, 1], C[..., 1, 1] - P[None, :, 1, 1]
+    c00, c01, c10, c11 = cd[..., 0, 0], cd[..., 0, 1], cd[..., 1, 0], cd[..., 1, 1]
+    t00, t01, t10, t11 = c00 * d00 + c01 * d01, c00 * d01 + c01 * d11, c10 * d00 + c11 * d01, c10 * d01 + c11 * d11
+    with np.errstate(invalid="ignore"):                        # the 2 x 2 products cd D cd^T, written out (S x n of them per call)
+        a = np.where(has, wgt * (t00 * c00 + t01 * c01), 0.0).sum(axis=1)
+        b = np.where(has, wgt * (t00 * c10 + t01 * c11), 0.0).sum(axis=1)
+        c = np.where(has, wgt * (t10 * c10 + t11 * c11), 0.0).sum(axis=1)
+    half, diff = 0.5 * (a + c), 0.5 * (a - c)
+    root = np.hypot(diff, b)
+    lmax = half + root
+    det = a * c - b * b
+    with np.errstate(invalid="ignore", divide="ignore"):
+        lmin = np.where(lmax > 0, det / lmax, -1.0)          # (the product of the two, not half - root: no cancellation)
+    usable = (Ntot >= n_min) & (lmin > 0) & (lmax > 0) & np.isfinite(lmax) & np.isfinite(lmin)
+    # the major eigenvector: (b, lmax - a) or (lmax - c, b), whichever is longer (both vanish only for a round A: any phi serves)
+    e1x, e1y, e2x, e2y = b, lmax - a, lmax - c, b
+    first = (e1x * e1x + e1y * e1y) >= (e2x * e2x + e2y * e2y)
+    ex, ey = np.where(first, e1x, e2x), np.where(first, e1y, e2y)
+    round_ = (ex == 0) & (ey == 0)
+    ex = np.where(round_, 1.0, ex)
+    phi_p = np.degrees(np.arctan2(-ey, ex))                   # e = (cos phi', -sin phi')
+    phi = np.mod(90.0 - phi_p, 180.0)
+    phi = np.where(phi >= 180.0, 0.0, phi)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rho = np.sqrt(np.where(usable, lmin / lmax, 0.25))
+    return usable, np.where(usable, lmax, 1.0), rho, np.where(usable, phi, 0.0)
+
+
+class MomentProposal(object):
+    """The star <-> galaxy move's proposal that looks at the data (ModelGibbs(type_proposal="moments"); resample_types(proposal=)).
+
+    Given the photon split a source's photons are fixed while it changes type, so a density q(shape | photons of s) serves
+    both directions of the Metropolis-Hastings ratio.  The statistic is the second moment of the source's photons
+    (ImageSet.photon_moments, reduced on the device) with each band's PSF taken out, carried to the sky and pooled over bands
+    and fields (moment_centre): it fixes rho, phi modulo 180 and, for a given theta, sigma:
+        sigma_hat(theta) = 3600 sqrt(lam_max / vbar(theta)),   vbar = theta V_exp + (1 - theta) V_dev,
+        rho_hat = sqrt(lam_min / lam_max) clipped to [0.05, 0.95],   phi_hat = the major axis, every image phi_hat + 180 k inside
+        (0, phi_period) with equal weight.
+    For a usable chain (sum N >= n_min, two positive eigenvalues)
+        q(shape | m) = w p(shape) + (1 - w) q_loc(shape | m)
+    with p the normalised prior (sample_shape_prior's law) and q_loc the product of theta ~ U(0, 1),
+    log sigma ~ N(log sigma_hat(theta), s_sigma^2), logit rho ~ N(logit rho_hat, s_rho^2), phi = (phi_hat_k + U(-a_phi, a_phi)) mod
+    period; the Jacobians 1 / sigma and 1 / (rho (1 - rho)) are in the density.  Any other chain's proposal is the prior's.  The
+    share w of the prior keeps h finite on the whole support, as cel_slice_sample demands.
+    The defaults (w = 0.1, s_sigma = 0.5, s_rho = 1, a_phi = 30 degrees capped at half the period, n_min = 50) are first guesses:
+    nobody has tuned them.
+
+    draw(seed, ids) takes THIRTEEN numbers per chain from ChainStreams(seed, ids), usable or not, in this order: the uniforms
+    theta, rho, phi and the normal z and uniform u of sigma exactly as sample_shape_prior takes them (five), then the uniform that
+    chooses the prior (< w) or q_loc, then q_loc's: the uniform theta, the normals of log sigma and of logit rho, the uniform that
+    picks the image of phi_hat and the uniform of its offset.  (A normal is two numbers of the chain's normal stream.)
+
+    Host numpy, vectorised over the chains; the host and device engines of resample_types take the same (shapes, h)."""
+
+    def __init__(self, w=0.1, s_sigma=0.5, s_rho=1.0, a_phi=30.0, n_min=50):
+        if not (0.0 < w <= 1.0):
+            raise ValueError("MomentProposal: the prior's share w must be in (0, 1]: without it h is not finite on the whole support")
+        if not (s_sigma > 0 and s_rho > 0 and a_phi > 0):
+            raise ValueError("MomentProposal: the widths must be positive")
+        self.w, self.s_sigma, self.s_rho, self.a_phi, self.n_min = float(w), float(s_sigma), float(s_rho), float(a_phi), n_min
+        self.V_exp, self.V_dev = _profile_variances()
+        self.moments = None
+
+    # -- the state: one centre per chain -----------------------------------------------------------------------------------------
+    def set_centre(self, usable, lam_max, rho_hat, phi_hat, phi_period):
+        """what moment_centre returned, and the period of phi"""
+        self.period = float(phi_period)
+        self.usable = np.asarray(usable, dtype=bool)
+        self.lam_max = np.asarray(lam_max, dtype=np.float64)
+        self.rho_hat = np.clip(np.asarray(rho_hat, dtype=np.float64), 0.05, 0.95)
+        phi0 = np.mod(np.asarray(phi_hat, dtype=np.float64), 180.0)
+        if self.period >= 180.0:
+            # images phi0 + 180 k below the period: floor((period - phi0) / 180) of them beyond phi0, at least phi0 itself
+            self.n_img = np.maximum(np.ceil((self.period - phi0) / 180.0), 1.0)
+            self.phi0 = phi0
+        else:
+            self.n_img = np.ones_like(phi0)
+            self.phi0 = np.mod(phi0, self.period)
+        self.half = min(self.a_phi, 0.5 * self.period)
+        return self
+
+    def observe(self, model):
+        """take the moments of every field's current split (once per call) and set the centres"""
+        N, C, P, CD = [], [], [], []
+        self.moments = []
+        for f in model.fields:
+            mom = f.iset.photon_moments()
+            self.moments.append(mom)
+            m = mom.astype(np.float64)
+            n = np.maximum(m[..., 0], 1.0)
+            mx, my = m[..., 1] / n, m[..., 2] / n
+            c = np.empty(m.shape[:2] + (2, 2))
+            c[..., 0, 0] = m[..., 3] / n - mx * mx
+            c[..., 0, 1] = c[..., 1, 0] = m[..., 4] / n - mx * my
+            c[..., 1, 1] = m[..., 5] / n - my * my
+            N.append(m[..., 0])
+            C.append(c)
+            for b in range(f.iset.B):
+                band = f.iset.band(b)
+                P.append(psf_covariance(band))
+                CD.append(band_cd_at(band, model.u))
+        out = moment_centre(np.concatenate(N, axis=1), np.concatenate(C, axis=1), np.stack(P), np.stack(CD, axis=1), self.n_min)
+        return self.set_centre(*out, phi_period=model.phi_period)
+
+    # -- the density -------------------------------------------------------------------------------------------------------------
+    def sigma_hat(self, theta):
+        """sigma_hat(theta) per chain, arc seconds"""
+        return 3600.0 * np.sqrt(self.lam_max / (theta * self.V_exp + (1.0 - theta) * self.V_dev))
+
+    def log_prior(self, shapes):
+        """log of the NORMALISED prior (sample_shape_prior's law): theta, rho ~ U(0, 1), phi ~ U(0, period),
+        p(sigma) = 2 sigma^-4 exp(-1 / sigma^2) / Gamma(3/2); -inf outside the support"""
+        from math import lgamma, log
+        th, sg, ph, rh = (np.asarray(shapes, dtype=np.float64)[:, i] for i in range(4))
+        inside = (th > 0) & (th < 1) & (sg > 0) & (ph > 0) & (ph < self.period) & (rh > 0) & (rh < 1)
+        s = np.where(inside, sg, 1.0)
+        return np.where(inside, (log(2.0) - lgamma(1.5) - log(self.period)) - 4.0 * np.log(s) - 1.0 / (s * s), -np.inf)
+
+    def log_phi(self, ph):
+        """log density of q_loc's phi: n_img windows of half width `half` about the images of phi_hat, wrapped into the period"""
+        dens = np.zeros_like(ph)
+        for k in range(int(self.n_img.max())):
+            d = np.abs(ph - (self.phi0 + 180.0 * k))
+            d = np.minimum(d, self.period - d)                 # distance on the circle of length `period`
+            dens += np.where((k < self.n_img) & (d < self.half), 1.0, 0.0)
+        with np.errstate(divide="ignore"):
+            return np.log(dens / (self.n_img * 2.0 * self.half))
+
+    def log_loc(self, shapes):
+        """log q_loc(shape | m) per chain (meaningful for the usable ones); -inf outside the support"""
+        from math import log, pi
+        th, sg, ph, rh = (np.asarray(shapes, dtype=np.float64)[:, i] for i in range(4))
+        inside = (th > 0) & (th < 1) & (sg > 0) & (ph > 0) & (ph < self.period) & (rh > 0) & (rh < 1)
+        t, s, r = np.where(inside, th, 0.5), np.where(inside, sg, 1.0), np.where(inside, rh, 0.5)
+        zs = (np.log(s) - np.log(self.sigma_hat(t))) / self.s_sigma
+        zr = (np.log(r / (1.0 - r)) - np.log(self.rho_hat / (1.0 - self.rho_hat))) / self.s_rho
+        lq = (-0.5 * zs * zs - log(self.s_sigma) - 0.5 * log(2.0 * pi) - np.log(s)
+              - 0.5 * zr * zr - log(self.s_rho) - 0.5 * log(2.0 * pi) - np.log(r * (1.0 - r))
+              + self.log_phi(np.where(inside, ph, self.phi0)))
+        return np.where(inside, lq, -np.inf)
+
+    def logq(self, shapes):
+        """log q(shape | m) for one shape per chain, (S, 4) -> (S,)"""
+        from math import log
+        lp = self.log_prior(shapes)
+        if self.w >= 1.0:
+            return lp
+        with np.errstate(invalid="ignore"):
+            mix = np.logaddexp(log(self.w) + lp, log(1.0 - self.w) + self.log_loc(shapes))
+        return np.where(self.usable & (lp > -np.inf), mix, lp)
+
+    # -- the draw ----------------------------------------------------------------------------------------------------------------
+    def draw(self, seed, ids):
+        """one shape per chain of `ids` (indices of the chains whose centres are set) -> (len(ids), 4); the order of the thirteen
+        numbers a chain takes: the class's docstring"""
+        from .util.infer.slicesample import ChainStreams
+        ids = np.asarray(ids)
+        cs = ChainStreams(seed, ids)
+        every = np.arange(len(ids))
+        theta, rho = cs.uniform(every), cs.uniform(every)
+        phi = cs.uniform(every) * self.period
+        z, u = cs.normal(every), cs.uniform(every)
+        sigma = 1.0 / np.sqrt(z * z / 2.0 - np.log(u))
+        prior = np.stack([theta, sigma, phi, rho], axis=1)
+        pick = cs.uniform(every)
+        t2, zs, zr, ui, uo = cs.uniform(every), cs.normal(every), cs.normal(every), cs.uniform(every), cs.uniform(every)
+        lam, rh = self.lam_max[ids], self.rho_hat[ids]
+        s2 = 3600.0 * np.sqrt(lam / (t2 * self.V_exp + (1.0 - t2) * self.V_dev)) * np.exp(self.s_sigma * zs)
+        lr = np.log(rh / (1.0 - rh)) + self.s_rho * zr
+        r2 = 1.0 / (1.0 + np.exp(-lr))
+        k = np.minimum(np.floor(ui * self.n_img[ids]), self.n_img[ids] - 1.0)
+        p2 = np.mod(self.phi0[ids] + 180.0 * k + (2.0 * uo - 1.0) * self.half, self.period)
+        loc = np.stack([t2, s2, p2, r2], axis=1)
+        take_prior = (pick < self.w) | ~self.usable[ids]
+        return np.where(take_prior[:, None], prior, loc)
+
+    # -- the caller's term of the log acceptance ratio ---------------------------------------------------------------------------------
+    def h_of(self, shapes, to_galaxy, type_log_odds):
+        """h for the move between a star and the galaxy of shape `shapes[s]`: + (odds + log p - log q) towards the galaxy, the
+        same number with the other sign towards the star -- one expression, one sign"""
+        lp = self.log_prior(shapes)
+        with np.errstate(invalid="ignore"):
+            # (a galaxy whose row lies outside the prior's support has no density to compare: the plain odds, as the prior proposal)
+            t = type_log_odds + np.where(lp > -np.inf, lp - self.logq(shapes), 0.0)
+        return np.where(to_galaxy, t, -t)
+
+    def __call__(self, model):
+        self.observe(model)
+        ids = np.arange(model.S)
+        drawn = self.draw(model.step_seed("type", 1), ids)
+        to_gal = model.typ == 0
+        shapes = np.where(to_gal[:, None], drawn, model.shape)
+        h = self.h_of(shapes, to_gal, model.type_log_odds)
+        moves = (model.typ == 0) | (model.typ == 1)
+        return drawn, np.where(moves, h, 0.0)
+
+
 # ---- the whole Gibbs sweep, catalogue-wide and device-resident -------------------------------------
 class GibbsField(object):
     """One field's images on the device plus what the sweep needs to know about them."""
@@ -217,8 +474,15 @@ class ModelGibbs(object):
 
     def __init__(self, fields, typ, u, fluxes, shape, seed=0, flux_a_0=5., flux_b_0=.005, slice_args=None, engine="auto",
                  deal=None, shape_args=None, shape_logprior=None, phi_period=180., shape_mass="reference", conditional="reference",
-                 mask="refuse", type_log_odds=0.0, grad_route="dense", hmc_conditional=None, mask_engine="host"):
+                 mask="refuse", type_log_odds=0.0, grad_route="dense", hmc_conditional=None, mask_engine="host", type_proposal="prior"):
         self.fields = list(fields)
+        # type_proposal: what resample_types(proposal=None) offers a star.  "prior" (default): a galaxy shape from the shape prior.
+        # "moments": MomentProposal -- a shape from the second moments of the source's own photons in the current split
+        # (ImageSet.photon_moments), with the proposal densities of both directions in h.  Either engine takes the same (shapes, h).
+        if type_proposal not in ("prior", "moments"):
+            raise ValueError("type_proposal must be 'prior' or 'moments'")
+        self.type_proposal = type_proposal
+        self.moment_proposal = MomentProposal() if type_proposal == "moments" else None
         # mask_engine: which slice engine a masked sweep (mask="honour") may take.  "host" (default): the host engine, as ever --
         # engine="device" raises.  "device": the device samplers of the exact conditional charge the OBSERVED mass per round
         # (CEL_OPT_SAMPLER_MASK around their calls; ImageSet.slice_sample / type_move / hmc_step(mask="honour")), so engine="auto"
@@ -912,7 +1176,8 @@ class ModelGibbs(object):
         step_seed("type").
         proposal: None -- a star's shape is drawn from the normalised shape prior (sample_shape_prior, the streams of
         step_seed("type", 1): not the accept test's), so proposal and prior cancel and h = +type_log_odds for star -> galaxy,
-        -type_log_odds for the reverse; or a callable(model) -> (shapes[S, 4], h[S]) with h everything of the log acceptance
+        -type_log_odds for the reverse (under ModelGibbs(type_proposal="moments"): MomentProposal, the shape the source's own photons
+        imply, with both directions' proposal densities in h); or a callable(model) -> (shapes[S, 4], h[S]) with h everything of the log acceptance
         ratio that is not the likelihood (prior odds, proposal densities, Jacobian).  A custom shape prior needs one."""
         import time
         from .util.infer.slicesample import ChainStreams
@@ -922,6 +1187,8 @@ class ModelGibbs(object):
         on_device = self._type_engine_on_device()
         t0 = time.perf_counter()
         ids_all = np.arange(self.S)
+        if proposal is None and self.type_proposal == "moments":
+            proposal = self.moment_proposal
         if proposal is None:
             shapes = self.sample_shape_prior(self.step_seed("type", 1), ids_all)
             h = np.where(self.typ == 0, self.type_log_odds, -self.type_log_odds).astype(np.float64)

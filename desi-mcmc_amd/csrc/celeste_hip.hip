@@ -104,6 +104,7 @@ static int fail(int code, const char *fmt, ...) {
 #include "k_patch_grad_nz.h"
 #include "k_mass_grad.h"
 #include "k_split.h"
+#include "k_moments.h"
 #include "k_slice.h"
 
 // ------------------------------------------------------------------------------------------
@@ -128,7 +129,7 @@ enum ScratchSlot {
     SCR_PLL_BOXES,    // cel_patch_loglik_multi: the caller's boxes, their photon rectangles, the owners
     SCR_OFFSETS,      // cel_patch_loglik_multi, cel_photon_split: a caller's patch offsets
     SCR_VALUES,       // cel_patch_loglik_multi: the jobs' sums; cel_photon_split: the noise partials; cel_stamp_mass_begin: the masses (PENDING)
-    SCR_PATCH_DATA,   // cel_patch_loglik_multi, cel_photon_split: a caller's patch pixels, staged; cel_samples_fetch: sums the split did not form
+    SCR_PATCH_DATA,   // cel_patch_loglik_multi, cel_photon_split: a caller's patch pixels, staged; cel_samples_fetch: sums the split did not form; cel_slice_sample's moments (param 10): the S*B*6 sums (free between a split and a sampler call: the samplers and the resident likelihoods take none of it)
     SCR_TMP_A,        // cel_render_stamps: jobs; cel_estep_stats: xtilde; cel_loglik_grad: sums; cel_patch_loglik_multi (gradient form): the parts' sums; cel_mog_loglike: components; cel_galaxy_mixture_params: inputs
     SCR_TMP_B,        // cel_render_stamps: boxes; cel_estep_stats: masses; cel_loglik_grad: staged gradients; cel_patch_loglik_multi (gradient form): the 7 + B rows; cel_mog_loglike: points; cel_galaxy_mixture_params: outputs
     SCR_TMP_C,        // cel_render_stamps: offsets; cel_estep_stats: per-entry sums; cel_mog_loglike: outputs; cel_flux_conditionals, cel_gamma_streams: inputs + outputs
@@ -2813,9 +2814,12 @@ static int slice_hmc(cel_images *im, cel_sources *src, const int32_t *chain_ids,
 }
 
 // The general slice sampler (k_slice_gen.h): random directions, stepping out by doubling, D = 2 or 4.
+static int samples_moments(cel_images *im, const cel_sources *src, int64_t *mom);      // (below, with the split)
 int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t *chain_ids, const double *dirs, int numdir,
                      int step_out, int max_steps_out, double sigma, double phi_max, uint64_t seed, int max_rounds,
                      double *x_out, double *llh_out, int64_t *stats) {
+    // param CEL_SLICE_MOMENTS: no sampler -- the moments of the resident split into stats (any set that holds a split; src may be null)
+    if (im && param == CEL_SLICE_MOMENTS) return samples_moments(im, src, stats);
     if (!im || !src) return fail(CEL_ERR_INVALID, "cel_slice_sample: null argument");
     // (a masked set: refused, unless CEL_OPT_SAMPLER_MASK and CEL_OPT_HONOUR_MASK hold and this call runs the exact conditional)
     { int rm = refuse_masked_sampler(im, "cel_slice_sample", param == 3 ? im->ctx->grad_conditional == 1 : im->ctx->slice_conditional == 1);
@@ -2828,7 +2832,7 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
                                      "with a row window (cel_images_set_window): its cover test is not window-relative");
     if (src->B != im->B || src->ctx != im->ctx) return fail(CEL_ERR_INVALID, "sources do not match images");
     { int rs = need_resident_split(im, src, "cel_slice_sample"); if (rs) return rs; }
-    if (param < 0 || param > 3) return fail(CEL_ERR_INVALID, "cel_slice_sample: param must be 0 (location), 1 (shape), 2 (type) or 3 (HMC)");
+    if (param < 0 || param > 3) return fail(CEL_ERR_INVALID, "cel_slice_sample: param must be 0 (location), 1 (shape), 2 (type), 3 (HMC) or 10 (the split's moments)");
     if (!(sigma > 0.0) || max_rounds < 1 || max_steps_out < 0) return fail(CEL_ERR_INVALID, "cel_slice_sample: sigma and max_rounds must be positive");
     if (param == 2) return slice_type_move(im, src, chain_ids, dirs, numdir, seed, x_out, llh_out, stats);
     if (param == 3) return slice_hmc(im, src, chain_ids, dirs, numdir, sigma, phi_max, seed, max_rounds, x_out, llh_out, stats);
@@ -3257,6 +3261,33 @@ int cel_samples_photon_rects(cel_images *im, int32_t *rects) {
         rects[4 * i + 2] = held ? hb[i].x : 0; rects[4 * i + 3] = held ? hb[i].y : 0;
     }
     return CEL_OK;
+}
+
+// cel_slice_sample(param = CEL_SLICE_MOMENTS).  Reads the split (patches or photon lists, behind whatever the split left queued on
+// the stream) and writes the caller's array: no stamp of the set changes.  src may be null (the split's own S).
+static int samples_moments(cel_images *im, const cel_sources *src, int64_t *mom) {
+    if (!mom) return fail(CEL_ERR_INVALID, "cel_slice_sample: the moments (param 10) need stats[S * B * 6]");
+    if (src) {
+        if (src->B != im->B || src->ctx != im->ctx) return fail(CEL_ERR_INVALID, "sources do not match images");
+        int rs = need_resident_split(im, src, "cel_slice_sample"); if (rs) return rs;
+    } else if (im->split.samp_S <= 0) {     // (need_resident_split's words; no catalogue was named, so no count of `these`)
+        return fail(CEL_ERR_INVALID, "cel_slice_sample needs a resident photon split (have %lld sources' patches)", (long long)im->split.samp_S);
+    }
+    cel_ctx *c = im->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t n = im->split.samp_S * im->B;
+    if (n * MOM_PARTS > 0x7fffffffLL) return fail(CEL_ERR_INVALID, "cel_slice_sample: too many (source, band) jobs for one launch of the moments");
+    long long *d_mom = nullptr;
+    int rc = scratch_get(c, SCR_PATCH_DATA, sizeof(long long) * 6 * n, (void **)&d_mom);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(d_mom, 0, sizeof(long long) * 6 * n, c->stream));
+    const bool use_nz = im->split.nz_valid && c->variant != 0;      // the likelihoods' rule (patch_ll_resident, the samplers)
+    hipLaunchKernelGGL(k_moments, dim3((unsigned)(n * MOM_PARTS)), dim3(64), 0, c->stream, n, (const int4 *)im->d_sbox,
+                       (const int64_t *)im->d_soff, (const int *)im->d_samp, use_nz ? (const int *)im->d_nzmode : (const int *)nullptr,
+                       (const int64_t *)im->d_nzoff, (const NzEntry *)im->d_nzlist, d_mom);
+    HIP_TRY(hipGetLastError());
+    static_assert(sizeof(long long) == sizeof(int64_t), "the kernel's sums are the ABI's int64");
+    return copy_out(mom, d_mom, sizeof(int64_t) * 6 * n, CEL_HOST, c->stream);
 }
 
 int cel_debug_binomial(cel_ctx *c, int64_t n, double p, uint64_t seed, int64_t N, int64_t *out) {

@@ -609,6 +609,19 @@ class ImageSet(object):
         L.check(L.lib().cel_samples_photon_rects(self._h, rects.ctypes.data_as(L.c_int32_p)))
         return rects
 
+    def photon_moments(self):
+        """(S, B, 6) int64 = N, Sx, Sy, Sxx, Sxy, Syy of every (source, band) patch of the resident split: the sums of z, z dx,
+        z dy, z dx dx, z dx dy, z dy dy over the patch, z the source's photons at a pixel and (dx, dy) counted from the low corner
+        (x0, y0) of the patch's box as fetch_samples reports it; zeros without a patch.  Reduced on the device
+        (cel_slice_sample, param = CEL_SLICE_MOMENTS: no sampler runs, no new entry point), exact.  Refuses, like every call that
+        needs it, when the set holds no resident photon split."""
+        S, tot = C.c_int64(0), C.c_int64(0)
+        L.check(L.lib().cel_samples_info(self._h, C.byref(S), C.byref(tot)))
+        mom = np.zeros((S.value, self.B, 6), dtype=np.int64)
+        L.check(L.lib().cel_slice_sample(self._h, None, L.CEL_SLICE_MOMENTS, None, None, 0, 0, 0, 0.0, 0.0, C.c_uint64(0), 0,
+                                         None, None, mom.ctypes.data_as(L.c_int64_p)))
+        return mom
+
     def stamp_mass(self, sources):
         """sum of every source's unit stamp over its own box -> (S, B)  (sources.py:336-339).  On a masked set under
         CEL_OPT_HONOUR_MASK: over the UNMASKED pixels of the box (estep_stats' mass); this, stamp_mass_begin / _end alike"""

@@ -304,7 +304,7 @@ int cel_images_destroy(cel_images *img);
  * mask) is unchanged, and a set without a NaN takes exactly the code it took before there was a mask.
  * THE RESIDENT SPLIT.  New pixels drop the resident photon split, which was drawn from the old ones: after this call
  * cel_samples_info reports S = 0, cel_stamp_mass_ready answers 0, and cel_flux_conditionals, cel_slice_locations, cel_slice_sample,
- * the resident forms of cel_patch_loglik_multi, cel_samples_fetch and cel_samples_photon_rects fail with CEL_ERR_INVALID, naming
+ * the resident forms of cel_patch_loglik_multi, cel_samples_fetch, cel_samples_photon_rects and cel_slice_sample's moments (param 10) fail with CEL_ERR_INVALID, naming
  * the missing split, until the next resident cel_photon_split (on a masked set the masked refusal above comes first).  Pixels
  * written in place through cel_images_device_ptrs are the caller's business, as that call says. */
 int cel_images_set_nelec(cel_images *img, const double *nelec, int mem);
@@ -646,7 +646,33 @@ int cel_slice_locations(cel_images *img, cel_sources *src, const int32_t *chain_
  * and V = the value launches of the two scored slots (1 or 2):
  *     reference's conditional:  1 + J + 3 (L + 1) + L + 2 + V + 1
  *     exact conditional:        1 + J + 9 (L + 1) + L + 3 + V + 2 + 1
- * Refused as under 0, and a masked set, a row window and a missing split as params 0-2 refuse them. */
+ * Refused as under 0, and a masked set, a row window and a missing split as params 0-2 refuse them.
+ *
+ * param CEL_SLICE_MOMENTS (10 = 8 + 2, as mode 8 + m of cel_patch_loglik is the gradient of mode m): no sampler runs -- the
+ * STATISTIC a data-driven proposal of the type move (param 2) conditions on, the moments of every source's photons in the
+ * resident photon split, reduced on the device (k_moments.h; celeste_mcmc.MomentProposal).  It enters as a new value of an
+ * existing argument, as the type move and the HMC step did: no new symbol.  Per (source, band),
+ *   stats[(s*B+b)*6 ..] = N, Sx, Sy, Sxx, Sxy, Syy = sum over the patch's pixels of z, z dx, z dy, z dx dx, z dx dy, z dy dy,
+ * z the photons the split gave s at that pixel, dx = x - x0, dy = y - y0 from the low corner of the patch's box as
+ * cel_samples_fetch reports it.  All zeros without a patch.  int64, EXACT (integer sums, any order) while they fit.
+ *   stats    S*B*6 int64 (host), S from cel_samples_info -- NOT the four counters of the other params
+ *   src      the catalogue of the split, or NULL (the split's own S is taken); every other argument is ignored and may be 0 / NULL
+ * RANGE.  Every sum must stay below 2^63: sum over a patch of z d^2 < 2^63.  With int32 samples and boxes of at most 2^12 pixels
+ * a side one pixel's term is below 2^31 * 2^24 = 2^55, so 2^8 such pixels fit whatever they hold -- and a patch whose photons
+ * number below 2^39 fits whatever its pixels.  Not checked on the device.
+ * ROUTES.  Where the split's photon lists stand, a patch is summed at its list or over its dense pixels as the conditional
+ * likelihoods read it (CEL_OPT_PHOTON_LISTS, CEL_OPT_KERNEL); the integers are the same.  A patch of more than
+ * CEL_MOMENTS_SPLIT_PIXELS pixels is dealt to several blocks that add with 64-bit integer atomics: invisible in the result.
+ * STATE.  Reads the split and writes only `stats`: no cached state of the set changes, the catalogue is not touched, and a call
+ * between a split and a sampler, the flux step or a resident likelihood leaves their results bit for bit.
+ * Fails with CEL_ERR_INVALID, before any launch and with `stats` untouched, when the set holds no resident photon split of these
+ * sources (none yet, or dropped by cel_images_set_nelec or a new window).  A masked set and a row window are NOT refused here: a
+ * masked set holds a split only while CEL_OPT_HONOUR_MASK is on; that split puts no photon on a masked pixel, so none
+ * contributes.  Every other value of param outside 0-3 is refused. */
+enum {
+    CEL_SLICE_MOMENTS = 10,
+    CEL_MOMENTS_SPLIT_PIXELS = 4096
+};
 int cel_slice_sample(cel_images *img, cel_sources *src, int param, const int32_t *chain_ids, const double *dirs, int numdir,
                      int step_out, int max_steps_out, double sigma, double phi_max, uint64_t seed, int max_rounds,
                      double *x_out, double *llh_out, int64_t *stats);
