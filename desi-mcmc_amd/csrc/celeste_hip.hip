@@ -2256,6 +2256,90 @@ static int64_t chains_here(const int32_t *chain_ids, int64_t S) {
     return chain_ids ? (int64_t)std::count_if(chain_ids, chain_ids + S, [](int32_t id) { return id >= 0; }) : S;
 }
 
+// What the two-slot samplers share -- cel_slice_sample's params 0 / 1, the type move, the HMC step.  Every chain owns the rows
+// 2 s and 2 s + 1 of the proposal set im->sgen_prop; a round scores the P = 2 S slots against the resident split.  Here: the facts
+// of the call, the scoring arrays (carved from im->d_sgen behind the caller's own state), the upload, the readback of the flag
+// words (SliceFlag, k_slice_state.h) into the mailbox's pinned slot and the round's launches.
+struct SlotScorer {
+    cel_images *const im;
+    cel_ctx *const c = im->ctx;
+    const hipStream_t st = c->stream;
+    const int64_t S, P = 2 * S;
+    const int B = im->B;
+    const bool exact;                                  // the exact conditional: a cover test, a stamp mass and a term per slot
+    const bool mass_list;                              // ... with the running chains' mass jobs listed (otherwise all P B run)
+    const bool lists = c->variant != 0;                // block lists; CEL_OPT_KERNEL = 0 scores all P B jobs in one launch
+    const bool use_nz = im->split.nz_valid && lists;
+    const int ostr = lists ? PLL_PARTS : 1;            // slots per job in d_ll: the recurrence kernels always fill all four
+    cel_sources *prop = nullptr;
+    double *d_ll = nullptr, *d_mass = nullptr, *d_exact = nullptr;
+    int *d_owner = nullptr, *d_ids = nullptr, *d_list = nullptr, *d_list_nz = nullptr, *d_list_mass = nullptr, *d_flags = nullptr;
+    int64_t n_dense = P * B, n_nz = 0, n_mass = mass_list ? 0 : P * B;          // the round's blocks and mass jobs, as last read
+    int *const h = c->mail->sh.slice_flags;            // the flag words as last read, in the mailbox's pinned slot: h[SF_ERROR], ...
+
+    SlotScorer(cel_images *im_, int64_t S_, bool exact_, bool mass_list_) : im(im_), S(S_), exact(exact_), mass_list(mass_list_) {}
+
+    void take(Carver &k) {
+        const size_t n = (size_t)S, nl = lists ? 2 * n * B * PLL_PARTS : 0;
+        d_ll = k.take<double>(2 * n * B * ostr);
+        d_mass = exact ? k.take<double>(2 * n * B) : nullptr;            // the slots' stamp masses, per (slot, band)
+        d_exact = exact ? k.take<double>(2 * n) : nullptr;               // the exact conditional's term per slot (k_sg_exact_terms)
+        d_owner = k.take<int>(2 * n);
+        d_ids = k.take<int>(n);
+        d_list = k.take<int>(nl);                                        // the running chains' blocks: dense, at the photons
+        d_list_nz = k.take<int>(nl);
+        d_list_mass = mass_list ? k.take<int>(2 * n * B) : nullptr;      // ... and their mass jobs
+        d_flags = k.take<int>(SF_WORDS, 16);
+    }
+    // the proposal set (after the caller has carved im->d_sgen: its own state, then take)
+    int proposals() {
+        const int rc = ensure_proposals(c, im->sgen_prop, P, B);
+        if (!rc) prop = im->sgen_prop.get();
+        return rc;
+    }
+    // the call's directions (or none) and chain ids (or none); the flags cleared
+    int upload(double *d_dirs, const double *dirs, int64_t n_doubles, const int32_t *chain_ids) {
+        if (dirs) HIP_TRY(hipMemcpyAsync(d_dirs, dirs, sizeof(double) * n_doubles, hipMemcpyHostToDevice, st));
+        if (chain_ids) HIP_TRY(hipMemcpyAsync(d_ids, chain_ids, sizeof(int) * S, hipMemcpyHostToDevice, st));
+        if (dirs || chain_ids) HIP_TRY(hipStreamSynchronize(st));        // pageable sources must stay valid
+        HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(int) * SF_WORDS, st));
+        return CEL_OK;
+    }
+    // the first `words` flags into h, synchronised; the counts they carry are taken
+    int read_counts(int words) {
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h, d_flags, sizeof(int) * words, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (lists && words > SF_NZ_BLOCKS) { n_dense = h[SF_DENSE_BLOCKS]; n_nz = h[SF_NZ_BLOCKS]; }
+        if (mass_list && words > SF_MASS_JOBS) n_mass = h[SF_MASS_JOBS];
+        return CEL_OK;
+    }
+    // One round on the slots `d_owner` names: their records -- with their own boxes under the exact conditional (cover test, mass),
+    // otherwise the patch limits are fixed --, the cover test (its verdict in pri and d_owner), the likelihoods into d_ll, the
+    // exact terms into d_exact.  *ll_launches: the likelihood launches
+    int score(double *pri, int64_t *ll_launches = nullptr) {
+        const int rc = run_prep(im, prop, d_owner, exact ? 0 : 1);
+        if (rc) return rc;
+        if (exact)
+            hipLaunchKernelGGL(k_sg_cover, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, P, B, d_owner, pri, (const int4 *)im->d_boxes,
+                               (const int *)im->d_status, (const int4 *)im->d_snz);
+        const int n = launch_resident_ll(c, im, P, d_owner, d_ll, use_nz, {n_dense, d_list, nullptr}, {n_nz, d_list_nz, nullptr}, nullptr);
+        if (ll_launches) *ll_launches = n;
+        if (exact) launch_exact_terms(c, im, prop, P, d_owner, n_mass, d_list_mass, d_mass, d_exact);
+        return CEL_OK;
+    }
+};
+
+// what run_prep(im, src, d_live, nobox) hands k_prep, for the kernels that write a named point's records themselves (k_slice_step,
+// SliceFuse); taken after ensure_recs, when the tables stand
+static PrepArgs prep_args(const cel_images *im, const cel_sources *src, int nobox) {
+    PrepArgs pa;
+    pa.bands = im->d_bands; pa.B = im->B; pa.H = im->full_H; pa.W = im->W; pa.win_y0 = im->win_y0; pa.win_h = im->H; pa.S = src->S;
+    pa.type = src->d_type; pa.counts = src->d_counts; pa.shape = src->d_shape; pa.rsq_gal = rsq_galaxy();
+    pa.recs = im->d_recs; pa.boxes = im->d_boxes; pa.kind = im->d_kind; pa.status = im->d_status; pa.nobox = nobox;
+    return pa;
+}
+
 int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_ids, double sigma, uint64_t seed,
                         int max_rounds, double *radec_out, double *llh_out, int64_t *stats) {
     if (!im || !src) return fail(CEL_ERR_INVALID, "cel_slice_locations: null argument");
@@ -2308,17 +2392,12 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
         d_tick = k.take<int>(n);
         d_need_full = k.take<int>(n);
         d_need_live = k.take<int>(n);
-        d_flags = k.take<int>(13);      // [0] chains still running, [1] error bits, [2] likelihood evaluations so far, [3] rounds with work,
-                                        // [4] / [5] live dense / photon-list jobs of the batch, [6..7] byte counter, [8] / [9] dense / photon-list jobs;
-                                        // a call that may fuse rounds: [6] chains still running (k_slice_live_jobs, per batch: a fused round keeps no
-                                        // count), [11] / [12] evaluations / rounds with work (k_slice_bytes, at the end)
+        d_flags = k.take<int>(SFL_WORDS);       // (SliceFlag, k_slice_state.h)
         // the fused rounds' arguments, in device memory: [0] for the full lists, [1] for the live lists (they differ in `need`)
         d_fz = k.take<SliceFuse>(2, 16);
         return k.off;
     };
-    const size_t need = carve(nullptr);
-    HIP_TRY(im->d_slice.grow(need, need + need / 4, st));
-    carve(im->d_slice);
+    HIP_TRY(carved(im->d_slice, st, carve));
     { int rp = ensure_proposals(c, im->slice_prop, S, B); if (rp) return rp; }
     cel_sources *prop = im->slice_prop.get();
     // the proposal set: this catalogue with the locations rewritten every round
@@ -2330,7 +2409,7 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
         HIP_TRY(hipMemcpyAsync(d_ids, chain_ids, sizeof(int) * S, hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(int) * 13, st));      // [0..3] and [10]: see k_slice.h; the rest is set where it is used
+    HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(int) * SFL_WORDS, st));
     if (c->slice_fuse) HIP_TRY(hipMemsetAsync(d_tick, 0, sizeof(int) * 2 * S, st));    // the tickets and the full lists' block counts
     const unsigned g256 = (unsigned)((S + 255) / 256);
     hipLaunchKernelGGL(k_slice_init, dim3(g256), dim3(256), 0, st, ss, S, src->d_radec, chain_ids ? d_ids : (const int *)nullptr,
@@ -2347,16 +2426,17 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
                            (const int *)(use_nz ? im->d_nzmode : nullptr), (const int *)im->d_nnz, use_nz ? d_work_nz : (int *)nullptr,
                            (use_nz && c->slice_fuse) ? d_need_full : (int *)nullptr);
         // members compacted by the whole GPU, then ordered heaviest first by one block (the live-list arrays are free now)
-        HIP_TRY(hipMemsetAsync(d_flags + 8, 0, sizeof(int) * 2, st));
-        hipLaunchKernelGGL(k_list_members, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, st, d_work, nent, d_live, d_live_nz, d_flags + 8);
-        hipLaunchKernelGGL(k_order_compact, dim3(1), dim3(1024), 0, st, (const int *)d_live, (const int *)d_live_nz, (const int *)(d_flags + 8), d_jobs);
+        static_assert(SFL_NZ_JOBS == SFL_DENSE_JOBS + 1, "the two lengths are cleared and read as a pair");
+        HIP_TRY(hipMemsetAsync(d_flags + SFL_DENSE_JOBS, 0, sizeof(int) * 2, st));
+        hipLaunchKernelGGL(k_list_members, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, st, d_work, nent, d_live, d_live_nz, d_flags + SFL_DENSE_JOBS);
+        hipLaunchKernelGGL(k_order_compact, dim3(1), dim3(1024), 0, st, (const int *)d_live, (const int *)d_live_nz, (const int *)(d_flags + SFL_DENSE_JOBS), d_jobs);
         if (use_nz) {
-            hipLaunchKernelGGL(k_list_members, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, st, d_work_nz, nent, d_live, d_live_nz, d_flags + 9);
-            hipLaunchKernelGGL(k_order_compact, dim3(1), dim3(1024), 0, st, (const int *)d_live, (const int *)d_live_nz, (const int *)(d_flags + 9), d_jobs_nz);
+            hipLaunchKernelGGL(k_list_members, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, st, d_work_nz, nent, d_live, d_live_nz, d_flags + SFL_NZ_JOBS);
+            hipLaunchKernelGGL(k_order_compact, dim3(1), dim3(1024), 0, st, (const int *)d_live, (const int *)d_live_nz, (const int *)(d_flags + SFL_NZ_JOBS), d_jobs_nz);
         }
         int *h_cnt = c->mail->sh.slice_flags;
         h_cnt[1] = 0;
-        HIP_TRY(hipMemcpyAsync(h_cnt, d_flags + 8, sizeof(int) * (use_nz ? 2 : 1), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_cnt, d_flags + SFL_DENSE_JOBS, sizeof(int) * (use_nz ? 2 : 1), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         n_dense = h_cnt[0]; n_nz = use_nz ? h_cnt[1] : 0;
     }
@@ -2389,12 +2469,8 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
     // PLL_PARTS where the lists in between began to deal every job), and the kernels stop at the device's own count.
     int64_t live_dense = -1, live_nz = -1;                       // < 0: no live lists read yet
     int *h_flag_slot[2] = {c->mail->sh.slice_flags, c->mail->slice_flags1};
-    PrepArgs pa;                                                 // what run_prep(im, prop, d_owner, 1) hands k_prep
-    pa.bands = im->d_bands; pa.B = B; pa.H = im->full_H; pa.W = im->W; pa.win_y0 = im->win_y0; pa.win_h = im->H; pa.S = S;
-    pa.type = prop->d_type; pa.counts = prop->d_counts; pa.shape = prop->d_shape; pa.rsq_gal = rsq_galaxy();
-    pa.recs = im->d_recs; pa.boxes = im->d_boxes; pa.kind = im->d_kind; pa.status = im->d_status; pa.nobox = 1;
     if ((rc = ensure_recs(im, S * B > 0 ? S * B : 1))) return rc;   // (before the pointers are taken)
-    pa.recs = im->d_recs; pa.boxes = im->d_boxes; pa.kind = im->d_kind; pa.status = im->d_status;
+    const PrepArgs pa = prep_args(im, prop, 1);                  // what run_prep(im, prop, d_owner, 1) hands k_prep
     SliceFuse fz[2];        // the source of an asynchronous copy: alive until the stream is synchronised at the end of the call
     if (fuse_ok) {
         memset(fz, 0, sizeof(fz));
@@ -2429,8 +2505,8 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
                 prop->all_rows_changed(true);
                 // the first round's records; every later round's were written by the step kernel that named its points
                 if (queued == 0 && (rc = run_prep(im, prop, d_owner, 1))) return rc;      // the patch limits are fixed: no boxes
-                launch_resident_ll(c, im, S, d_owner, d_ll, use_nz, {gd, use_live ? d_live : d_jobs, use_live ? d_flags + 4 : nullptr},
-                                   {gn, use_live ? d_live_nz : d_jobs_nz, use_live ? d_flags + 5 : nullptr},
+                launch_resident_ll(c, im, S, d_owner, d_ll, use_nz, {gd, use_live ? d_live : d_jobs, use_live ? d_flags + SF_DENSE_BLOCKS : nullptr},
+                                   {gn, use_live ? d_live_nz : d_jobs_nz, use_live ? d_flags + SF_NZ_BLOCKS : nullptr},
                                    fused ? d_fz + (use_live ? 1 : 0) : nullptr);
                 if (!fused)
                 hipLaunchKernelGGL(k_slice_step, dim3((unsigned)((S + 63) / 64)), dim3(64 * B), 0, st, ss, S, B, ostr, d_ll, sigma, d_flags, (int)queued, prop->d_radec, d_owner,
@@ -2442,14 +2518,16 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
             if (c->variant != 0) {          // the running chains' blocks, for the next batch; few chains left: every job dealt
                 deal_of[slot] = (live * B <= SLICE_SPLIT_JOBS) ? 1 : 0;
                 if (fuse_ok) {                   // (otherwise the batch's last k_slice_step cleared the two counts)
-                    HIP_TRY(hipMemsetAsync(d_flags + 4, 0, sizeof(int) * 3, st));
+                    static_assert(SFL_LIVE_RUNNING == SF_DENSE_BLOCKS + 2, "the two counts and the running chains are cleared as one");
+                    HIP_TRY(hipMemsetAsync(d_flags + SF_DENSE_BLOCKS, 0, sizeof(int) * 3, st));
                     HIP_TRY(hipMemsetAsync(d_need_live, 0, sizeof(int) * S, st));
                 }
-                hipLaunchKernelGGL(k_slice_live_jobs, dim3((unsigned)((S * B + 255) / 256)), dim3(256), 0, st, ss, S, B, d_live, d_flags + 4,
-                                   (const int *)(use_nz ? im->d_nzmode : nullptr), d_live_nz, d_flags + 5, (const int *)im->d_nnz,
-                                   (const int4 *)im->d_snz, deal_of[slot], fuse_ok ? d_need_live : (int *)nullptr, fuse_ok ? d_flags + 6 : (int *)nullptr);
+                hipLaunchKernelGGL(k_slice_live_jobs, dim3((unsigned)((S * B + 255) / 256)), dim3(256), 0, st, ss, S, B, d_live, d_flags + SF_DENSE_BLOCKS,
+                                   (const int *)(use_nz ? im->d_nzmode : nullptr), d_live_nz, d_flags + SF_NZ_BLOCKS, (const int *)im->d_nnz,
+                                   (const int4 *)im->d_snz, deal_of[slot], fuse_ok ? d_need_live : (int *)nullptr,
+                                   fuse_ok ? d_flags + SFL_LIVE_RUNNING : (int *)nullptr);
             }
-            HIP_TRY(hipMemcpyAsync(h_flag_slot[slot], d_flags, sizeof(int) * 11, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(h_flag_slot[slot], d_flags, sizeof(int) * (SFL_RUNNING_ODD + 1), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipEventRecord(c->slice_ev[slot], st));
             HIP_TRY(hipGetLastError());
             last_par[slot] = (int)((queued - 1) & 1);
@@ -2460,14 +2538,15 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
         HIP_TRY(hipEventSynchronize(c->slice_ev[slot]));
         rb++;
         const int *hf = h_flag_slot[slot];
-        const int running = fuse_ok ? hf[6] : hf[last_par[slot] ? 10 : 0], err = hf[1];    // the batch's last round's slot; a call that may fuse: k_slice_live_jobs' count
+        // the batch's last round's word of the parity pair; a call that may fuse: k_slice_live_jobs' count
+        const int running = hf[fuse_ok ? SFL_LIVE_RUNNING : last_par[slot] ? SFL_RUNNING_ODD : SF_RUNNING], err = hf[SF_ERROR];
         live = running;
-        if (c->variant != 0) { live_dense = hf[4]; live_nz = hf[5]; deal_read = deal_of[slot]; }
+        if (c->variant != 0) { live_dense = hf[SF_DENSE_BLOCKS]; live_nz = hf[SF_NZ_BLOCKS]; deal_read = deal_of[slot]; }
         if (err & 3) {
             (void)hipStreamSynchronize(st);                      // the batch still in flight works on this call's buffers
             return fail(CEL_ERR_INVALID, (err & 1) ? "Slice sampler got a NaN" : "Slice sampler shrank to zero!");
         }
-        if (!fuse_ok) { evals = hf[2]; rounds = hf[3]; }
+        if (!fuse_ok) { evals = hf[SF_EVALS]; rounds = hf[SF_ROUNDS]; }
         if (running == 0) finished = true;                       // whatever is still queued scores nothing
         else if (queued >= max_rounds && rb == qb)
             return fail(CEL_ERR_INVALID, "cel_slice_locations: %d rounds without every chain finishing", max_rounds);
@@ -2478,15 +2557,15 @@ int cel_slice_locations(cel_images *im, cel_sources *src, const int32_t *chain_i
     src->all_rows_changed(false);
     if (radec_out) HIP_TRY(hipMemcpyAsync(radec_out, ss.x, sizeof(double) * 2 * S, hipMemcpyDeviceToHost, st));
     if (llh_out) HIP_TRY(hipMemcpyAsync(llh_out, ss.new_llh, sizeof(double) * S, hipMemcpyDeviceToHost, st));
-    unsigned long long *d_bytes = reinterpret_cast<unsigned long long *>(((uintptr_t)(d_flags + 6) + 7) & ~(uintptr_t)7);
+    unsigned long long *d_bytes = reinterpret_cast<unsigned long long *>(((uintptr_t)(d_flags + SFL_BYTES) + 7) & ~(uintptr_t)7);
     if (stats) {
         // algorithmic bytes of the call: a chain made 1 + steps[s] evaluations (the first direction's level, then one
         // per shrink step), each walking its photon rectangles
         HIP_TRY(hipMemsetAsync(d_bytes, 0, sizeof(unsigned long long), st));
         hipLaunchKernelGGL(k_slice_bytes, dim3(g256), dim3(256), 0, st, ss, S, B, (const int4 *)im->d_snz, d_bytes,
-                           (const int *)(use_nz ? im->d_nzmode : nullptr), (const int64_t *)im->d_nzoff, fuse_ok ? d_flags + 11 : (int *)nullptr);
+                           (const int *)(use_nz ? im->d_nzmode : nullptr), (const int64_t *)im->d_nzoff, fuse_ok ? d_flags + SFL_EVALS_END : (int *)nullptr);
         HIP_TRY(hipMemcpyAsync(&c->mail->sh.w.slice_bytes, d_bytes, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        if (fuse_ok) HIP_TRY(hipMemcpyAsync(h_flag_slot[1], d_flags + 11, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
+        if (fuse_ok) HIP_TRY(hipMemcpyAsync(h_flag_slot[1], d_flags + SFL_EVALS_END, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
     if (stats) {
@@ -2513,12 +2592,11 @@ static int slice_type_move(cel_images *im, cel_sources *src, const int32_t *chai
     const bool exact = c->slice_conditional == 1;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    const int ostr = (c->variant != 0) ? PLL_PARTS : 1;
-    const bool lists = c->variant != 0;
-    // one allocation, carved (Carver: once for the size, once for the pointers)
+    SlotScorer sc(im, S, exact, exact);
+    // one allocation, carved: the move's own state, then the scorer's arrays
     TypeMove tm;
-    double *d_dirs, *d_ll, *d_out, *d_mass = nullptr, *d_exact = nullptr;
-    int *d_owner, *d_ids, *d_list, *d_list_nz, *d_flags, *d_flag, *d_list_mass = nullptr;
+    double *d_dirs, *d_out;
+    int *d_flag;
     auto carve = [&](char *base) {
         Carver k{base};
         const size_t n = (size_t)S;
@@ -2526,67 +2604,43 @@ static int slice_type_move(cel_images *im, cel_sources *src, const int32_t *chai
         tm.h = k.take<double>(n);
         tm.pri = k.take<double>(2 * n);
         d_dirs = k.take<double>(5 * n);
-        d_ll = k.take<double>(2 * n * B * ostr);
-        if (exact) {
-            d_mass = k.take<double>(2 * n * B);               // the slots' stamp masses, per (slot, band)
-            d_exact = k.take<double>(2 * n);                  // the exact conditional's term per slot (k_sg_exact_terms)
-        }
         d_out = k.take<double>(6 * n);                        // the new type and shape per chain, then log alpha per chain
         d_flag = k.take<int>(n);                              // right behind d_out: one readback takes both
         tm.run = k.take<int>(n);
-        d_owner = k.take<int>(2 * n);
-        d_ids = k.take<int>(n);
-        d_list = k.take<int>(lists ? 2 * n * B * PLL_PARTS : 0);
-        d_list_nz = k.take<int>(lists ? 2 * n * B * PLL_PARTS : 0);
-        if (exact) d_list_mass = k.take<int>(2 * n * B);
-        d_flags = k.take<int>(8, 16);                         // [1] error bits, [4] / [5] dense / photon-list blocks, [6] mass jobs
+        sc.take(k);
         return k.off;
     };
-    const size_t need = carve(nullptr);
-    HIP_TRY(im->d_sgen.grow(need, need + need / 4, st));
-    carve(im->d_sgen);
-    { int rp = ensure_proposals(c, im->sgen_prop, 2 * S, B); if (rp) return rp; }
-    cel_sources *prop = im->sgen_prop.get();
-    const int64_t P = 2 * S;
+    HIP_TRY(carved(im->d_sgen, st, carve));
+    int rc = sc.proposals();
+    if (rc) return rc;
+    cel_sources *prop = sc.prop;
+    const int64_t P = sc.P;
+    const bool lists = sc.lists;
+    int *const d_owner = sc.d_owner, *const d_flags = sc.d_flags;
     if (S == 0) {
         if (stats) { stats[0] = 1; stats[1] = 0; stats[2] = 0; stats[3] = 0; }
         return CEL_OK;
     }
-    HIP_TRY(hipMemcpyAsync(d_dirs, dirs, sizeof(double) * 5 * S, hipMemcpyHostToDevice, st));
-    if (chain_ids) HIP_TRY(hipMemcpyAsync(d_ids, chain_ids, sizeof(int) * S, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));                        // pageable sources must stay valid
-    HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(int) * 8, st));
+    if ((rc = sc.upload(d_dirs, dirs, 5 * S, chain_ids))) return rc;
     const unsigned g256 = (unsigned)((S + 255) / 256), p256 = (unsigned)((P + 255) / 256), j256 = (unsigned)((S * B + 255) / 256);
     hipLaunchKernelGGL(k_tm_fill, dim3(p256), dim3(256), 0, st, tm, S, B, (const int *)src->d_type, (const double *)src->d_radec,
                        (const double *)src->d_counts, (const double *)src->d_shape, (const double *)d_dirs,
-                       chain_ids ? (const int *)d_ids : (const int *)nullptr, (const int64_t *)im->d_soff, (unsigned long long)seed,
+                       chain_ids ? (const int *)sc.d_ids : (const int *)nullptr, (const int64_t *)im->d_soff, (unsigned long long)seed,
                        prop->d_type, prop->d_radec, prop->d_counts, prop->d_shape, d_owner);
     prop->S = P;
     prop->all_rows_changed(true);
-    const bool use_nz = im->split.nz_valid && c->variant != 0;
-    int64_t n_dense = P * B, n_nz = 0, n_mass = 0;
-    int *h_flags = c->mail->sh.slice_flags;
     if (lists || exact) {
         const int64_t live = chains_here(chain_ids, S);
-        hipLaunchKernelGGL(k_tm_jobs, dim3(j256), dim3(256), 0, st, tm, S, B, (const int *)(use_nz ? im->d_nzmode : nullptr),
+        hipLaunchKernelGGL(k_tm_jobs, dim3(j256), dim3(256), 0, st, tm, S, B, (const int *)(sc.use_nz ? im->d_nzmode : nullptr),
                            (const int *)im->d_nnz, (const int4 *)im->d_snz, (live * 2 * B <= 8192) ? 1 : 0,
-                           lists ? d_list : (int *)nullptr, d_flags + 4, d_list_nz, d_flags + 5, d_list_mass, d_flags + 6);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * 7, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (lists) { n_dense = h_flags[4]; n_nz = h_flags[5]; }
-        if (exact) n_mass = h_flags[6];
+                           lists ? sc.d_list : (int *)nullptr, d_flags + SF_DENSE_BLOCKS, sc.d_list_nz, d_flags + SF_NZ_BLOCKS,
+                           sc.d_list_mass, d_flags + SF_MASS_JOBS);
+        if ((rc = sc.read_counts(SF_MASS_JOBS + 1))) return rc;
     }
-    // the slots' records, with their own boxes under the exact conditional (cover test, mass); otherwise the patch limits are fixed
-    int rc = run_prep(im, prop, d_owner, exact ? 0 : 1);
-    if (rc) return rc;
-    if (exact)
-        hipLaunchKernelGGL(k_sg_cover, dim3(p256), dim3(256), 0, st, P, B, d_owner, tm.pri, (const int4 *)im->d_boxes,
-                           (const int *)im->d_status, (const int4 *)im->d_snz);
-    const int64_t launches = launch_resident_ll(c, im, P, d_owner, d_ll, use_nz, {n_dense, d_list, nullptr}, {n_nz, d_list_nz, nullptr}, nullptr);
-    if (exact) launch_exact_terms(c, im, prop, P, d_owner, n_mass, d_list_mass, d_mass, d_exact);
-    hipLaunchKernelGGL(k_tm_decide, dim3(g256), dim3(256), 0, st, tm, S, B, ostr, (const double *)d_ll, (const double *)d_exact,
-                       (const double *)prop->d_shape, (int *)src->d_type, (double *)src->d_shape, d_out, d_flag, d_flags + 1);
+    int64_t launches = 0;
+    if ((rc = sc.score(tm.pri, &launches))) return rc;
+    hipLaunchKernelGGL(k_tm_decide, dim3(g256), dim3(256), 0, st, tm, S, B, sc.ostr, (const double *)sc.d_ll, (const double *)sc.d_exact,
+                       (const double *)prop->d_shape, (int *)src->d_type, (double *)src->d_shape, d_out, d_flag, d_flags + SF_ERROR);
     HIP_TRY(hipGetLastError());
     src->all_rows_changed(true);          // the catalogue on the device has new rows, types among them
     // one readback: the rows, log alpha and the flags lie one behind the other (the flags behind 6 S doubles)
@@ -2594,8 +2648,7 @@ static int slice_type_move(cel_images *im, cel_sources *src, const int32_t *chai
     std::vector<double> back((size_t)(6 * S + (S + 1) / 2));
     const size_t back_bytes = sizeof(double) * 6 * S + sizeof(int) * S;
     HIP_TRY(hipMemcpyAsync(back.data(), d_out, back_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = sc.read_counts(SF_ERROR + 1))) return rc;       // (synchronises: `back` is complete)
     const int *hf = reinterpret_cast<const int *>(back.data() + 6 * S);
     int64_t running = 0, accepted = 0;
     std::vector<int32_t> types((size_t)S);
@@ -2608,7 +2661,7 @@ static int slice_type_move(cel_images *im, cel_sources *src, const int32_t *chai
     if (x_out) memcpy(x_out, back.data(), sizeof(double) * 5 * S);
     if (llh_out) memcpy(llh_out, back.data() + 5 * S, sizeof(double) * S);
     if (stats) { stats[0] = 1; stats[1] = 2 * running; stats[2] = accepted; stats[3] = launches; }
-    if (h_flags[1] & 1)
+    if (sc.h[SF_ERROR] & 1)
         return fail(CEL_ERR_INVALID, "cel_slice_sample: the type move found a state outside its own conditional (its current row scores -inf)");
     return CEL_OK;
 }
@@ -2649,12 +2702,11 @@ static int slice_hmc(cel_images *im, cel_sources *src, const int32_t *chain_ids,
     }
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    const int ostr = (c->variant != 0) ? PLL_PARTS : 1;
-    const bool lists = c->variant != 0;
-    // one allocation, carved (Carver: once for the size, once for the pointers)
+    SlotScorer sc(im, S, exact, false);                       // q0 / qL are scored with every mass job: no list
+    // one allocation, carved: the step's own state, then the scorer's arrays
     Hmc hm;
-    double *d_dirs, *d_ll, *d_sums, *d_grad, *d_out, *d_mass = nullptr, *d_exact = nullptr, *d_msums = nullptr, *d_mg = nullptr, *d_cpri = nullptr;
-    int *d_owner, *d_owner2, *d_ids, *d_list, *d_list_nz, *d_flags, *d_flag;
+    double *d_dirs, *d_sums, *d_grad, *d_out, *d_msums = nullptr, *d_mg = nullptr, *d_cpri = nullptr;
+    int *d_owner, *d_flag;
     auto carve = [&](char *base) {
         Carver k{base};
         const size_t n = (size_t)S;
@@ -2666,7 +2718,6 @@ static int slice_hmc(cel_images *im, cel_sources *src, const int32_t *chain_ids,
         hm.k0 = k.take<double>(n);
         hm.pri = k.take<double>(2 * n);
         d_dirs = k.take<double>(2 * HMC_D * n);
-        d_ll = k.take<double>(2 * n * B * ostr);
         d_sums = k.take<double>((size_t)GRAD_NS * PGRAD_PARTS * n * B);      // k_patch_grad's sums per (chain, band, part)
         d_grad = k.take<double>(n * (7 + B));                                // the mode-8 rows
         d_out = k.take<double>((2 * HMC_D + 1) * n);          // q and the momentum per chain, then log alpha per chain
@@ -2674,62 +2725,47 @@ static int slice_hmc(cel_images *im, cel_sources *src, const int32_t *chain_ids,
         hm.nev = k.take<int>(n);
         hm.run = k.take<int>(n);
         hm.dead = k.take<int>(n);
-        d_owner = k.take<int>(n);
-        d_owner2 = k.take<int>(2 * n);
-        d_ids = k.take<int>(n);
-        d_list = k.take<int>(lists ? 2 * n * B * PLL_PARTS : 0);
-        d_list_nz = k.take<int>(lists ? 2 * n * B * PLL_PARTS : 0);
-        d_flags = k.take<int>(8, 16);                         // [1] error bits, [4] / [5] dense / photon-list blocks
+        d_owner = k.take<int>(n);                             // of the trajectory's one slot per chain
+        sc.take(k);                                           // (its sc.d_owner: of the two scored slots)
         if (exact) {
-            d_mass = k.take<double>(2 * n * B);               // the slots' stamp masses, per (slot, band)
-            d_exact = k.take<double>(2 * n);                  // the exact conditional's term per scored slot (k_sg_exact_terms)
             d_msums = k.take<double>((size_t)GRAD_NS * PGRAD_PARTS * n * B);     // k_mass_grad's sums per (chain, band, part)
             d_mg = k.take<double>(n * (7 + B));               // the chain rule on them
             d_cpri = k.take<double>(n);                       // k_sg_cover's flag per gradient evaluation (owner carries the verdict)
         }
         return k.off;
     };
-    const size_t need = carve(nullptr);
-    HIP_TRY(im->d_sgen.grow(need, need + need / 4, st));
-    carve(im->d_sgen);
-    { int rp = ensure_proposals(c, im->sgen_prop, 2 * S, B); if (rp) return rp; }
-    cel_sources *prop = im->sgen_prop.get();
-    const int64_t P = 2 * S;
+    HIP_TRY(carved(im->d_sgen, st, carve));
+    int rc = sc.proposals();
+    if (rc) return rc;
+    cel_sources *prop = sc.prop;
+    const int64_t P = sc.P;
+    double *const d_mass = sc.d_mass;
+    int *const d_flags = sc.d_flags;
     if (S == 0) {
         if (stats) { stats[0] = L; stats[1] = 0; stats[2] = 0; stats[3] = 0; }
         return CEL_OK;
     }
-    { int rr = ensure_recs(im, P * B); if (rr) return rr; }  // (the records of both proposal sets: nothing grows between the launches)
-    HIP_TRY(hipMemcpyAsync(d_dirs, dirs, sizeof(double) * 2 * HMC_D * S, hipMemcpyHostToDevice, st));
-    if (chain_ids) HIP_TRY(hipMemcpyAsync(d_ids, chain_ids, sizeof(int) * S, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));                        // pageable sources must stay valid
-    HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(int) * 8, st));
-    if (exact) HIP_TRY(hipMemsetAsync(d_exact, 0, sizeof(double) * 2 * S, st));      // (a slot that is not scored gets no term)
+    rc = ensure_recs(im, P * B);                              // (the records of both proposal sets: nothing grows between the launches)
+    if (rc || (rc = sc.upload(d_dirs, dirs, 2 * HMC_D * S, chain_ids))) return rc;
+    if (exact) HIP_TRY(hipMemsetAsync(sc.d_exact, 0, sizeof(double) * 2 * S, st));   // (a slot that is not scored gets no term)
     const unsigned g256 = (unsigned)((S + 255) / 256), j256 = (unsigned)((S * B + 255) / 256);
     hipLaunchKernelGGL(k_hmc_fill, dim3(g256), dim3(256), 0, st, hm, S, B, phi_max, (const int *)src->d_type, (const double *)src->d_radec,
                        (const double *)src->d_counts, (const double *)src->d_shape, (const double *)d_dirs,
-                       chain_ids ? (const int *)d_ids : (const int *)nullptr, (const int64_t *)im->d_soff, (unsigned long long)seed,
-                       prop->d_type, prop->d_radec, prop->d_counts, prop->d_shape, d_owner, d_flags + 1);
+                       chain_ids ? (const int *)sc.d_ids : (const int *)nullptr, (const int64_t *)im->d_soff, (unsigned long long)seed,
+                       prop->d_type, prop->d_radec, prop->d_counts, prop->d_shape, d_owner, d_flags + SF_ERROR);
     int64_t launches = 1;
-    const bool use_nz = im->split.nz_valid && c->variant != 0;
-    int64_t n_dense = P * B, n_nz = 0;
-    int *h_flags = c->mail->sh.slice_flags;
-    if (lists) {                                              // the two slots' blocks of every running chain (k_tm_jobs on this step's `run`)
+    if (sc.lists) {                                            // the two slots' blocks of every running chain (k_tm_jobs on this step's `run`)
         TypeMove view{nullptr, nullptr, nullptr, hm.run};
         const int64_t live = chains_here(chain_ids, S);
-        hipLaunchKernelGGL(k_tm_jobs, dim3(j256), dim3(256), 0, st, view, S, B, (const int *)(use_nz ? im->d_nzmode : nullptr),
-                           (const int *)im->d_nnz, (const int4 *)im->d_snz, (live * 2 * B <= 8192) ? 1 : 0, d_list, d_flags + 4,
-                           d_list_nz, d_flags + 5, (int *)nullptr, (int *)nullptr);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * 6, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        n_dense = h_flags[4]; n_nz = h_flags[5];
+        hipLaunchKernelGGL(k_tm_jobs, dim3(j256), dim3(256), 0, st, view, S, B, (const int *)(sc.use_nz ? im->d_nzmode : nullptr),
+                           (const int *)im->d_nnz, (const int4 *)im->d_snz, (live * 2 * B <= 8192) ? 1 : 0, sc.d_list, d_flags + SF_DENSE_BLOCKS,
+                           sc.d_list_nz, d_flags + SF_NZ_BLOCKS, (int *)nullptr, (int *)nullptr);
+        if ((rc = sc.read_counts(SF_NZ_BLOCKS + 1))) return rc;
         launches++;
     }
     // L + 1 gradients, a step behind each but the last: nothing here depends on what the device finds
     // (their route -- the dense patches or the photon lists -- is chosen once for the call: grad_at_photons)
     const bool grad_nz = grad_at_photons(im, true);
-    int rc = CEL_OK;
     for (int l = 0; l <= L; l++) {
         prop->S = S;
         prop->all_rows_changed(true);
@@ -2773,22 +2809,14 @@ static int slice_hmc(cel_images *im, cel_sources *src, const int32_t *chain_ids,
     }
     hipLaunchKernelGGL(k_hmc_slots, dim3(g256), dim3(256), 0, st, hm, S, B, eps, phi_max, (const int *)src->d_type, (const double *)src->d_radec,
                        (const double *)src->d_counts, (const double *)src->d_shape, (const double *)d_grad, prop->d_type, prop->d_radec,
-                       prop->d_counts, prop->d_shape, d_owner2);
+                       prop->d_counts, prop->d_shape, sc.d_owner);
     prop->S = P;
     prop->all_rows_changed(true);
-    if ((rc = run_prep(im, prop, d_owner2, exact ? 0 : 1))) return rc;
-    if (exact) {                     // the two scored slots get their cover test ...
-        hipLaunchKernelGGL(k_sg_cover, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, P, B, d_owner2, hm.pri, (const int4 *)im->d_boxes,
-                           (const int *)im->d_status, (const int4 *)im->d_snz);
-        launches++;
-    }
-    launches += 2 + launch_resident_ll(c, im, P, d_owner2, d_ll, use_nz, {n_dense, d_list, nullptr}, {n_nz, d_list_nz, nullptr}, nullptr);
-    if (exact) {                     // ... and their e
-        launch_exact_terms(c, im, prop, P, d_owner2, P * B, nullptr, d_mass, d_exact);
-        launches += 2;
-    }
-    hipLaunchKernelGGL(k_hmc_decide, dim3(g256), dim3(256), 0, st, hm, S, B, ostr, (const double *)d_ll, (const double *)d_exact, (const int *)src->d_type,
-                       (double *)src->d_radec, (double *)src->d_shape, d_out, d_flag, d_flags + 1);
+    int64_t ll_launches = 0;         // the two scored slots: records; exact: their cover test, every mass job and the terms
+    if ((rc = sc.score(hm.pri, &ll_launches))) return rc;
+    launches += 2 + ll_launches + (exact ? 3 : 0);            // (k_hmc_slots and k_prep; k_sg_cover, the mass kernel, k_sg_exact_terms)
+    hipLaunchKernelGGL(k_hmc_decide, dim3(g256), dim3(256), 0, st, hm, S, B, sc.ostr, (const double *)sc.d_ll, (const double *)sc.d_exact,
+                       (const int *)src->d_type, (double *)src->d_radec, (double *)src->d_shape, d_out, d_flag, d_flags + SF_ERROR);
     launches++;
     HIP_TRY(hipGetLastError());
     src->all_rows_changed(false);         // the catalogue on the device has new locations and shapes; the types stand
@@ -2797,8 +2825,7 @@ static int slice_hmc(cel_images *im, cel_sources *src, const int32_t *chain_ids,
     const int64_t nd = (2 * HMC_D + 1) * S;
     std::vector<double> back((size_t)(nd + S));
     HIP_TRY(hipMemcpyAsync(back.data(), d_out, sizeof(double) * nd + sizeof(int) * 2 * S, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = sc.read_counts(SF_ERROR + 1))) return rc;       // (synchronises: `back` is complete)
     const int *hf = reinterpret_cast<const int *>(back.data() + nd), *hn = hf + S;
     int64_t evals = 0, accepted = 0;
     for (int64_t s = 0; s < S; s++) {
@@ -2808,7 +2835,7 @@ static int slice_hmc(cel_images *im, cel_sources *src, const int32_t *chain_ids,
     if (x_out) memcpy(x_out, back.data(), sizeof(double) * 2 * HMC_D * S);
     if (llh_out) memcpy(llh_out, back.data() + 2 * HMC_D * S, sizeof(double) * S);
     if (stats) { stats[0] = L; stats[1] = evals; stats[2] = accepted; stats[3] = launches; }
-    if (h_flags[1] & 1)
+    if (sc.h[SF_ERROR] & 1)
         return fail(CEL_ERR_INVALID, "cel_slice_sample: the HMC step found a state outside its own conditional (its current row scores -inf)");
     return CEL_OK;
 }
@@ -2845,12 +2872,11 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
     hipStream_t st = c->stream;
     const int B = im->B;
     const int64_t S = src->S;
-    const int ostr = (c->variant != 0) ? PLL_PARTS : 1;
-    // one allocation, carved (Carver: once for the size, once for the pointers)
+    SlotScorer sc(im, S, exact, exact);
+    // one allocation, carved: the sampler's own state, then the scorer's arrays
     SliceGen g;
     SliceState rs;
-    double *d_dirs, *d_ll, *d_mass = nullptr, *d_exact = nullptr;
-    int *d_owner, *d_ids, *d_list, *d_list_nz, *d_flags, *d_list_mass = nullptr;
+    double *d_dirs;
     auto carve = [&](char *base) {
         Carver k{base};
         const size_t n = (size_t)S;
@@ -2872,35 +2898,22 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
         g.acc_U = k.take<double>(n);
         g.pri = k.take<double>(2 * n);
         d_dirs = k.take<double>(n * ndir * D);
-        d_ll = k.take<double>(2 * n * B * ostr);
         g.phase = k.take<int>(n);
         g.kdir = k.take<int>(n);
         g.l_out = k.take<int>(n);
         g.u_out = k.take<int>(n);
         g.order = k.take<int>(n * D);
-        d_owner = k.take<int>(2 * n);
-        d_ids = k.take<int>(n);
-        d_list = k.take<int>(2 * n * B * PLL_PARTS);          // the running chains' blocks (k_sg_live_jobs): dense, at the photons
-        d_list_nz = k.take<int>(2 * n * B * PLL_PARTS);
-        d_flags = k.take<int>(8, 16);
-        if (exact) {
-            d_mass = k.take<double>(2 * n * B);               // the proposals' stamp masses, per (slot, band)
-            d_exact = k.take<double>(2 * n);                  // the exact conditional's term per slot (k_sg_exact_terms)
-            d_list_mass = k.take<int>(2 * n * B);             // the running chains' mass jobs (k_sg_mass_jobs)
-        }
+        sc.take(k);
         return k.off;
     };
-    const size_t need = carve(nullptr);
-    HIP_TRY(im->d_sgen.grow(need, need + need / 4, st));
-    carve(im->d_sgen);
-    { int rp = ensure_proposals(c, im->sgen_prop, 2 * S, B); if (rp) return rp; }
-    cel_sources *prop = im->sgen_prop.get();
+    HIP_TRY(carved(im->d_sgen, st, carve));
+    int rc = sc.proposals();
+    if (rc) return rc;
+    cel_sources *prop = sc.prop;
+    int *const d_owner = sc.d_owner, *const d_flags = sc.d_flags;
     g.D = D; g.ndir = ndir; g.compwise = compwise; g.step_out = step_out ? 1 : 0; g.max_steps_out = max_steps_out; g.param = param;
     g.sigma = sigma; g.phi_max = param ? phi_max : 0.0; g.dirs = compwise ? nullptr : d_dirs;
-    if (!compwise) HIP_TRY(hipMemcpyAsync(d_dirs, dirs, sizeof(double) * S * ndir * D, hipMemcpyHostToDevice, st));
-    if (chain_ids) HIP_TRY(hipMemcpyAsync(d_ids, chain_ids, sizeof(int) * S, hipMemcpyHostToDevice, st));
-    if (!compwise || chain_ids) HIP_TRY(hipStreamSynchronize(st));          // pageable sources must stay valid
-    HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(int) * 8, st));
+    if ((rc = sc.upload(d_dirs, dirs, S * ndir * D, chain_ids))) return rc;      // (compwise: no dirs)
     const unsigned g256 = (unsigned)((S + 255) / 256);
     // the proposal set: every chain's source twice, the sampled parameter rewritten every round
     hipLaunchKernelGGL(k_sg_fill, dim3((unsigned)((2 * S + 255) / 256)), dim3(256), 0, st, S, B, (const int *)src->d_type,
@@ -2908,72 +2921,53 @@ int cel_slice_sample(cel_images *im, cel_sources *src, int param, const int32_t 
                        prop->d_type, prop->d_radec, prop->d_counts, prop->d_shape);
     prop->S = 2 * S;
     hipLaunchKernelGGL(k_sg_init, dim3(g256), dim3(256), 0, st, g, rs, S, (const double *)(param ? src->d_shape : src->d_radec),
-                       chain_ids ? (const int *)d_ids : (const int *)nullptr, (const int64_t *)im->d_soff, B, (const int *)src->d_type,
+                       chain_ids ? (const int *)sc.d_ids : (const int *)nullptr, (const int64_t *)im->d_soff, B, (const int *)src->d_type,
                        (unsigned long long)seed);
-    const bool use_nz = im->split.nz_valid && c->variant != 0;
     int64_t rounds = 0, evals = 0, queued = 0;
-    int *h_flags = c->mail->sh.slice_flags;
-    int rc = CEL_OK;
-    const int64_t P = 2 * S;
     const int BATCH = 4;
     const int64_t DEAL_ALL_BELOW = 8192;          // (chain, slot, band) jobs: fewer than the GPU has wave slots for -- deal every job
     int64_t live = S;                             // chains running at the last readback
-    // the first batch's block lists (every later one is built behind the batch before it); their counts come back now
-    int64_t n_dense = P * B, n_nz = 0, n_mass = 0;
-    const int nflags = exact ? 7 : 6;             // flag 6: the mass kernel's job count
-    if (c->variant != 0)
-        hipLaunchKernelGGL(k_sg_live_jobs, dim3((unsigned)((S * B + 255) / 256)), dim3(256), 0, st, g, S, B,
-                           (const int *)(use_nz ? im->d_nzmode : nullptr), (const int *)im->d_nnz, (const int4 *)im->d_snz, 0,
-                           d_list, d_flags + 4, d_list_nz, d_flags + 5);
-    if (exact)
-        hipLaunchKernelGGL(k_sg_mass_jobs, dim3((unsigned)((S * B + 255) / 256)), dim3(256), 0, st, g, S, B, d_list_mass, d_flags + 6);
-    if (c->variant != 0 || exact) {
-        HIP_TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * nflags, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (c->variant != 0) { n_dense = h_flags[4]; n_nz = h_flags[5]; }
-        if (exact) n_mass = h_flags[6];
-    }
+    const int nflags = (exact ? SF_MASS_JOBS : SF_NZ_BLOCKS) + 1;
+    // the running chains' blocks and mass jobs: the first batch's now (their counts come back at once), every later batch's behind
+    // the batch before it (the flags were cleared by the upload, then by `again`)
+    auto list_jobs = [&](bool again, int deal_all) {
+        const unsigned j256 = (unsigned)((S * B + 255) / 256);
+        if (sc.lists) {
+            if (again) HIP_TRY(hipMemsetAsync(d_flags + SF_DENSE_BLOCKS, 0, sizeof(int) * 2, st));
+            hipLaunchKernelGGL(k_sg_live_jobs, dim3(j256), dim3(256), 0, st, g, S, B, (const int *)(sc.use_nz ? im->d_nzmode : nullptr),
+                               (const int *)im->d_nnz, (const int4 *)im->d_snz, deal_all, sc.d_list, d_flags + SF_DENSE_BLOCKS, sc.d_list_nz,
+                               d_flags + SF_NZ_BLOCKS);
+        }
+        if (exact) {
+            if (again) HIP_TRY(hipMemsetAsync(d_flags + SF_MASS_JOBS, 0, sizeof(int), st));
+            hipLaunchKernelGGL(k_sg_mass_jobs, dim3(j256), dim3(256), 0, st, g, S, B, sc.d_list_mass, d_flags + SF_MASS_JOBS);
+        }
+        return (int)CEL_OK;
+    };
+    if ((rc = list_jobs(false, 0))) return rc;
+    if ((sc.lists || exact) && (rc = sc.read_counts(nflags))) return rc;
     for (;;) {
         const int nb = (int)std::min<int64_t>(BATCH, (int64_t)max_rounds - queued);
         for (int k = 0; k < nb; k++) {
             hipLaunchKernelGGL(k_sg_propose, dim3(g256), dim3(256), 0, st, g, rs, S, param ? prop->d_shape : prop->d_radec, d_owner, d_flags,
                                queued == 0 ? 1 : 0);
             prop->all_rows_changed(true);
-            // the patch limits are fixed: no boxes -- but the exact conditional needs the proposals' own (cover test, mass)
-            if ((rc = run_prep(im, prop, d_owner, exact ? 0 : 1))) return rc;
+            if ((rc = sc.score(g.pri))) return rc;
             if (exact)
-                hipLaunchKernelGGL(k_sg_cover, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, P, B, d_owner, g.pri,
-                                   (const int4 *)im->d_boxes, (const int *)im->d_status, (const int4 *)im->d_snz);
-            launch_resident_ll(c, im, P, d_owner, d_ll, use_nz, {n_dense, d_list, nullptr}, {n_nz, d_list_nz, nullptr}, nullptr);
-            if (exact) {
-                launch_exact_terms(c, im, prop, P, d_owner, n_mass, d_list_mass, d_mass, d_exact);
-                hipLaunchKernelGGL(k_sg_consume_exact, dim3(g256), dim3(256), 0, st, g, rs, S, B, ostr, (const double *)d_ll, d_flags,
-                                   (const double *)d_exact);
-            } else
-                hipLaunchKernelGGL(k_sg_consume, dim3(g256), dim3(256), 0, st, g, rs, S, B, ostr, (const double *)d_ll, d_flags);
+                hipLaunchKernelGGL(k_sg_consume_exact, dim3(g256), dim3(256), 0, st, g, rs, S, B, sc.ostr, (const double *)sc.d_ll, d_flags,
+                                   (const double *)sc.d_exact);
+            else
+                hipLaunchKernelGGL(k_sg_consume, dim3(g256), dim3(256), 0, st, g, rs, S, B, sc.ostr, (const double *)sc.d_ll, d_flags);
             queued++;
         }
-        if (c->variant != 0) {          // the next batch's blocks: the chains still running now
-            HIP_TRY(hipMemsetAsync(d_flags + 4, 0, sizeof(int) * 2, st));
-            hipLaunchKernelGGL(k_sg_live_jobs, dim3((unsigned)((S * B + 255) / 256)), dim3(256), 0, st, g, S, B,
-                               (const int *)(use_nz ? im->d_nzmode : nullptr), (const int *)im->d_nnz, (const int4 *)im->d_snz,
-                               (live * 2 * B <= DEAL_ALL_BELOW) ? 1 : 0, d_list, d_flags + 4, d_list_nz, d_flags + 5);
-        }
-        if (exact) {
-            HIP_TRY(hipMemsetAsync(d_flags + 6, 0, sizeof(int), st));
-            hipLaunchKernelGGL(k_sg_mass_jobs, dim3((unsigned)((S * B + 255) / 256)), dim3(256), 0, st, g, S, B, d_list_mass, d_flags + 6);
-        }
-        HIP_TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * nflags, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(st));
-        const int running = h_flags[0], err = h_flags[1];
-        if (c->variant != 0) { n_dense = h_flags[4]; n_nz = h_flags[5]; }
-        if (exact) n_mass = h_flags[6];
+        // the next batch's blocks: the chains still running now
+        if ((rc = list_jobs(true, (live * 2 * B <= DEAL_ALL_BELOW) ? 1 : 0)) || (rc = sc.read_counts(nflags))) return rc;
+        const int running = sc.h[SF_RUNNING], err = sc.h[SF_ERROR];
         live = running;
         if (err & 1) return fail(CEL_ERR_INVALID, "Slice sampler got a NaN");
         if (err & 2) return fail(CEL_ERR_INVALID, "Slice sampler shrank to zero!");
-        evals = h_flags[2];
-        rounds = h_flags[3];
+        evals = sc.h[SF_EVALS];
+        rounds = sc.h[SF_ROUNDS];
         if (running == 0) break;
         if (queued >= max_rounds) return fail(CEL_ERR_INVALID, "cel_slice_sample: %d rounds without every chain finishing", max_rounds);
     }

@@ -89,3 +89,12 @@ struct Carver {
         return r;
     }
 };
+
+// ... in a grow-only buffer: `carve(base)` names the arrays over a Carver{base} and returns its `off`.  The buffer grows with a
+// quarter to spare; a failed grow leaves every pointer null.
+template <class F> hipError_t carved(DevBuf<char> &buf, hipStream_t stream, F &&carve) {
+    const size_t need = carve(static_cast<char *>(nullptr));
+    const hipError_t e = buf.grow((int64_t)need, (int64_t)(need + need / 4), stream);
+    if (e == hipSuccess) carve(buf.get());
+    return e;
+}

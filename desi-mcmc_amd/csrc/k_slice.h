@@ -127,17 +127,11 @@ k_slice_init(SliceState st, int64_t S, const double *__restrict__ radec, const i
     owner[s] = has_patch ? (int)s : -1;
 }
 
-// Flags of a call (ints): [0] / [10] chains still running after the last even / odd round, [1] error bits, [2] likelihood
-// evaluations so far, [3] rounds that had a chain to score.  The host queues rounds in batches and reads the flags once per
-// batch, so the device counts: round r's consume kernel adds its running chains to slot r & 1, and -- the other slot holding
-// the complete count of round r - 1 -- books round r as a round with work when that count is positive, then clears it for
-// round r + 1.
-
 // the first round of a call: every chain's first point
 __global__ void __launch_bounds__(256)
 k_slice_propose(SliceState st, int64_t S, double *__restrict__ prop_radec, int *__restrict__ owner, int *__restrict__ flags) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s == 0) { flags[3] += 1; flags[0] = 0; flags[10] = 0; }
+    if (s == 0) { flags[SF_ROUNDS] += 1; flags[SF_RUNNING] = 0; flags[SFL_RUNNING_ODD] = 0; }
     if (s >= S) return;
     sl_propose_chain(st, s, prop_radec, owner);
 }
@@ -151,7 +145,7 @@ __global__ void __launch_bounds__(1024)
 k_slice_step(SliceState st, int64_t S, int B, int nparts /* blocks per (chain, band) job: their partial sums are added first, in order */,
              const double *__restrict__ ll_pb, double sigma, int *__restrict__ flags, int round,
              double *__restrict__ prop_radec, int *__restrict__ owner,
-             int zero_live /* the last round of a batch: flags[4], flags[5] -- the live lists' lengths, which this batch's likelihood launches
+             int zero_live /* the last round of a batch: SF_DENSE_BLOCKS, SF_NZ_BLOCKS -- the live lists' lengths, which this batch's likelihood launches
                               have read -- are cleared for k_slice_live_jobs, instead of a fill launch of their own (13 per sweep) */,
              PrepArgs pa /* pa.recs != nullptr: the named point's records (k_prep's own arithmetic, prep_one) are written here too --
                             the round's k_prep launch, 7 us of kernel and as much of queue, is gone */) {
@@ -160,19 +154,19 @@ k_slice_step(SliceState st, int64_t S, int B, int nparts /* blocks per (chain, b
     __shared__ int s_own[64];
     const bool chain_thread = threadIdx.x < 64;
     const int64_t s = chain_thread ? (int64_t)blockIdx.x * 64 + threadIdx.x : S;        // (the other waves: no chain)
-    int *const n_active = flags + ((round & 1) ? 10 : 0);
-    int *const err = flags + 1;
-    if (s == 0 && zero_live) { flags[4] = 0; flags[5] = 0; }
+    int *const n_active = flags + ((round & 1) ? SFL_RUNNING_ODD : SF_RUNNING);
+    int *const err = flags + SF_ERROR;
+    if (s == 0 && zero_live) { flags[SF_DENSE_BLOCKS] = 0; flags[SF_NZ_BLOCKS] = 0; }
     if (s == 0 && round > 0) {
-        int *const prev = flags + ((round & 1) ? 0 : 10);        // complete: round - 1's kernel has finished
-        if (*prev > 0) flags[3] += 1;
+        int *const prev = flags + ((round & 1) ? SF_RUNNING : SFL_RUNNING_ODD);        // complete: round - 1's kernel has finished
+        if (*prev > 0) flags[SF_ROUNDS] += 1;
         *prev = 0;                                               // round + 1 adds here
     }
     bool active = false, scored = false;
     if (s < S) scored = sl_consume_chain(st, s, B, nparts, ll_pb, sigma, err, active);
     const unsigned long long m = __ballot(active), me = __ballot(scored);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_active, __popcll(m));
-    if ((threadIdx.x & 63) == 0 && me) atomicAdd(err + 1, __popcll(me));         // evaluations so far (int: < 2^31 per call)
+    if ((threadIdx.x & 63) == 0 && me) atomicAdd(flags + SF_EVALS, __popcll(me));  // evaluations so far (int: < 2^31 per call)
     if (chain_thread) s_own[threadIdx.x] = -1;
     if (s < S) {
         sl_propose_chain(st, s, prop_radec, owner);                              // the next round's point (a finished chain retires)

@@ -105,8 +105,8 @@ k_sg_propose(SliceGen g, SliceState rs, int64_t S, double *__restrict__ prop /* 
 #pragma clang fp contract(off)
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s == 0) {
-        if (first || flags[0] > 0) flags[3] += 1;          // rounds that had a chain to score
-        flags[0] = 0;
+        if (first || flags[SF_RUNNING] > 0) flags[SF_ROUNDS] += 1;
+        flags[SF_RUNNING] = 0;
     }
     if (s >= S) return;
     const int ph = g.phase[s];
@@ -200,7 +200,7 @@ __device__ __forceinline__ void sg_consume(const SliceGen &g, const SliceState &
                     sg_enter_shrink(g, s);
                 }
             } else if (ph == SG_SHRINK) {                                        // :173-190
-                if (v[0] != v[0]) atomicOr(flags + 1, 1);                        // "Slice sampler got a NaN"
+                if (v[0] != v[0]) atomicOr(flags + SF_ERROR, 1);                        // "Slice sampler got a NaN"
                 const double z = g.new_z[s];
                 if (v[0] > g.llh_s[s]) {
                     g.new_llh[s] = v[0];
@@ -216,7 +216,7 @@ __device__ __forceinline__ void sg_consume(const SliceGen &g, const SliceState &
                 } else if (z > 0.0) {
                     g.upper[s] = z;
                 } else {
-                    atomicOr(flags + 1, 2);                                      // "Slice sampler shrank to zero!"
+                    atomicOr(flags + SF_ERROR, 2);                                      // "Slice sampler shrank to zero!"
                     g.phase[s] = SG_FINAL;
                 }
             } else if (ph == SG_ACCEPT) {
@@ -246,9 +246,9 @@ __device__ __forceinline__ void sg_consume(const SliceGen &g, const SliceState &
         }
     }
     const unsigned long long m = __ballot(active);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(flags, __popcll(m));
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(flags + SF_RUNNING, __popcll(m));
     for (int o = 32; o > 0; o >>= 1) scored += __shfl_xor(scored, o);
-    if ((threadIdx.x & 63) == 0 && scored) atomicAdd(flags + 2, scored);          // evaluations so far
+    if ((threadIdx.x & 63) == 0 && scored) atomicAdd(flags + SF_EVALS, scored);
 }
 
 __global__ void __launch_bounds__(256)

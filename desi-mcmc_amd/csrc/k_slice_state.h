@@ -10,6 +10,30 @@
 #define SL_SHRINK 4
 #define SL_FINAL 7
 
+// The words of a sampler's `flags` array (ints in device memory, zeroed by the host when a call starts), for the host and the
+// kernels alike.  The host queues rounds in batches and reads the flags once per batch, so the device counts.
+enum SliceFlag {
+    SF_RUNNING = 0,          // chains still running after the last round (k_sg_consume adds, k_sg_propose clears)
+    SF_ERROR = 1,            // error bits: 1 a NaN, 2 shrank to zero; type move and HMC step: 1 the current row scores -inf
+    SF_EVALS = 2,            // likelihood evaluations so far
+    SF_ROUNDS = 3,           // rounds that had a chain to score
+    SF_DENSE_BLOCKS = 4,     // the next launches' blocks: of the jobs scored densely ...
+    SF_NZ_BLOCKS = 5,        // ... and at their photons (k_sg_live_jobs, k_tm_jobs, k_slice_live_jobs)
+    SF_MASS_JOBS = 6,        // the two-slot samplers' mass jobs (k_sg_mass_jobs, k_tm_jobs); cel_slice_locations uses the word otherwise
+    SF_WORDS = 8,            // the two-slot samplers' array
+    // cel_slice_locations.  Its running count has a parity pair: round r's k_slice_step adds its running chains to
+    // SF_RUNNING (r even) or SFL_RUNNING_ODD and -- the other word holding the complete count of round r - 1 -- books round r
+    // as a round with work when that count is positive, then clears it for round r + 1.
+    SFL_LIVE_RUNNING = 6,    // a call that may fuse rounds: chains still running (k_slice_live_jobs, per batch: a fused round keeps no count)
+    SFL_BYTES = 6,           // [6..7], once the last batch has been read: k_slice_bytes' 8-byte counter
+    SFL_DENSE_JOBS = 8,      // the full lists' lengths: dense ...
+    SFL_NZ_JOBS = 9,         // ... and photon-list blocks (k_list_members)
+    SFL_RUNNING_ODD = 10,    // SF_RUNNING's partner; a batch's readback ends here
+    SFL_EVALS_END = 11,      // a call that may fuse rounds: evaluations and ...
+    SFL_ROUNDS_END = 12,     // ... rounds with work, counted at the end (k_slice_bytes)
+    SFL_WORDS = 13
+};
+
 struct SliceState {            // SoA over chains
     unsigned long long *key, *count;
     double *x;                 // current location (ra, dec), 2 per chain
@@ -139,7 +163,7 @@ struct SliceFuse {
     const double *ll_pb;       // the slots of every (chain, band) job, nparts each
     int nparts, B;
     double sigma;
-    int *flags;                // [1] error bits
+    int *flags;                // (SF_ERROR is written)
     double *prop_radec;
     int *owner;
     PrepArgs pa;
@@ -165,7 +189,7 @@ __device__ __forceinline__ void sl_fused_step(const SliceFuse &fz, int64_t p, in
     if (lane == 0) {
         __hip_atomic_store(&fz.tick[p], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // for the next round
         bool active;
-        sl_consume_chain(fz.st, p, fz.B, fz.nparts, fz.ll_pb, fz.sigma, fz.flags + 1, active, true);
+        sl_consume_chain(fz.st, p, fz.B, fz.nparts, fz.ll_pb, fz.sigma, fz.flags + SF_ERROR, active, true);
         sl_propose_chain(fz.st, p, fz.prop_radec, fz.owner);
         ra = fz.prop_radec[2 * p]; dec = fz.prop_radec[2 * p + 1]; own = fz.owner[p];
     }

@@ -176,7 +176,23 @@ def _log_u(seed, ids):
 @pytest.mark.parametrize("L", [1, 3])
 @pytest.mark.parametrize("phi_max", [PHI_MAX, 0.0])
 def test_restated_from_public_calls(scene, L, phi_max):
-    sc = scene
+    _restated_step(scene, L, phi_max)
+
+
+@gpu
+def test_the_direct_kernel_backs_the_step(scene):
+    """1., CEL_OPT_KERNEL = 0: no block lists, k_patch_ll<int> over all 2 S B jobs of q0 / qL; the restatement is taken under the
+    same option, so the bar stands"""
+    L = scene.L
+    before = scene.ctx.get_option(L.CEL_OPT_KERNEL)
+    scene.ctx.set_kernel("direct")
+    try:
+        _restated_step(scene, 1, PHI_MAX)
+    finally:
+        scene.ctx.set_option(L.CEL_OPT_KERNEL, before)
+
+
+def _restated_step(sc, L, phi_max):
     eps, seed = 0.4, 21 + L
     imass = sc.default_imass()
     imass[C_FLOOR, 3] *= 1e-4                 # (the prior's wall at sigma = 0.02 is steep: keep the trajectory inside the support)
